@@ -2,7 +2,8 @@
 """
 bench.py -- headline benchmark of the MI355X lsp-dsp-units hot path.
 
-    python bench.py --gpus N --steps K --warmup W [--workload biquad]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W --full [--workload biquad]
 
 A "step" is one pass of the hot path over one batch of synthetic input that is already resident in HBM:
   biquad    : BASELINE.json configs[1] -- 1024 channels x 4096-sample block through an 8-stage biquad
@@ -10,7 +11,13 @@ A "step" is one pass of the hot path over one batch of synthetic input that is a
 With N > 1 (launched by torch.distributed.run, one process per GPU) the channels are sharded: every rank
 owns its own 1024 channels (weak scaling, no data-path collective: channels are independent).
 
-Prints ONE JSON line on rank 0.  After the W warm-up steps the K-step region (barrier + synchronize on both sides,
+Prints ONE JSON line on rank 0.  A plain run measures the headline alone: a second of its launches on a scratch bank (the
+shader clock settles), W warm-up steps through the timed path, then ONE timed region of exactly K steps (barrier +
+synchronize on both sides, max over ranks); `value` is whole-job Msamples/s of that region and `ms_per_step` its time
+over K.  `--dump-outputs DIR` then writes the output blocks of the last timed step (DIR/biquad_out.npy); the inputs are
+seeded, so the same arguments give the same inputs on every run and every build.
+
+With --full, everything else as well.  After the W warm-up steps the K-step region (barrier + synchronize on both sides,
 max over ranks) is timed `--regions` times back to back and `value` is whole-job Msamples/s of the MEDIAN region, so
 a short region (the driver's K = 20 is a quarter of a millisecond) does not rest on one sample; every region's time is
 in `region_ms`.  The K steady-state calls of a region are captured once into a hipGraph and replayed (the calls take
@@ -43,12 +50,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--workload", default="all", choices=["all", "biquad", "convolver", "equalizer", "spectral", "stft", "crossover", "splitter", "loudness", "dynfilter"],
-                    help="all = headline biquad line with the convolver result attached under \"convolver\"")
+                    help="all = headline biquad line, with --full the sub-workloads' results attached (\"convolver\", ...); "
+                         "a sub-workload alone needs --full")
     ap.add_argument("--channels", type=int, default=1024, help="channels per GPU")
     ap.add_argument("--samples", type=int, default=4096, help="samples per block")
     ap.add_argument("--ring", type=int, default=16, help="distinct resident blocks cycled through "
                     "(16 x 32 MiB in+out > the 256 MiB Infinity Cache, so steps stream from HBM)")
-    ap.add_argument("--regions", type=int, default=0, help="timed repetitions of the K-step region (0 = 25, or 5 when K >= 500)")
+    ap.add_argument("--regions", type=int, default=0, help="--full: timed repetitions of the K-step region (0 = 101, or 5 "
+                    "when K >= 500, raised to fill about a second)")
     ap.add_argument("--launch", default="blocks", choices=["blocks", "graph", "eager"],
                     help="how the K steps of a region are issued: blocks = one mi_biquad_bank_process_blocks call (the K blocks ride "
                          "one launch of biquad_stream_kernel; `value` is this), graph = one hipGraph of K process() calls (always "
@@ -65,6 +74,14 @@ def parse():
                     "a stream each (kernel profiles of the row then hold the one-stream launches only)")
     ap.add_argument("--conv-steps", type=int, default=192, help="steps per timed region of the sub-workloads (a multiple of their launches' 16 / 64 / 128 units)")
     ap.add_argument("--conv-warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the timed regions repeated (--regions), kernel probes and roofline, "
+                         "per_call and exact_mode, the CPU baseline, the sub-workloads and the detail file.  Without it a run "
+                         "times exactly --steps steps of the headline once")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the output blocks of the headline's last timed step as DIR/<name>.npy "
+                         "(float32, at most 64 MB: a seeded sample of the channels beyond that; rank 0's shard when N > 1); "
+                         "with --full, those of a fresh bank through the same W + K steps: the same bits as a plain run")
     return ap.parse_args()
 
 
@@ -1351,10 +1368,119 @@ def _spawn_ranks(args):
     return subprocess.call(cmd)
 
 
+def _headline_line(args, world, sections, elapsed):
+    """The contract's keys of the headline (C2 biquad) line; `elapsed`: the seconds of one timed region of --steps steps."""
+    C, n, K = args.channels, args.samples, args.steps
+    per_call = " -- those are timed beside it under \"per_call\"" if args.full else ""
+    return {
+        "metric": "Msamples/sec per GPU (biquad-x8 1024ch; Convolver 65536-tap) + HBM roofline %",
+        "value": round(C * n * world * K / elapsed / 1e6, 1),
+        "unit": "Msamples/s",
+        "n_gpus": world,
+        "steps": K,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / K * 1e3, 5),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": "biquad-x8 cascade (FilterBank::process), %d channels x %d-sample blocks per GPU, "
+                        "FLT_BT_LRX_LOPASS slope 4 per-channel cutoffs, state carried across blocks" % (C, n),
+            "channels_per_gpu": C, "block": n, "sections": sections,
+            "resident_ring_blocks": args.ring, "parallelism": "channel-shard x%d, no collective" % world,
+            "blocks_per_call": K if args.launch == "blocks" else 1,
+            "call": ("mi_biquad_bank_process_blocks: the %d blocks of a timed region in one call (one launch per run of <= 128 blocks), "
+                     "bit-identical to %d mi_biquad_bank_process calls%s" % (K, K, per_call))
+                    if args.launch == "blocks" else "mi_biquad_bank_process: one call and one launch per block",
+        },
+        "per_gpu_msamples_s": round(C * n * K / elapsed / 1e6, 1),
+    }
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+SETTLE_SECONDS = 1.0       # load in front of a plain run's warm-up (main)
+
+
+def _dump_outputs(path, name, out):
+    """--dump-outputs: `out` ([channels][samples], host) as <path>/<name>.npy in float32.  Beyond DUMP_LIMIT_BYTES the rows of
+    a fixed seeded sample of the channels are written instead, and their indices as <path>/<name>_channels.npy."""
+    import numpy as np
+    out = np.asarray(out, dtype=np.float32)
+    os.makedirs(path, exist_ok=True)
+    if out.nbytes > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - 4096) // (out[0].nbytes + 8)     # (+ 8: the row's index; 4096: the two .npy headers)
+        rows = np.sort(np.random.default_rng(0).choice(out.shape[0], size=keep, replace=False))
+        np.save(os.path.join(path, name + "_channels.npy"), rows.astype(np.float64))
+        out = out[rows]
+    np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(out))
+
+
+def _plain_region(args, mi, torch, dist, world, step, blocks_call, stream, settle):
+    """A run without --full: `settle` (the load that brings the shader clock to where the timed steps run), the W warm-up
+    steps, then ONE timed region of exactly K steps through the path `value` measures (--launch), bracketed by synchronize
+    (+ barrier) on both sides and reduced with MAX over the ranks.  No host pause between the three: an idle GPU drops its
+    clock again (the --full path's first regions after its garbage collection read 0.20 ms against a settled 0.16 ms at K = 20).
+    blocks_call(first, count): the callable that issues steps first .. first + count - 1 as one mi_biquad_bank_process_blocks
+    call.  Returns (seconds, launch mode)."""
+    import ctypes
+    import gc
+    K, W = args.steps, args.warmup
+    sp, exe = ctypes.c_void_p(stream.cuda_stream), None
+    if args.launch == "blocks":
+        timed, mode = blocks_call(W, K), "one mi_biquad_bank_process_blocks call: the K blocks ride one launch per run of 128"
+        warm = blocks_call(0, W) if W else (lambda: None)  # the warm-up takes the timed call's path
+    else:
+        timed, mode = (lambda: [step(W + i) for i in range(K)]), "eager: K process() calls"
+        warm = lambda: [step(i) for i in range(W)]
+        if args.launch == "graph":
+            torch.cuda.synchronize()
+            mi.check(mi.lib.mi_dspu_graph_begin_capture(sp))
+            try:
+                for i in range(K):
+                    step(W + i)
+            finally:
+                h = ctypes.c_void_p()
+                rc = mi.lib.mi_dspu_graph_end_capture(sp, ctypes.byref(h))
+            mi.check(rc)
+            exe = h
+            timed, mode = (lambda: mi.check(mi.lib.mi_dspu_graph_launch(exe, sp))), "hipGraph of K process() calls, one graph launch"
+    torch.cuda.synchronize()
+    gc.collect()
+    gc.disable()
+    settle()
+    warm()
+    torch.cuda.synchronize()
+    if world > 1:
+        dist.barrier()
+        torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    timed()
+    torch.cuda.synchronize()
+    elapsed = time.perf_counter() - t0
+    gc.enable()
+    if exe is not None:
+        mi.lib.mi_dspu_graph_destroy(exe)
+    if world > 1:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=stream.device)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    return elapsed, mode
+
+
 def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if not args.full and args.workload not in ("all", "biquad"):
+        raise SystemExit("bench.py: --workload %s is part of the full run: add --full" % args.workload)
+    if not args.full and args.regions:
+        raise SystemExit("bench.py: --regions repeats the timed region, which only the full run does: add --full")
+    if args.dump_outputs and args.workload not in ("all", "biquad"):
+        raise SystemExit("bench.py: --dump-outputs writes the headline's outputs; --workload %s has none" % args.workload)
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:                                   # nothing of this process has initialised the GPU yet
             sys.exit(_spawn_ranks(args))
@@ -1437,6 +1563,53 @@ def main():
         k = i % ring
         bank.process(yout[k], xin[k], n, stream=stream)
 
+    import ctypes
+    last = (args.warmup + args.steps - 1) % ring            # the ring slot of the last timed step's output
+    ring_out, ring_in = [yout[k].data_ptr() for k in range(ring)], [xin[k].data_ptr() for k in range(ring)]
+
+    def blocks_call(first, count, on=bank):
+        """The callable that issues steps first .. first + count - 1 of bank `on` as one mi_biquad_bank_process_blocks call."""
+        seq = [(first + i) % ring for i in range(count)]
+        po = (ctypes.c_void_p * count)(*[ring_out[k] for k in seq])
+        pi = (ctypes.c_void_p * count)(*[ring_in[k] for k in seq])
+        sp = ctypes.c_void_p(stream.cuda_stream)
+        return lambda: mi.check(mi.lib.mi_biquad_bank_process_blocks(on.handle, po, pi, count, n, n, n, sp))
+
+    if not args.full:
+        # The shader clock dips at the onset of the load and settles within a second (the --full path's fill_seconds): the
+        # headline's launches run for that second first on a scratch bank of the same filters, so that `value` is the settled
+        # rate, while the timed bank's state and outputs come from the W warm-up and K timed steps alone.
+        scratch = mi.BiquadBank(C, max(1, coef.shape[1]))
+        scratch.set_all_chains(coef)
+        load, settled = blocks_call(0, 128, on=scratch), []
+
+        def settle():
+            t_end = time.perf_counter() + SETTLE_SECONDS
+            while time.perf_counter() < t_end:
+                for _ in range(8):
+                    load()
+                settled.append(8)
+                stream.synchronize()
+        elapsed, mode = _plain_region(args, mi, torch, dist, world, step, blocks_call, stream, settle)
+        scratch.close()
+        assert bool(torch.isfinite(yout[last]).all()) and float(yout[last].abs().max()) > 0.0
+        if args.dump_outputs and rank == 0:
+            _dump_outputs(args.dump_outputs, "biquad_out", yout[last].cpu().numpy())
+        bank.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            line = _headline_line(args, world, int(coef.shape[1]), elapsed)
+            line["timing"] = {"regions": 1, "launch": mode, "region_ms": round(elapsed * 1e3, 5),
+                              "settle_s": SETTLE_SECONDS, "settle_calls": sum(settled),
+                              "settle": "calls of 128 blocks on a scratch bank in front of the warm-up: a kernel profile of a "
+                                        "plain run holds their launches beside the timed ones (--full has no settle phase)"}
+            if rehearsal:
+                line["data"] = "synthetic; REHEARSAL: ranks share one device over gloo, not a measurement"
+            print(json.dumps(line), flush=True)
+        return
+
     # Short regions (K = 20: 0.16 - 0.2 ms each) are timed 101 times: the chip's power controller answers the onset of the
     # load with a dip of the shader clock that lasts 20 - 30 regions (160 -> 215 us per region) and settles after 60 - 80
     # (165 - 175 us; timing.region_ms.in_order shows the walk, profiles/r04_experiments/bench_k20_regions.txt) -- 25 regions
@@ -1495,6 +1668,19 @@ def main():
     # sanity: the output of the last step is finite and non-trivial
     chk = yout[(args.warmup + args.steps - 1) % ring]
     assert bool(torch.isfinite(chk).all()) and float(chk.abs().max()) > 0.0
+    if args.dump_outputs:
+        # The regions above repeat the K steps a number of times sized by the clock, and the filter state carries across
+        # them: the dump comes from a fresh bank of the same filters through the W warm-up and K steps of a plain run
+        # instead (process_blocks is bit-identical to the process() calls), so that its bits depend on the arguments alone.
+        fresh = mi.BiquadBank(C, max(1, coef.shape[1]))
+        fresh.set_all_chains(coef)
+        if args.warmup:
+            blocks_call(0, args.warmup, on=fresh)()
+        blocks_call(args.warmup, args.steps, on=fresh)()
+        stream.synchronize()
+        if rank == 0:
+            _dump_outputs(args.dump_outputs, "biquad_out", yout[last].cpu().numpy())
+        fresh.close()
     assert args.sections == 8 or args.no_cpu_baseline, "--sections is an experiment knob; the headline config has 8"
 
     if rank == 0:
@@ -1508,30 +1694,8 @@ def main():
                      "rocprofv3_avg_us": _profile_avg_us("biquad", "biquad_stream_kernel" if streamed else "biquad_bank_kernel<16, 2")
                                          if (C, n) == (1024, 4096) else None,
                      "parity": _committed_json("c2_parity_latest.json")}
-        line = {
-            "metric": "Msamples/sec per GPU (biquad-x8 1024ch; Convolver 65536-tap) + HBM roofline %",
-            "value": round(samples_per_step * args.steps / elapsed / 1e6, 1),
-            "unit": "Msamples/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 5),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {
-                "workload": "biquad-x8 cascade (FilterBank::process), %d channels x %d-sample blocks per GPU, "
-                            "FLT_BT_LRX_LOPASS slope 4 per-channel cutoffs, state carried across blocks" % (C, n),
-                "channels_per_gpu": C, "block": n, "sections": int(coef.shape[1]),
-                "resident_ring_blocks": ring, "parallelism": "channel-shard x%d, no collective" % world,
-                "blocks_per_call": args.steps if args.launch == "blocks" else 1,
-                "call": ("mi_biquad_bank_process_blocks: the %d blocks of a timed region in one call (one launch per run of <= 128 blocks), "
-                         "bit-identical to %d mi_biquad_bank_process calls -- those are timed beside it under \"per_call\"" % (args.steps, args.steps))
-                        if args.launch == "blocks" else "mi_biquad_bank_process: one call and one launch per block",
-            },
-            "per_gpu_msamples_s": round(C * n * args.steps / elapsed / 1e6, 1),
+        line = _headline_line(args, world, int(coef.shape[1]), elapsed)
+        line.update({
             "timing": tinfo,
             "roofline": _roofline(kname, alg_bytes * launch_steps, kernel_ms, elapsed / args.steps * 1e3, tinfo["probe"],
                                   committed["traffic"],
@@ -1539,7 +1703,7 @@ def main():
                                                      "r06_biquad_stream_pmc_sq.json" if streamed else "r06_biquad_pmc_sq.json", clock_ghz=stream_clock),
                                   launch_steps=launch_steps),
             "committed_profile": committed,
-        }
+        })
         line["timing"]["value_is"] = ("the K blocks of a region as ONE mi_biquad_bank_process_blocks call (one launch)" if streamed
                                       else "one launch per block (%s)" % tinfo["launch"])
         if per_call is not None:

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 for S in 0 1 2 4 6 8; do
   for V in "" "MI_BIQUAD_NO_WIDE=1"; do
-    env $V MI_BENCH_DETAIL=sweep_detail.json python3 $R/bench.py --workload biquad --no-cpu-baseline --steps ${1:-20} --sections $S 2>/dev/null | python3 -c "
+    env $V MI_BENCH_DETAIL=sweep_detail.json python3 $R/bench.py --full --workload biquad --no-cpu-baseline --steps ${1:-20} --sections $S 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().split('\n')[-1])
 r=d['roofline']

@@ -10,7 +10,7 @@ grep -E "passed|failed" $O/pytest_dyn.txt | tail -2
 MI_DYNFILTER_GENERIC=1 timeout 1200 python3 -m pytest tests/test_dynfilter_gpu.py -x -q -m gpu > $O/pytest_dyn_generic.txt 2>&1
 grep -E "passed|failed" $O/pytest_dyn_generic.txt | tail -2
 row() {
-  python3 bench.py --workload dynfilter --no-cpu-baseline > $O/bench_$1.json 2> $O/bench_$1.err
+  python3 bench.py --full --workload dynfilter --no-cpu-baseline > $O/bench_$1.json 2> $O/bench_$1.err
   python3 - <<PY
 import json
 try:

@@ -5,7 +5,7 @@ O=$R/gpurun_out/r3dyn
 mkdir -p $O
 cd $R
 row() {
-  python3 bench.py --workload dynfilter --no-cpu-baseline > $O/bench_$1.json 2> $O/bench_$1.err
+  python3 bench.py --full --workload dynfilter --no-cpu-baseline > $O/bench_$1.json 2> $O/bench_$1.err
   python3 - <<PY
 import json
 try:

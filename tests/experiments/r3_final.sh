@@ -6,9 +6,9 @@ mkdir -p $O
 cd $R
 timeout 2400 python3 -m pytest tests -x -q -m gpu > $O/pytest_gpu.txt 2>&1
 grep -E "passed|failed" $O/pytest_gpu.txt | tail -2
-python3 bench.py --steps 20 --warmup 5 > $O/bench_k20.json 2> $O/bench_k20.err
-python3 bench.py --steps 1000 --warmup 50 --no-cpu-baseline > $O/bench_k1000.json 2> $O/bench_k1000.err
-python3 bench.py --workload convolver --call 256 --no-cpu-baseline > $O/bench_conv_call256.json 2> $O/bench_conv_call256.err
+python3 bench.py --full --steps 20 --warmup 5 > $O/bench_k20.json 2> $O/bench_k20.err
+python3 bench.py --full --steps 1000 --warmup 50 --no-cpu-baseline > $O/bench_k1000.json 2> $O/bench_k1000.err
+python3 bench.py --full --workload convolver --call 256 --no-cpu-baseline > $O/bench_conv_call256.json 2> $O/bench_conv_call256.err
 python3 - <<PY
 import json
 d=json.loads(open("$O/bench_k20.json").read())

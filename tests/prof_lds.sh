@@ -11,7 +11,7 @@ for W in equalizer spectral stft splitter; do
     for CTRS in "SQ_WAVES SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_INST_LDS" \
                 "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_BUSY_CYCLES SQ_LDS_ADDR_CONFLICT"; do
         P=$((P+1))
-        rocprofv3 --pmc $CTRS --kernel-trace -d $O/${W}_$P --output-format csv -- python3 $R/bench.py --workload $W --no-cpu-baseline --conv-steps 128 > $O/${W}_$P.log 2>&1
+        rocprofv3 --pmc $CTRS --kernel-trace -d $O/${W}_$P --output-format csv -- python3 $R/bench.py --full --workload $W --no-cpu-baseline --conv-steps 128 > $O/${W}_$P.log 2>&1
     done
 done
 python3 - "$O" "$R/gpurun_out/profiles_$TAG/${TAG}_fft_lds_pmc_sq.json" <<'PY'
@@ -24,7 +24,7 @@ for fn in glob.glob(os.path.join(src, "**", "*counter_collection.csv"), recursiv
         for k in KEEP:
             if k in r["Kernel_Name"]:
                 acc[k][r["Counter_Name"]].append(float(r["Counter_Value"]))
-out = {"note": "rocprofv3 --pmc, two passes per workload (tests/prof_lds.sh: bench.py --workload W --conv-steps 128), averages per dispatch; "
+out = {"note": "rocprofv3 --pmc, two passes per workload (tests/prof_lds.sh: bench.py --full --workload W --conv-steps 128), averages per dispatch; "
                "SQ_WAVE_CYCLES / SQ_ACTIVE_* / SQ_WAIT_* in units of four clocks summed over the waves, SQ_LDS_IDX_ACTIVE / SQ_LDS_BANK_CONFLICT in clocks "
                "summed over the CUs (256)", "kernels": {}}
 for k, d in acc.items():

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
 rm -rf $O/stats_$W; cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $O/stats_$W --output-format csv -- python3 $R/bench.py --workload $W --no-cpu-baseline > $O/stats_$W.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/stats_$W --output-format csv -- python3 $R/bench.py --full --workload $W --no-cpu-baseline > $O/stats_$W.log 2>&1
 python3 - <<PY
 import csv, glob
 f = glob.glob("$O/stats_$W/**/*kernel_stats.csv", recursive=True)[0]

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/pmc_$W
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc $CTRS --kernel-trace -d $O --output-format csv -- python3 $R/bench.py --workload $W --no-cpu-baseline --steps 50 --conv-steps 50 > $O/log.txt 2>&1
+rocprofv3 --pmc $CTRS --kernel-trace -d $O --output-format csv -- python3 $R/bench.py --full --workload $W --no-cpu-baseline --steps 50 --conv-steps 50 > $O/log.txt 2>&1
 python3 - <<PY
 import csv, glob, collections
 f = glob.glob("$O/**/*counter_collection.csv", recursive=True)

@@ -11,7 +11,7 @@ for CTRS in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_
             "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU" \
             "SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INST_CYCLES_VMEM GRBM_GUI_ACTIVE"; do
     P=$((P+1))
-    rocprofv3 --pmc $CTRS --kernel-trace -d $O/pass$P --output-format csv -- python3 $R/bench.py --workload biquad --no-cpu-baseline --steps 50 > $O/pass$P.log 2>&1
+    rocprofv3 --pmc $CTRS --kernel-trace -d $O/pass$P --output-format csv -- python3 $R/bench.py --full --workload biquad --no-cpu-baseline --steps 50 > $O/pass$P.log 2>&1
 done
 python3 - <<PY
 import csv, glob, json, collections, os, sys
@@ -25,7 +25,7 @@ for fn in glob.glob("$O/**/*counter_collection.csv", recursive=True):
                 acc[key][r["Counter_Name"]].append(float(r["Counter_Value"]))
 for key, name, per in (("biquad_stream_kernel", "${TAG}_biquad_stream_pmc_sq.json", 50), ("biquad_bank_kernel", "${TAG}_biquad_pmc_sq.json", 1)):
     d = {"kernel": key, "config": "C2: 1024 channels x 4096 samples, 8 sections", "blocks_per_launch": per, "sources": prof_sources.sources_for(key),
-         "note": "rocprofv3 --pmc in three passes (tests/prof_sq.sh), averages per dispatch of bench.py --workload biquad --steps 50; "
+         "note": "rocprofv3 --pmc in three passes (tests/prof_sq.sh), averages per dispatch of bench.py --full --workload biquad --steps 50; "
                  "cycle counters are in units of four clocks on gfx950"}
     for c, v in acc[key].items():
         d[c] = sum(v) / len(v)

@@ -9,7 +9,7 @@ rm -rf $O; mkdir -p $O $R/gpurun_out/profiles_$TAG
 cd /tmp && export TMPDIR=/tmp
 for W in convolver equalizer spectral stft splitter crossover dynfilter loudness; do
     rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --kernel-trace -d $O/$W --output-format csv -- \
-        python3 $R/bench.py --workload $W --no-cpu-baseline --no-stream-pair --conv-steps 128 > $O/$W.log 2>&1
+        python3 $R/bench.py --full --workload $W --no-cpu-baseline --no-stream-pair --conv-steps 128 > $O/$W.log 2>&1
 done
 python3 - "$O" "$R/gpurun_out/profiles_$TAG/${TAG}_kernels_pmc_sq.json" <<'PY'
 import csv, glob, json, os, sys, collections
@@ -21,7 +21,7 @@ UNITS = {"conv_frames_kernel": 128, "conv_frames_wave_kernel": 128, "conv_batch_
          "analyzer_frames_wave_kernel": 16, "bin_smooth_reduce_kernel": 16, "bin_reduce_frames_kernel": 16, "stft_stream_blocks_kernel": 64, "stft_wave_blocks_kernel": 64, "splitter_hops_blocks_kernel": 64, "splitter_wave_blocks_kernel": 64,
          "biquad_stream_chain_kernel": 64}
 out = {"note": "rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR, one pass per bench workload "
-               "(tests/prof_valu.sh: bench.py --workload W --conv-steps 128), averages per dispatch of the smallest grid a kernel ran with "
+               "(tests/prof_valu.sh: bench.py --full --workload W --conv-steps 128), averages per dispatch of the smallest grid a kernel ran with "
                "(the convolver row's 512-channel pass doubles it)", "kernels": {}}
 for wl in sorted(os.listdir(src)):
     if not os.path.isdir(os.path.join(src, wl)):

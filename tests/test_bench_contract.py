@@ -8,6 +8,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
@@ -103,3 +105,89 @@ def test_final_line_sheds_parts_rather_than_grow():
     text = json.dumps(line)
     assert len(text) <= bench.LINE_LIMIT
     assert "roofline" in line and "cpu_baseline" in line and "value" in line
+
+
+def test_plain_run_refuses_what_only_the_full_run_does():
+    """A run without --full measures the headline alone; asking it for a sub-workload or for repeated regions is refused
+    before anything else happens (no JSON line, no device touched)."""
+    for extra, word in ((["--workload", "convolver"], b"--full"), (["--regions", "5"], b"--full"),
+                        (["--full", "--workload", "spectral", "--dump-outputs", "x"], b"--dump-outputs")):
+        r = _run(["--gpus", "1", "--steps", "1", "--warmup", "0"] + extra, {})
+        assert r.returncode != 0, extra
+        assert word in r.stderr, (extra, r.stderr[-400:])
+        assert not r.stdout.strip(), extra
+
+
+def test_dump_outputs_writes_float32_within_the_limit(tmp_path, monkeypatch):
+    import importlib
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    out = np.random.default_rng(1).standard_normal((64, 256)).astype(np.float32)
+    bench._dump_outputs(str(tmp_path / "a"), "biquad_out", out)
+    got = np.load(str(tmp_path / "a" / "biquad_out.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, out)
+    assert not (tmp_path / "a" / "biquad_out_channels.npy").exists()
+    # over the limit: the rows of a fixed seeded sample of the channels, and which rows they are
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 16 * out[0].nbytes)
+    for d in ("b", "c"):
+        bench._dump_outputs(str(tmp_path / d), "biquad_out", out)
+    files = [tmp_path / "b" / "biquad_out.npy", tmp_path / "b" / "biquad_out_channels.npy"]
+    assert sum(os.path.getsize(str(f)) for f in files) <= bench.DUMP_LIMIT_BYTES
+    rows = np.load(str(files[1]))
+    assert rows.dtype == np.float64 and len(rows) > 0 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(str(files[0])), out[rows.astype(np.int64)])
+    assert np.array_equal(rows, np.load(str(tmp_path / "c" / "biquad_out_channels.npy")))
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_its_outputs_repeat(gpu, tmp_path):
+    """Without --full: one timed region of exactly --steps steps, the contract's keys and nothing measured beside them.  The
+    blocks --dump-outputs writes are those of step W + K - 1, recomputed here from the same seeded inputs by W + K process()
+    calls of a fresh bank: a wrong ring slot, a block of the warm-up or of the scratch bank's settle phase, or a number of steps
+    other than W + K would differ.  A second run and a --full run (whose timed regions repeat a clock-sized number of times)
+    write the same bits."""
+    import json
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import importlib
+    bench = importlib.import_module("bench")
+    C, n, ring, W, K = 128, 4096, 4, 3, 7
+    common = ["--gpus", "1", "--steps", str(K), "--warmup", str(W), "--channels", str(C), "--ring", str(ring)]
+    lines, outs = {}, {}
+    for d, extra in (("a", []), ("b", []), ("full", ["--full", "--workload", "biquad", "--no-cpu-baseline"])):
+        r = _run(common + extra + ["--dump-outputs", str(tmp_path / d)], {"MI_BENCH_DETAIL": "bench_detail_test.json"}, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines[d] = json.loads(r.stdout.decode().strip().splitlines()[-1])
+        outs[d] = np.load(str(tmp_path / d / "biquad_out.npy"))
+    line = lines["a"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == K and line["warmup"] == W and line["timing"]["regions"] == 1
+    assert line["ms_per_step"] > 0 and line["value"] > 0 and line["timing"]["settle_calls"] > 0
+    for k in ("roofline", "cpu_baseline", "per_call", "exact_mode", "convolver", "next_rows"):
+        assert k not in line, k
+    assert "roofline" in lines["full"] and lines["full"]["timing"]["regions"] > 1
+
+    # bench.py's inputs: C2 cutoffs from seed 3 designed by the product's designer, blocks from torch's CPU generator, seed 2 + rank
+    fc = np.exp(np.random.default_rng(3).uniform(np.log(200.0), np.log(18000.0), size=C))
+    coef = np.zeros((C, 8, 5), np.float32)
+    for c in range(C):
+        coef[c] = gpu.design_filter(bench.FLT_BT_LRX_LOPASS, 4, float(fc[c]), float(fc[c]), 1.0, 0.75, 48000)[2]
+    # (torch in a child process of its own: a second HIP runtime in this one leaves the tests that call HIP directly without a device)
+    xp = str(tmp_path / "x.npy")
+    subprocess.check_call([sys.executable, "-c", "import sys, numpy, torch; g = torch.Generator(device='cpu'); g.manual_seed(2); "
+                           "numpy.save(sys.argv[1], (torch.randn((%d, %d, %d), generator=g, dtype=torch.float32) * 0.25).numpy())"
+                           % (ring, C, n), xp])
+    x = np.load(xp)
+    bank = gpu.BiquadBank(C, 8)
+    bank.set_all_chains(coef)
+    ins = [gpu.DeviceBuffer.from_host(np.ascontiguousarray(x[k])) for k in range(ring)]
+    out = gpu.DeviceBuffer((C, n))
+    for i in range(W + K):
+        bank.process(out, ins[i % ring], n)
+    want = out.download()
+    bank.close()
+    assert outs["a"].dtype == np.float32 and outs["a"].shape == (C, n) and np.abs(want).max() > 0
+    assert np.array_equal(outs["a"], want), np.abs(outs["a"] - want).max()
+    assert np.array_equal(outs["b"], want) and np.array_equal(outs["full"], want)

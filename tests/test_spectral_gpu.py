@@ -812,7 +812,7 @@ def test_bench_rehearsal_two_ranks_on_one_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MI_BENCH_REHEARSAL="1", MI_BENCH_DETAIL="bench_detail_rehearsal.json")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "spectral", "--spec-channels", "128",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--workload", "spectral", "--spec-channels", "128",
                         "--conv-steps", "32", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
