@@ -787,6 +787,42 @@ int mi_ilufs_bank_loudness(mi_ilufs_bank_t *bank, float *loudness, void *stream)
  * [meters][*size] (NULL: only the size is wanted), head / count HOST [meters] or NULL. */
 int mi_ilufs_bank_history(mi_ilufs_bank_t *bank, float *hist, uint32_t *size, uint32_t *head, uint32_t *count, void *stream);
 
+/* ---- true-peak meter bank (ITU-R BS.1770-4 Annex 2) ------------------------------------------------------------------ */
+/*
+ * mi_truepeak_bank: `channels` x lsp::dspu::TruePeakMeter (meters/TruePeakMeter.h:36-155, src/main/meters/TruePeakMeter.cpp):
+ * every input upsampled N times by a Lanczos kernel (a = 10, lsp-dsp-lib's lanczos_resample_Nx16bit), every output the
+ * largest magnitude of its N oversampled values.  N from the sample rate (:85-100): 0 (plain |x|) at 176400 Hz and above,
+ * 2 from 88200, 3 from 58800, 4 from 44100, 6 from 29400, 8 below.  The state is the last 20 inputs of each channel, kept
+ * on the device; the bank has no positions, so its process calls can be captured into a graph and replayed.
+ * Rows of the sample buffers: [channels][stride].
+ */
+typedef struct mi_truepeak_bank mi_truepeak_bank_t;
+/* TruePeakMeter::init(), TruePeakMeter.cpp:69-82: sample rate 0 as constructed, so the first update picks N = 8 */
+int mi_truepeak_bank_create(mi_truepeak_bank_t **bank, uint32_t channels);
+int mi_truepeak_bank_destroy(mi_truepeak_bank_t *bank);                                 /* :59-67 */
+/* set_sample_rate(sr), :102-109: takes effect at the next update_settings() */
+int mi_truepeak_bank_set_sample_rate(mi_truepeak_bank_t *bank, uint32_t sample_rate);
+/* update_settings(), :149-189: clears the state only when N changes.  On a stream being captured an update that changes N
+ * is refused (MI_ESTATE): call it before the capture. */
+int mi_truepeak_bank_update_settings(mi_truepeak_bank_t *bank, void *stream);
+int mi_truepeak_bank_clear(mi_truepeak_bank_t *bank, void *stream);                     /* :191-195 */
+/* latency(), :274-277: 10 samples while N != 0, else 0; oversampling(): the current N (nTimes) */
+int mi_truepeak_bank_latency(const mi_truepeak_bank_t *bank, uint32_t *samples);
+int mi_truepeak_bank_oversampling(const mi_truepeak_bank_t *bank, uint32_t *times);
+/* process(dst, src, count), :197-236, update_settings() first.  dst may equal src (in place, same stride); otherwise the
+ * two must not overlap. */
+int mi_truepeak_bank_process(mi_truepeak_bank_t *bank, float *dst, const float *src, size_t count, size_t dst_stride,
+                             size_t src_stride, void *stream);
+/* process_max(src, count), :238-272, update_settings() first: peaks is a DEVICE array of `channels` floats, each the largest
+ * value process() would have written for that channel; the state advances as process() advances it.  (The reference's
+ * returns 0.0f and looks at only part of the oversampled block; its header documents the maximum, which is what this is.) */
+int mi_truepeak_bank_process_max(mi_truepeak_bank_t *bank, float *peaks, const float *src, size_t count, size_t src_stride,
+                                 void *stream);
+/* The coefficients the kernels use for `times` = 2, 3, 4, 6, 8 (0: none): h is HOST memory [times][20] or NULL, row k the
+ * phase k / times, h_k[t] = float(L(t - 10 + k / times)) with L(x) = sinc(x) sinc(x / 10) computed in double; row 0 is the
+ * unit impulse at t = 10.  *count = times * 20.  No device needed. */
+int mi_truepeak_coefficients(uint32_t times, float *h, size_t *count);
+
 /*
  * mi_splitter_bank: lsp::dspu::SpectralSplitter for `channels` channels sharing the settings
  * (util/SpectralSplitter.h:62-250, src/main/util/SpectralSplitter.cpp:62-361) -- the engine of lsp::dspu::FFTCrossover.

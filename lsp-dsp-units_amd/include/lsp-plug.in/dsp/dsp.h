@@ -53,6 +53,9 @@ namespace lsp
             float b[4];
         };
 
+        // lsp-dsp-lib's resampling function type (TruePeakMeter keeps one): dst receives the oversampled src
+        typedef void (*resampling_function_t)(float *dst, const float *src, size_t count);
+
         // lsp-dsp-lib's per-thread context / init are no-ops here: there is no SIMD dispatch to select
         struct context_t { uint32_t top; uint32_t data[15]; };
         inline void init() {}

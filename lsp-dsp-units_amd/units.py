@@ -638,6 +638,64 @@ class RingBank:
             pass
 
 
+class TruePeakBank:
+    """`channels` x lsp::dspu::TruePeakMeter (mi_truepeak_bank_*): BS.1770-4 true peak per sample, or its maximum per call."""
+
+    def __init__(self, channels):
+        h = c_void_p()
+        check(lib.mi_truepeak_bank_create(byref(h), channels))
+        self.handle, self.channels = h, channels
+
+    @staticmethod
+    def coefficients(times):
+        """The kernels' table for `times` (mi_truepeak_coefficients): float32 [times][20], row k the phase k / times."""
+        n = ctypes.c_size_t()
+        check(lib.mi_truepeak_coefficients(times, None, byref(n)))
+        h = np.zeros(n.value, np.float32)
+        check(lib.mi_truepeak_coefficients(times, h.ctypes.data_as(ctypes.POINTER(c_float)), byref(n)))
+        return h.reshape(times, 20) if times else h.reshape(0, 20)
+
+    def set_sample_rate(self, sr):
+        check(lib.mi_truepeak_bank_set_sample_rate(self.handle, sr))
+
+    def update_settings(self, stream=None):
+        check(lib.mi_truepeak_bank_update_settings(self.handle, _stream(stream)))
+
+    def clear(self, stream=None):
+        check(lib.mi_truepeak_bank_clear(self.handle, _stream(stream)))
+
+    def latency(self):
+        v = c_uint32()
+        check(lib.mi_truepeak_bank_latency(self.handle, byref(v)))
+        return v.value
+
+    def oversampling(self):
+        v = c_uint32()
+        check(lib.mi_truepeak_bank_oversampling(self.handle, byref(v)))
+        return v.value
+
+    def process(self, out, inp, count, out_stride=None, in_stride=None, stream=None):
+        """process(dst, src, count); out may be inp (in place)."""
+        check(lib.mi_truepeak_bank_process(self.handle, _ptr(out), _ptr(inp), count, count if out_stride is None else out_stride,
+                                           count if in_stride is None else in_stride, _stream(stream)))
+
+    def process_max(self, peaks, inp, count, in_stride=None, stream=None):
+        """process_max(src, count) of every channel into the device array `peaks` [channels]."""
+        check(lib.mi_truepeak_bank_process_max(self.handle, _ptr(peaks), _ptr(inp), count, count if in_stride is None else in_stride,
+                                               _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            lib.mi_truepeak_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class LoudnessBank:
     """`meters` x lsp::dspu::LoudnessMeter(channels) sharing one configuration (mi_loudness_bank_*)."""
     WEIGHT_NONE, WEIGHT_A, WEIGHT_B, WEIGHT_C, WEIGHT_D, WEIGHT_K = range(6)
