@@ -823,6 +823,81 @@ int mi_truepeak_bank_process_max(mi_truepeak_bank_t *bank, float *peaks, const f
  * unit impulse at t = 10.  *count = times * 20.  No device needed. */
 int mi_truepeak_coefficients(uint32_t times, float *h, size_t *count);
 
+/* ---- oversampler bank (Lanczos resampling with anti-alias filter) ----------------------------------------------------- */
+/*
+ * mi_oversampler_bank: `channels` x lsp::dspu::Oversampler (util/Oversampler.h:107-288, src/main/util/Oversampler.cpp):
+ * every input upsampled N times by a Lanczos kernel of half-width a, the caller's work on the oversampled rows, the
+ * anti-alias low-pass (FLT_BT_BWC_LOPASS, slope 30, min(20 kHz, 0.42 sr), designed at sr N; :108-126) and the decimation.
+ * The upsample state is the last 2a inputs of each channel on the device; the bank has no positions (no nUpHead), so its
+ * calls can be captured into a graph and replayed.  The filter is an ordinary mi_biquad_bank the bank owns: it follows the
+ * process-wide exact / fast default (mi_dspu_set_exact_iir_default) and mi_oversampler_bank_set_exact.
+ * Rows of the sample buffers: [channels][stride]; oversampled rows hold N * count samples.
+ */
+typedef struct mi_oversampler_bank mi_oversampler_bank_t;
+/* over_mode_t with the same enumerator values (util/Oversampler.h:62-100).  N = 2, 3, 4, 6, 8 by group; a = 2, 3, 4 for
+ * *X2, *X3, *X4, 4 for *12BIT (the reference says only "latency 4": the *X4 table is used),
+ * 10 for *16BIT (the true-peak table), 62 for *24BIT. */
+enum mi_over_mode
+{
+    MI_OM_NONE = 0,
+    MI_OM_LANCZOS_2X2 = 1, MI_OM_LANCZOS_2X3 = 2, MI_OM_LANCZOS_2X4 = 3, MI_OM_LANCZOS_2X12BIT = 4, MI_OM_LANCZOS_2X16BIT = 5, MI_OM_LANCZOS_2X24BIT = 6,
+    MI_OM_LANCZOS_3X2 = 7, MI_OM_LANCZOS_3X3 = 8, MI_OM_LANCZOS_3X4 = 9, MI_OM_LANCZOS_3X12BIT = 10, MI_OM_LANCZOS_3X16BIT = 11, MI_OM_LANCZOS_3X24BIT = 12,
+    MI_OM_LANCZOS_4X2 = 13, MI_OM_LANCZOS_4X3 = 14, MI_OM_LANCZOS_4X4 = 15, MI_OM_LANCZOS_4X12BIT = 16, MI_OM_LANCZOS_4X16BIT = 17, MI_OM_LANCZOS_4X24BIT = 18,
+    MI_OM_LANCZOS_6X2 = 19, MI_OM_LANCZOS_6X3 = 20, MI_OM_LANCZOS_6X4 = 21, MI_OM_LANCZOS_6X12BIT = 22, MI_OM_LANCZOS_6X16BIT = 23, MI_OM_LANCZOS_6X24BIT = 24,
+    MI_OM_LANCZOS_8X2 = 25, MI_OM_LANCZOS_8X3 = 26, MI_OM_LANCZOS_8X4 = 27, MI_OM_LANCZOS_8X12BIT = 28, MI_OM_LANCZOS_8X16BIT = 29, MI_OM_LANCZOS_8X24BIT = 30
+};
+/* IOversamplerCallback::process / oversampler_callback_t (util/Oversampler.h:36-60) for a bank: called on the HOST once per
+ * process() call, it enqueues the caller's work on `stream` over the oversampled rows -- buf is DEVICE memory
+ * [channels][stride] with `samples` = N * count samples per row, worked on in place -- and returns an MI_* status. */
+typedef int (*mi_oversampler_callback_t)(float *buf, size_t samples, size_t stride, uint32_t channels, void *stream, void *arg);
+/* Oversampler::construct() + init(), Oversampler.cpp:53-93: OM_NONE, rate 0, filtering on, every update pending */
+int mi_oversampler_bank_create(mi_oversampler_bank_t **bank, uint32_t channels);
+int mi_oversampler_bank_destroy(mi_oversampler_bank_t *bank);                           /* :95-106 */
+/* set_sample_rate(sr), :108-126: the only call that sets the filter's parameters (a bank whose rate was never set filters
+ * with FLT_NONE).  The sections are designed and sent at the next update_settings(). */
+int mi_oversampler_bank_set_sample_rate(mi_oversampler_bank_t *bank, uint32_t sample_rate);
+/* set_mode(mode), :1055-1063: the resampling kernels follow the mode at once (as pFunc does), state and filter at the next
+ * update_settings(); mode(), :1065-1068 */
+int mi_oversampler_bank_set_mode(mi_oversampler_bank_t *bank, uint32_t mode);
+int mi_oversampler_bank_mode(const mi_oversampler_bank_t *bank, uint32_t *mode);
+/* set_filtering(filter), util/Oversampler.h:191-197; filtering(), :1070-1073; modified(), util/Oversampler.h:209-212 */
+int mi_oversampler_bank_set_filtering(mi_oversampler_bank_t *bank, int on);
+int mi_oversampler_bank_filtering(const mi_oversampler_bank_t *bank, int *on);
+int mi_oversampler_bank_modified(const mi_oversampler_bank_t *bank, int *yes);
+/* update_settings(), :128-144: zeroes the upsample state and clears the filter when the mode, the filtering flag or the
+ * sample rate changed, and designs the filter at sr N for the current N.  The caller runs it, as in the reference; the
+ * process entries do not.  On a stream being captured an update that changes anything is refused (MI_ESTATE). */
+int mi_oversampler_bank_update_settings(mi_oversampler_bank_t *bank, void *stream);
+/* get_oversampling(), :146-195; latency(), :955-1006 (a); max_latency(), util/Oversampler.h:281 (62) */
+int mi_oversampler_bank_oversampling(const mi_oversampler_bank_t *bank, uint32_t *times);
+int mi_oversampler_bank_latency(const mi_oversampler_bank_t *bank, uint32_t *samples);
+int mi_oversampler_bank_max_latency(const mi_oversampler_bank_t *bank, uint32_t *samples);
+/* The scratch rows [channels][N count] of process() and of a filtered downsample() (fUpBuffer / fDownBuffer, :70-93) for
+ * calls of up to `count` samples at the current mode.  A call that would have to grow them on a stream being captured
+ * returns MI_ESTATE: reserve before capturing. */
+int mi_oversampler_bank_reserve(mi_oversampler_bank_t *bank, size_t count);
+/* mi_biquad_bank_set_exact of the anti-alias filter's bank (sFilter, util/Oversampler.h:131) */
+int mi_oversampler_bank_set_exact(mi_oversampler_bank_t *bank, int on);
+/* upsample(dst, src, count), :197-367: dst rows of N * count samples; dst and src must not overlap.  OM_NONE copies. */
+int mi_oversampler_bank_upsample(mi_oversampler_bank_t *bank, float *dst, const float *src, size_t count, size_t dst_stride,
+                                 size_t src_stride, void *stream);
+/* downsample(dst, src, count), :369-525: src rows of N * count samples through the filter (when filtering is on), every
+ * N-th kept; dst and src must not overlap.  OM_NONE copies. */
+int mi_oversampler_bank_downsample(mi_oversampler_bank_t *bank, float *dst, const float *src, size_t count, size_t dst_stride,
+                                   size_t src_stride, void *stream);
+/* process(dst, src, count, callback, arg), :527-953: upsample into the scratch rows, the callback (NULL: none), the filter
+ * in place, the decimation.  dst may equal src (same stride).  It shares the upsample state with upsample() and the filter
+ * state with downsample().  OM_NONE (:731-737, :945-951): a copy, then the callback on the dst rows. */
+int mi_oversampler_bank_process(mi_oversampler_bank_t *bank, float *dst, const float *src, size_t count, size_t dst_stride,
+                                size_t src_stride, mi_oversampler_callback_t callback, void *arg, void *stream);
+/* The filter_params_t the bank holds (:117-125, limited as Filter::update limits them) and the rate it designs them at */
+int mi_oversampler_bank_get_filter(const mi_oversampler_bank_t *bank, mi_filter_params_t *params, uint32_t *sample_rate);
+/* The coefficients the kernels of `mode` use (lanczos_resample_NxK of lsp-dsp-lib as get_function() picks them, :1008-1052;
+ * inferred): h is HOST memory [N][2a] or NULL, row k the phase k / N, h_k[t] = float(L(t - a + k / N)) with
+ * L(x) = sinc(x) sinc(x / a) computed in double; row 0 is the unit impulse at t = a.  *count = N * 2a, 0 for OM_NONE.
+ * No device needed. */
+int mi_oversampler_coefficients(uint32_t mode, float *h, size_t *count);
+
 /*
  * mi_splitter_bank: lsp::dspu::SpectralSplitter for `channels` channels sharing the settings
  * (util/SpectralSplitter.h:62-250, src/main/util/SpectralSplitter.cpp:62-361) -- the engine of lsp::dspu::FFTCrossover.

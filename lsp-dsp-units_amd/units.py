@@ -696,6 +696,122 @@ class TruePeakBank:
             pass
 
 
+class OversamplerBank:
+    """`channels` x lsp::dspu::Oversampler (mi_oversampler_bank_*): Lanczos upsampling, the caller's work on the oversampled
+    rows, the anti-alias filter and the decimation."""
+    # over_mode_t (util/Oversampler.h:62-100): OM_NONE, then LANCZOS_<N>X<K> for N in 2, 3, 4, 6, 8 and K as below
+    OM_NONE = 0
+    MODES = {"%dX%s" % (n, k): 1 + 6 * g + j for g, n in enumerate((2, 3, 4, 6, 8))
+             for j, k in enumerate(("2", "3", "4", "12BIT", "16BIT", "24BIT"))}
+
+    def __init__(self, channels):
+        h = c_void_p()
+        check(lib.mi_oversampler_bank_create(byref(h), channels))
+        self.handle, self.channels = h, channels
+        self._cb = None
+
+    @staticmethod
+    def coefficients(mode):
+        """The kernels' table of `mode` (mi_oversampler_coefficients): float32 [N][2a], row k the phase k / N."""
+        n = ctypes.c_size_t()
+        check(lib.mi_oversampler_coefficients(mode, None, byref(n)))
+        h = np.zeros(n.value, np.float32)
+        if n.value:
+            check(lib.mi_oversampler_coefficients(mode, h.ctypes.data_as(ctypes.POINTER(c_float)), byref(n)))
+        times = 1 if mode == 0 else (2, 3, 4, 6, 8)[(mode - 1) // 6]
+        return h.reshape(times, -1) if n.value else h.reshape(0, 0)
+
+    def set_sample_rate(self, sr):
+        check(lib.mi_oversampler_bank_set_sample_rate(self.handle, sr))
+
+    def set_mode(self, mode):
+        check(lib.mi_oversampler_bank_set_mode(self.handle, mode))
+
+    def mode(self):
+        v = c_uint32()
+        check(lib.mi_oversampler_bank_mode(self.handle, byref(v)))
+        return v.value
+
+    def set_filtering(self, on=True):
+        check(lib.mi_oversampler_bank_set_filtering(self.handle, 1 if on else 0))
+
+    def filtering(self):
+        v = c_int()
+        check(lib.mi_oversampler_bank_filtering(self.handle, byref(v)))
+        return bool(v.value)
+
+    def modified(self):
+        v = c_int()
+        check(lib.mi_oversampler_bank_modified(self.handle, byref(v)))
+        return bool(v.value)
+
+    def update_settings(self, stream=None):
+        check(lib.mi_oversampler_bank_update_settings(self.handle, _stream(stream)))
+
+    def _u32(self, fn):
+        v = c_uint32()
+        check(fn(self.handle, byref(v)))
+        return v.value
+
+    def oversampling(self):
+        return self._u32(lib.mi_oversampler_bank_oversampling)
+
+    def latency(self):
+        return self._u32(lib.mi_oversampler_bank_latency)
+
+    def max_latency(self):
+        return self._u32(lib.mi_oversampler_bank_max_latency)
+
+    def reserve(self, count):
+        check(lib.mi_oversampler_bank_reserve(self.handle, count))
+
+    def set_exact(self, on=True):
+        check(lib.mi_oversampler_bank_set_exact(self.handle, 1 if on else 0))
+
+    def get_filter(self):
+        """(filter parameters as a dict, the rate they are designed at)."""
+        fp, sr = FilterParams(), c_uint32()
+        check(lib.mi_oversampler_bank_get_filter(self.handle, byref(fp), byref(sr)))
+        return {n: getattr(fp, n) for n, _ in FilterParams._fields_}, sr.value
+
+    def upsample(self, out, inp, count, out_stride=None, in_stride=None, stream=None):
+        """upsample(dst, src, count): out rows of N * count samples."""
+        n = self.oversampling()
+        check(lib.mi_oversampler_bank_upsample(self.handle, _ptr(out), _ptr(inp), count, n * count if out_stride is None else out_stride,
+                                               count if in_stride is None else in_stride, _stream(stream)))
+
+    def downsample(self, out, inp, count, out_stride=None, in_stride=None, stream=None):
+        """downsample(dst, src, count): inp rows of N * count samples."""
+        n = self.oversampling()
+        check(lib.mi_oversampler_bank_downsample(self.handle, _ptr(out), _ptr(inp), count, count if out_stride is None else out_stride,
+                                                 n * count if in_stride is None else in_stride, _stream(stream)))
+
+    def process(self, out, inp, count, callback=None, out_stride=None, in_stride=None, stream=None):
+        """process(dst, src, count, callback); out may be inp.  callback(buf_ptr, samples, stride, channels, stream) runs on
+        the host once per call and enqueues its work on `stream` over the oversampled device rows, in place."""
+        from .capi import OVERSAMPLER_FUNC
+        cb = None
+        if callback is not None:
+            def _call(buf, samples, stride, channels, st, arg):
+                r = callback(buf, samples, stride, channels, st)
+                return 0 if r is None else int(r)
+            cb = self._cb = OVERSAMPLER_FUNC(_call)
+        check(lib.mi_oversampler_bank_process(self.handle, _ptr(out), _ptr(inp), count, count if out_stride is None else out_stride,
+                                              count if in_stride is None else in_stride,
+                                              ctypes.cast(cb, c_void_p) if cb is not None else None, None, _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            lib.mi_oversampler_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class LoudnessBank:
     """`meters` x lsp::dspu::LoudnessMeter(channels) sharing one configuration (mi_loudness_bank_*)."""
     WEIGHT_NONE, WEIGHT_A, WEIGHT_B, WEIGHT_C, WEIGHT_D, WEIGHT_K = range(6)
