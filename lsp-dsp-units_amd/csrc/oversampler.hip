@@ -1,34 +1,28 @@
 // lsp::dspu::Oversampler as a bank of `channels` oversamplers (src/main/util/Oversampler.cpp): N-times Lanczos upsampling,
 // the caller's work on the oversampled rows, the anti-alias low-pass and the decimation back.
 //
-// Upsampling is truepeak.hip's arithmetic with the values kept: the reference SCATTERS each input into a zero-filled buffer
-// of pending sums (lsp-dsp-lib's lanczos_resample_NxK); an oversampled value is final once input i has been added, so the
-// same bits come out of the GATHER
-//      y[N i + k] = (((+0 + h_k[2a-1] x[i-2a+1]) + h_k[2a-2] x[i-2a+2]) + ...) + h_k[0] x[i],   h_k[t] = float(L(t - a + k / N))
-// oldest input first, every product and every sum rounded on its own, and y[N i] = x[i - a] copied.  A sum starts from
-// +0.0f, as the reference's zero-filled buffer makes it, so a sum of negative zeros is +0; only the copied phase 0 can
-// carry a -0 through.  The state is the last 2a inputs of each channel, [channels][124] on the device, read at the start
-// of a call and written at its end: no host positions (nUpHead and the 12 K buffer of the reference hold pending sums and
-// change no value), so a captured graph replays.
+// Upsampling is lanczos_device.h's gather with the values kept (coefficients, window, pairs, packed tap loop, tile fill
+// and the planning of a launch are there, shared with truepeak.hip).  A sum starts from +0.0f, so a sum of negative zeros
+// is +0; only the copied phase 0 can carry a -0 through.  State: [channels][124] on the device (nUpHead and the 12 K
+// buffer of the reference hold pending sums and change no value).
 //
-// The taps are INFERRED, as the true-peak table is: L(x) = sinc(x) sinc(x / a) in double, rounded once, a = latency()
-// (:955-1006).  For the *12BIT modes the reference says only "latency 4", the same as *X4; nothing here tells their
-// kernels apart, so they take a = 4 and the *X4 table (unpinned).
+// The taps take a = latency() (:955-1006).  For the *12BIT modes the reference says only "latency 4", the same as *X4;
+// nothing here tells their kernels apart, so they take a = 4 and the *X4 table (unpinned).
 //
 // Kernel shape: a workgroup walks its row in tiles of inputs through LDS.  A thread owns 8 consecutive inputs and makes
 // their 8 (N - 1) values phase by phase (coefficients in scalar registers, packed multiplies and adds for a <= 10, a tap
 // loop over LDS for a = 62) into one LDS plane per phase; then the tile's N x 8 x BLOCK outputs leave as contiguous
 // 16-byte stores, lane by lane adjacent, each lane picking its four values out of the planes.
-#include "mi_common.h"
+#include "lanczos_device.h"
 
-#include <cmath>
 #include <new>
 
-// no fused multiply-add may form in the tap loops, whatever -ffp-contract the file is compiled with
-#pragma clang fp contract(off)
+#pragma clang fp contract(off)      // no fused multiply-add in the tap loops below: lanczos_device.h says why
 
 namespace
 {
+    using namespace mi_lanczos;
+
     constexpr int      PT         = 8;                  // consecutive inputs of one thread
     constexpr int      A_MAX      = 62;                 // OVERSAMPLER_MAX_LATENCY
     constexpr int      STATE      = 2 * A_MAX;          // floats of state per channel (the first 2a are used)
@@ -36,9 +30,6 @@ namespace
     constexpr uint32_t MAX_SPLITS = 64;                 // workgroups per row when few rows are long
     constexpr int      DOWN_BLOCK = 256;
     static_assert(STAGE_BLOCK >= STATE, "one thread per state value");
-
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef const __attribute__((address_space(4))) f32x2 *const_pairs;
 
     // Oversampler::get_oversampling (:146-195) and latency (:955-1006) of a mode: modes 1 .. 30 are five groups of six
     __host__ __device__ constexpr int mode_times(uint32_t mode)
@@ -53,31 +44,11 @@ namespace
         return (k == 0) ? 2 : (k == 1) ? 3 : (k == 2) ? 4 : (k == 3) ? 4 : (k == 4) ? 10 : 62;
     }
 
-    // the device table: for each a of { 2, 3, 4, 10, 62 } and N of { 2, 3, 4, 6, 8 } the phases k = 1 .. N-1, 2a pairs each
-    // (every coefficient twice: the packed multiply's operand)
-    constexpr int a_index(int a) { return (a == 2) ? 0 : (a == 3) ? 1 : (a == 4) ? 2 : (a == 10) ? 3 : 4; }
-    constexpr int n_phases_before(int n) { return (n == 2) ? 0 : (n == 3) ? 1 : (n == 4) ? 3 : (n == 6) ? 6 : 11; }
+    // the device table: for each a of { 2, 3, 4, 10, 62 } phase_pairs of every N
+    constexpr int LATENCIES[] = { 2, 3, 4, 10, 62 };
     constexpr int a_taps_before(int a) { return (a == 2) ? 0 : (a == 3) ? 4 : (a == 4) ? 10 : (a == 10) ? 18 : 38; }
-    constexpr int TABLE_PAIRS = 18 * (4 + 6 + 8 + 20 + 124);
-    constexpr int table_offset(int n, int a) { return 18 * a_taps_before(a) + n_phases_before(n) * 2 * a; }
-
-    // L(x) = sinc(x) sinc(x / a) at x = num / n, in double, rounded to float once.  |num| makes the table bit-symmetric.
-    // At whole x the kernel is exactly 1 (x = 0) or 0, not the rounding residue of sin(pi x).
-    float lanczos_tap(int num, int n, int a)
-    {
-        if (num % n == 0)
-            return (num == 0) ? 1.0f : 0.0f;
-        const double x = double(num < 0 ? -num : num) / double(n);
-        const double px = M_PI * x, pxa = px / double(a);
-        return float((std::sin(px) / px) * (std::sin(pxa) / pxa));
-    }
-
-    void make_table(int n, int a, float *h)                 // [n][2a], row 0 the unit impulse at t = a
-    {
-        for (int k = 0; k < n; ++k)
-            for (int t = 0; t < 2 * a; ++t)
-                h[k * 2 * a + t] = lanczos_tap(n * (t - a) + k, n, a);
-    }
+    constexpr int TABLE_PAIRS = PHASES * (4 + 6 + 8 + 20 + 124);
+    constexpr int table_offset(int n, int a) { return PHASES * a_taps_before(a) + phases_before(n) * 2 * a; }
 
     constexpr int block_of(int n) { return (n >= 6) ? 128 : 256; }      // 32 KB of LDS at every N
 
@@ -94,27 +65,14 @@ namespace
         static_assert(BLOCK >= TAPS, "the carry is one value per thread");
     };
 
-    // a <= 10: the outputs p = o .. o + 7 of phase k from r[j] = lin[o + j].  Pairs of consecutive outputs share a packed
-    // multiply and a packed add; even-aligned pairs of inputs are the loaded ones, odd ones are made (truepeak.hip).
+    // a <= 10: the outputs p = o .. o + 7 of phase k from r[j] = lin[o + j], the sums started from +0.0f, the values kept
     template <int N, int A>
     __device__ __forceinline__ void phases_packed(const float *lin, float *planes, const_pairs h, int o)
     {
         using S = shape<N, A>;
-        constexpr int TAPS = S::TAPS, R = S::R;
-        float r[S::RL];
-        #pragma unroll
-        for (int j = 0; j < S::RL / 4; ++j)
-        {
-            const float4 v = *reinterpret_cast<const float4 *>(&lin[o + 4 * j]);
-            r[4 * j] = v.x; r[4 * j + 1] = v.y; r[4 * j + 2] = v.z; r[4 * j + 3] = v.w;
-        }
-        f32x2 ev[R / 2], od[R / 2 - 1];
-        #pragma unroll
-        for (int j = 0; j < R / 2; ++j)
-            ev[j] = f32x2{ r[2 * j], r[2 * j + 1] };
-        #pragma unroll
-        for (int j = 0; j < R / 2 - 1; ++j)
-            od[j] = f32x2{ r[2 * j + 1], r[2 * j + 2] };
+        constexpr int TAPS = S::TAPS;
+        MI_LANCZOS_WINDOW(r, lin, o, S::RL)
+        MI_LANCZOS_PAIRS(ev, od, r, S::R);
         #pragma unroll 1
         for (int k = 1; k < N; ++k)
         {
@@ -123,14 +81,7 @@ namespace
             #pragma unroll
             for (int q = 0; q < PT / 2; ++q)
             {
-                // outputs o + 2q, o + 2q + 1 read inputs r[TAPS + 2q - t], r[TAPS + 2q + 1 - t]
-                f32x2 acc = f32x2{ 0.0f, 0.0f };
-                #pragma unroll
-                for (int t = TAPS - 1; t >= 0; --t)
-                {
-                    const int b = TAPS + 2 * q - t;
-                    acc = acc + hk[t] * ((b % 2 == 0) ? ev[b / 2] : od[b / 2]);
-                }
+                MI_LANCZOS_PAIR_SUM(acc, hk, ev, od, TAPS, q, true);        // the sign of a zero is kept
                 out[2 * q] = acc.x;
                 out[2 * q + 1] = acc.y;
             }
@@ -181,8 +132,8 @@ namespace
         }
     }
 
-    // One workgroup per (split, row): inputs [split * span, min(count, (split + 1) * span)) of the row, TILE at a time, the
-    // TAPS inputs before the tile carried in LDS.  dst and src are disjoint, so a later split reads the inputs before its
+    // One workgroup per (split, row): inputs [split * span, min(count, (split + 1) * span)) of the row, in lanczos_device.h's
+    // tile walk.  dst and src are disjoint, so a later split reads the inputs before its
     // range from src; split 0 reads the state (splits == 1) or the copy oversampler_stage_kernel made of it.
     template <int N, int A>
     __global__ __launch_bounds__(block_of(N)) void oversampler_up_kernel(float *dst, const float *src, size_t dst_stride,
@@ -205,12 +156,7 @@ namespace
         for (uint32_t t0 = begin; t0 < end; t0 += TILE)
         {
             const uint32_t n = (end - t0 < uint32_t(TILE)) ? end - t0 : uint32_t(TILE);
-            #pragma unroll
-            for (int j = 0; j < PT; ++j)
-            {
-                const uint32_t p = uint32_t(j * BLOCK + tid);
-                lin[TAPS + p] = (p < n) ? xs[t0 + p] : 0.0f;
-            }
+            MI_LANCZOS_FILL_TILE(lin, xs, t0, n, tid, TAPS, BLOCK, PT)
             __syncthreads();
             if constexpr (A <= 10)
                 phases_packed<N, A>(lin, planes, h, tid * PT);
@@ -253,7 +199,8 @@ namespace
     }
 
     // Before a split launch, one workgroup per row: halo[row] = the state, and the new state = the last `taps` inputs of
-    // the call.  All of them are read before any is written.
+    // the call.  All of them are read before any is written.  (truepeak_stage_kernel is a different kernel on purpose: the
+    // meter runs in place, so it has to copy the inputs before every split as well.)
     __global__ __launch_bounds__(STAGE_BLOCK) void oversampler_stage_kernel(const float *src, size_t src_stride, uint32_t count,
                                                                             uint32_t taps, float *state, float *halo)
     {
@@ -329,17 +276,6 @@ namespace
     {
         return a.nType == b.nType && a.nSlope == b.nSlope && a.fFreq == b.fFreq && a.fFreq2 == b.fFreq2 && a.fGain == b.fGain &&
                a.fQuality == b.fQuality;
-    }
-
-    int capturing(hipStream_t st, bool *yes)
-    {
-        *yes = false;
-        if (st == nullptr)
-            return MI_OK;
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        MI_HIP_CHECK(hipStreamIsCapturing(st, &cs));
-        *yes = cs != hipStreamCaptureStatusNone;
-        return MI_OK;
     }
 
     // the scratch rows of a call of `count` samples at the current factor
@@ -428,17 +364,8 @@ namespace
                    hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, int aligned)
     {
         using S = shape<N, A>;
-        const uint32_t tiles = (count + S::TILE - 1) / S::TILE;
-        uint32_t splits = 1, span = count;
-        if (tiles >= 2)
-        {
-            // enough workgroups to fill the device, every split a whole number of tiles
-            uint32_t want = (1024 + b->channels - 1) / b->channels;
-            want = (want < MAX_SPLITS) ? want : MAX_SPLITS;
-            want = (want < tiles) ? want : tiles;
-            span = ((tiles + want - 1) / want) * S::TILE;
-            splits = (count + span - 1) / span;
-        }
+        const split_plan plan = plan_splits(count, S::TILE, b->channels, MAX_SPLITS);
+        const uint32_t splits = plan.splits, span = plan.span;
         if (splits > 1)
             hipLaunchKernelGGL(oversampler_stage_kernel, dim3(b->channels), dim3(STAGE_BLOCK), 0, st, src, src_stride, count,
                                uint32_t(S::TAPS), b->d_state, b->d_halo);
@@ -521,20 +448,15 @@ int mi_oversampler_bank_create(mi_oversampler_bank_t **bank, uint32_t channels) 
     MI_REQUIRE(mi_dspu_device_count() > 0, MI_ENODEV, "no HIP device available (there is no CPU fallback)");
     mi_oversampler_bank *b = new (std::nothrow) mi_oversampler_bank();
     f32x2 *table = new (std::nothrow) f32x2[TABLE_PAIRS];
-    float *rows = new (std::nothrow) float[8 * STATE];
-    if (b == nullptr || table == nullptr || rows == nullptr)
+    if (b == nullptr || table == nullptr)
     {
-        delete b; delete[] table; delete[] rows;
+        delete b; delete[] table;
         return mi::fail(MI_ENOMEM, "mi_oversampler_bank_create: out of host memory");
     }
     b->channels = channels;
-    for (int a : { 2, 3, 4, 10, 62 })
-        for (int n : { 2, 3, 4, 6, 8 })
-        {
-            make_table(n, a, rows);
-            for (int j = 0; j < (n - 1) * 2 * a; ++j)
-                table[table_offset(n, a) + j] = f32x2{ rows[2 * a + j], rows[2 * a + j] };
-        }
+    for (int a : LATENCIES)
+        for (int n : FACTORS)
+            phase_pairs(n, a, table + table_offset(n, a));
     int r = mi_biquad_bank_create(&b->biquads, channels, FILTER_SECTIONS);
     hipError_t e = hipSuccess;
     if (r == MI_OK)
@@ -546,7 +468,6 @@ int mi_oversampler_bank_create(mi_oversampler_bank_t **bank, uint32_t channels) 
         if (e == hipSuccess) e = hipMemset(b->d_state, 0, size_t(channels) * STATE * sizeof(float));
     }
     delete[] table;
-    delete[] rows;
     if (r != MI_OK || e != hipSuccess)
     {
         mi_oversampler_bank_destroy(b);

@@ -3,27 +3,23 @@
 // lanczos_resample_Nx16bit (a = 10) and every output is the largest magnitude of its N oversampled values (reduce_Nx,
 // :115-147).
 //
-// The reference SCATTERS each input into a buffer of pending sums: buf[N j + a N + d] += L(d / N) x[j], |d| < a N, zero
-// taps skipped.  An oversampled value is final once input i has been added, so the same bits come out of the GATHER
-//      y[N i + k] = ((h_k[2a-1] x[i-2a+1] + h_k[2a-2] x[i-2a+2]) + ...) + h_k[0] x[i],   h_k[t] = float(L(t - a + k / N))
-// in the scatter's order (oldest input first, every product and every sum rounded on its own), and y[N i] = x[i - a].
-// The meter's state is the last 2a inputs of each channel: [channels][2a] on the device, read at the start of a call and
-// written at its end, so the bank keeps no positions on the host and a captured graph replays correctly.
+// The oversampled values (coefficients, window, pairs, packed tap loop, tile fill) and the planning of a launch are
+// lanczos_device.h's, shared with oversampler.hip.  The meter's own: the largest magnitude of every N values, kept in
+// registers, and the splits of an in-place call.  State: [channels][2a] on the device.
 //
 // process_max: the reference's (:238-272) returns 0.0f and looks at only `to_process` of the N * to_process oversampled
 // values.  Here it is what the header documents: the largest value process() would have written, with the state
 // advanced exactly as process() advances it.
-#include "mi_common.h"
+#include "lanczos_device.h"
 
-#include <cmath>
 #include <new>
 
-// The tap loop must stay separate multiplies and adds in the scatter's order: no fused multiply-add may form, whatever
-// -ffp-contract the file is compiled with (v_pk_mul_f32 / v_pk_add_f32 round each half on its own, so they keep the bits).
-#pragma clang fp contract(off)
+#pragma clang fp contract(off)      // no fused multiply-add in the tap loops below: lanczos_device.h says why
 
 namespace
 {
+    using namespace mi_lanczos;
+
     constexpr int      A          = 10;                 // Lanczos a of the *16bit kernels (TRUE_PEAK_LATENCY, :34)
     constexpr int      TAPS       = 2 * A;              // inputs behind one oversampled value; the state per channel
     constexpr int      BLOCK      = 256;
@@ -34,15 +30,8 @@ namespace
     constexpr int      STAGE_ITEMS = 6;                 // per thread of the staging kernel: (MAX_SPLITS + 1) * TAPS <= 6 * BLOCK
     static_assert((MAX_SPLITS + 1) * TAPS <= STAGE_ITEMS * BLOCK, "staging items");
 
-    // the device table: the non-centre phases k = 1 .. N-1 of N = 2, 3, 4, 6, 8, TAPS floats each
-    constexpr int TABLE_FLOATS = (1 + 2 + 3 + 5 + 7) * TAPS;
-    __host__ __device__ constexpr int table_offset(int n)
-    {
-        return (n == 2) ? 0 : (n == 3) ? 1 * TAPS : (n == 4) ? 3 * TAPS : (n == 6) ? 6 * TAPS : (n == 8) ? 11 * TAPS : -1;
-    }
-
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef const __attribute__((address_space(4))) f32x2 *const_pairs;
+    constexpr int      TABLE_PAIRS = PHASES * TAPS; // the device table: phase_pairs of every N
+    __host__ __device__ constexpr int table_offset(int n) { return phases_before(n) * TAPS; }
 
     // TruePeakMeter::calc_oversampling_multiplier, TruePeakMeter.cpp:85-100 (TRUE_PEAK_FREQUENCY = 4 * 44100)
     uint32_t oversampling(uint32_t sr)
@@ -51,40 +40,12 @@ namespace
         return (s >= f) ? 0 : (s * 2 >= f) ? 2 : (s * 3 >= f) ? 3 : (s * 4 >= f) ? 4 : (s * 6 >= f) ? 6 : 8;
     }
 
-    // L(x) = sinc(x) sinc(x / a) at x = num / n, in double, rounded to float once.  |num| makes the table bit-symmetric.
-    // At whole x the kernel is exactly 1 (x = 0) or 0, not the rounding residue of sin(pi x).
-    float lanczos_tap(int num, int n)
-    {
-        if (num % n == 0)
-            return (num == 0) ? 1.0f : 0.0f;
-        const double x = double(num < 0 ? -num : num) / double(n);
-        const double px = M_PI * x, pxa = px / double(A);
-        return float((std::sin(px) / px) * (std::sin(pxa) / pxa));
-    }
-
-    void make_table(uint32_t n, float *h)                   // [n][TAPS], row 0 the unit impulse at t = a
-    {
-        for (uint32_t k = 0; k < n; ++k)
-            for (int t = 0; t < TAPS; ++t)
-                h[k * TAPS + t] = lanczos_tap(int(n) * (t - A) + int(k), int(n));
-    }
-
-    // One trip's worth of outputs of one thread: p = o .. o + PER_THREAD - 1 of the tile, from r[j] = lds[o + j], where
-    // lds[TAPS + p] holds input p of the tile and lds[0 .. TAPS) the inputs before it.  Pairs of consecutive outputs of one
-    // phase share a packed multiply and a packed add; even-aligned pairs of inputs are the loaded ones, odd ones are made.
-    // The phases are a loop that is not unrolled: one phase's 20 coefficient pairs (40 SGPRs, loaded as they are stored,
-    // each value twice) are all the scalar registers hold, where all phases at once would spill them into vector lanes.
+    // One trip's worth of outputs of one thread: p = o .. o + PER_THREAD - 1 of the tile, from r[j] = lds[o + j]: the
+    // largest magnitude over the phases
     template <int N>
     __device__ __forceinline__ void tile_outputs(const float *r, const_pairs h, float *out)
     {
-        constexpr int R = PER_THREAD + TAPS;
-        f32x2 ev[R / 2], od[R / 2 - 1];
-        #pragma unroll
-        for (int j = 0; j < R / 2; ++j)
-            ev[j] = f32x2{ r[2 * j], r[2 * j + 1] };
-        #pragma unroll
-        for (int j = 0; j < R / 2 - 1; ++j)
-            od[j] = f32x2{ r[2 * j + 1], r[2 * j + 2] };
+        MI_LANCZOS_PAIRS(ev, od, r, PER_THREAD + TAPS);
         #pragma unroll
         for (int j = 0; j < PER_THREAD; ++j)
             out[j] = fabsf(r[TAPS + j - A]);                    // k = 0: y[N i] = x[i - a]
@@ -95,15 +56,7 @@ namespace
             #pragma unroll
             for (int q = 0; q < PER_THREAD / 2; ++q)
             {
-                // outputs o + 2q, o + 2q + 1 read inputs r[TAPS + 2q - t], r[TAPS + 2q + 1 - t]
-                f32x2 acc;
-                #pragma unroll
-                for (int t = TAPS - 1; t >= 0; --t)
-                {
-                    const int b = TAPS + 2 * q - t;
-                    const f32x2 p = hk[t] * ((b % 2 == 0) ? ev[b / 2] : od[b / 2]);
-                    acc = (t == TAPS - 1) ? p : acc + p;        // 0 + p == p but for the sign of a zero, which |.| drops
-                }
+                MI_LANCZOS_PAIR_SUM(acc, hk, ev, od, TAPS, q, false);       // |.| drops the sign of a zero
                 out[2 * q] = fmaxf(out[2 * q], fabsf(acc.x));
                 out[2 * q + 1] = fmaxf(out[2 * q + 1], fabsf(acc.y));
             }
@@ -118,8 +71,8 @@ namespace
             out[j] = fabsf(r[TAPS + j]);                        // dsp::abs2 (:202-205)
     }
 
-    // One workgroup per (split, row): inputs [split * span, min(count, (split + 1) * span)) of the row, TILE at a time, the
-    // TAPS inputs before the tile carried in LDS.  The whole tile is in LDS before any output is stored, so dst may be src:
+    // One workgroup per (split, row): inputs [split * span, min(count, (split + 1) * span)) of the row, in lanczos_device.h's
+    // tile walk.  The whole tile is in LDS before any output is stored, so dst may be src:
     // with one split the workgroup owns its row; with several the inputs before each split were staged beforehand
     // (truepeak_stage_kernel), and no workgroup reads inputs of another split's range.
     // MAX: no dst; the largest output of the range goes to peaks[row] (atomically when the row is split; peaks zeroed first).
@@ -142,21 +95,11 @@ namespace
         for (uint32_t t0 = begin; t0 < end; t0 += TILE)
         {
             const uint32_t n = (end - t0 < uint32_t(TILE)) ? end - t0 : uint32_t(TILE);
-            #pragma unroll
-            for (int j = 0; j < PER_THREAD; ++j)
-            {
-                const uint32_t p = uint32_t(j * BLOCK + tid);
-                lin[TAPS + p] = (p < n) ? xs[t0 + p] : 0.0f;
-            }
+            MI_LANCZOS_FILL_TILE(lin, xs, t0, n, tid, TAPS, BLOCK, PER_THREAD)
             __syncthreads();
             const int o = tid * PER_THREAD;
-            float r[PER_THREAD + TAPS], out[PER_THREAD];
-            #pragma unroll
-            for (int j = 0; j < (PER_THREAD + TAPS) / 4; ++j)
-            {
-                const float4 v = *reinterpret_cast<const float4 *>(&lin[o + 4 * j]);
-                r[4 * j] = v.x; r[4 * j + 1] = v.y; r[4 * j + 2] = v.z; r[4 * j + 3] = v.w;
-            }
+            MI_LANCZOS_WINDOW(r, lin, o, PER_THREAD + TAPS)
+            float out[PER_THREAD];
             tile_outputs<N>(r, h, out);
             if (MAX)
             {
@@ -213,7 +156,8 @@ namespace
 
     // Before a split launch, one workgroup per row: halo[row][s] = the TAPS inputs before split s (split 0: the state), and
     // the new state = the last TAPS inputs of the call.  All of them are read before any is written, so the state may be
-    // overwritten here and the splits of an in-place call find their halos intact.
+    // overwritten here and the splits of an in-place call find their halos intact.  (oversampler_stage_kernel is a
+    // different kernel on purpose: upsampling never runs in place, so its splits read their halos from src.)
     __global__ __launch_bounds__(BLOCK) void truepeak_stage_kernel(const float *src, size_t src_stride, uint32_t count, uint32_t span,
                                                                    uint32_t splits, float *state, float *halo)
     {
@@ -253,7 +197,7 @@ struct mi_truepeak_bank
     uint32_t    times = 0;              // nTimes
     bool        update = true;          // bUpdate
     float      *d_state = nullptr;      // [channels][TAPS]
-    f32x2      *d_taps = nullptr;       // TABLE_FLOATS pairs (each coefficient twice: the packed multiply's operand)
+    f32x2      *d_taps = nullptr;       // TABLE_PAIRS
     float      *d_halo = nullptr;       // [channels][MAX_SPLITS][TAPS] when channels <= SPLIT_ROWS
 };
 
@@ -271,11 +215,13 @@ namespace
         if (!b->update)
             return MI_OK;
         const uint32_t times = oversampling(b->sample_rate);
-        if (times != b->times && st != nullptr)
+        if (times != b->times)
         {
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            MI_HIP_CHECK(hipStreamIsCapturing(st, &cs));
-            MI_REQUIRE(cs == hipStreamCaptureStatusNone, MI_ESTATE,
+            bool cap = false;
+            const int r = capturing(st, &cap);
+            if (r != MI_OK)
+                return r;
+            MI_REQUIRE(!cap, MI_ESTATE,
                        "mi_truepeak_bank: a new oversampling factor clears the state; call update_settings() before capturing");
         }
         b->update = false;
@@ -289,17 +235,10 @@ namespace
     int tp_launch(mi_truepeak_bank *b, float *dst, const float *src, uint32_t count, size_t dst_stride, size_t src_stride,
                   float *peaks, hipStream_t st)
     {
-        const uint32_t tiles = (count + TILE - 1) / TILE;
-        uint32_t splits = 1, span = count;
-        if (b->d_halo != nullptr && tiles >= 2)
-        {
-            // enough workgroups to fill the device, every split a whole number of tiles
-            uint32_t want = (1024 + b->channels - 1) / b->channels;
-            want = (want < MAX_SPLITS) ? want : MAX_SPLITS;
-            want = (want < tiles) ? want : tiles;
-            span = ((tiles + want - 1) / want) * TILE;
-            splits = (count + span - 1) / span;
-        }
+        // no halo buffer above SPLIT_ROWS rows: there are workgroups enough, and a row stays whole
+        const split_plan plan = (b->d_halo != nullptr) ? plan_splits(count, TILE, b->channels, MAX_SPLITS)
+                                                           : split_plan{ 1, count };
+        const uint32_t splits = plan.splits, span = plan.span;
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         mi::take_profile_events(&ev0, &ev1);
         if (splits > 1 && b->times != 0)
@@ -335,7 +274,7 @@ int mi_truepeak_coefficients(uint32_t times, float *h, size_t *count)
     MI_REQUIRE(times == 0 || table_offset(int(times)) >= 0, MI_EINVAL, "mi_truepeak_coefficients: no kernel for %u times", times);
     *count = size_t(times) * TAPS;
     if (h != nullptr && times != 0)
-        make_table(times, h);
+        make_table(int(times), A, h);
     return MI_OK;
 }
 
@@ -348,14 +287,9 @@ int mi_truepeak_bank_create(mi_truepeak_bank_t **bank, uint32_t channels)       
     mi_truepeak_bank *b = new (std::nothrow) mi_truepeak_bank();
     MI_REQUIRE(b != nullptr, MI_ENOMEM, "mi_truepeak_bank_create: out of host memory");
     b->channels = channels;
-    f32x2 table[TABLE_FLOATS];
-    float row[8 * TAPS];
-    for (int n : { 2, 3, 4, 6, 8 })
-    {
-        make_table(uint32_t(n), row);
-        for (int j = 0; j < (n - 1) * TAPS; ++j)
-            table[table_offset(n) + j] = f32x2{ row[TAPS + j], row[TAPS + j] };
-    }
+    f32x2 table[TABLE_PAIRS];
+    for (int n : FACTORS)
+        phase_pairs(n, A, table + table_offset(n));
     hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_state), size_t(channels) * TAPS * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_taps), sizeof(table));
     if (e == hipSuccess && channels <= SPLIT_ROWS)
