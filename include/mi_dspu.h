@@ -898,6 +898,68 @@ int mi_oversampler_bank_get_filter(const mi_oversampler_bank_t *bank, mi_filter_
  * No device needed. */
 int mi_oversampler_coefficients(uint32_t mode, float *h, size_t *count);
 
+/* ---- compressor bank (envelope follower and two-knee gain curve) ------------------------------------------------------ */
+/*
+ * mi_compressor_bank: `channels` x lsp::dspu::Compressor (dynamics/Compressor.h:44-289, src/main/dynamics/Compressor.cpp),
+ * every channel with settings of its own.  process() is the reference's: the envelope follower (:226-259), a serial
+ * recurrence over (fEnvelope, fPeak, nHoldCounter), then the gain curve of two knees (dsp::compressor_x2_gain, as the scalar
+ * overload states it, :297-310).  The envelope, the peak and the hold counter are the reference's bit for bit in float32
+ * (each product and each sum rounds once); the gain goes through the device's logf / expf and is within the bound
+ * DESIGN.md section 3.10 derives.  The state lives on the device; the bank has no positions, so its process calls can be
+ * captured into a graph and replayed.  Inputs are finite: NaN is out of scope.  Subnormal envelopes are kept.
+ * Rows of the sample buffers: [channels][stride].
+ */
+typedef struct mi_compressor_bank mi_compressor_bank_t;
+enum mi_compressor_mode { MI_CM_DOWNWARD = 0, MI_CM_UPWARD = 1, MI_CM_BOOSTING = 2 };     /* compressor_mode_t */
+/* dsp::compressor_knee_t / compressor_x2_t of lsp-dsp-lib: below start the constant gain, above end
+ * exp(tilt[0] ln x + tilt[1]), between them exp((herm[0] ln x + herm[1]) ln x + herm[2]) */
+typedef struct { float start, end, gain, herm[3], tilt[2]; } mi_compressor_knee_t;
+/* what update_settings() computes: fTauAttack, fTauRelease, fReleaseThresh as set, nHold, sComp */
+typedef struct { float tau_attack, tau_release, release_threshold; uint32_t hold; mi_compressor_knee_t k[2]; } mi_compressor_params_t;
+/* the setters' values: times in ms, thresholds, knee and ratio as the reference takes them */
+typedef struct
+{
+    uint32_t sample_rate, mode;
+    float attack_threshold, release_threshold, boost_threshold, attack, release, hold, knee, ratio;
+} mi_compressor_settings_t;
+/* update_settings(), :89-220, of one compressor in host float32 (expf, logf): all three modes, boosting with its two cases
+ * on boost_threshold >= 1.  No device needed. */
+int mi_compressor_compute_params(const mi_compressor_settings_t *settings, mi_compressor_params_t *params);
+/* construct(), :46-83: every channel DOWNWARD, ratio 1, boost threshold -72 dB, everything else 0, an update pending */
+int mi_compressor_bank_create(mi_compressor_bank_t **bank, uint32_t channels);
+int mi_compressor_bank_destroy(mi_compressor_bank_t *bank);
+/* The setters of one channel (:362-461): each returns early on an unchanged value, otherwise the channel's update is
+ * pending until update_settings().  set_knee limits to [0, 1], set_hold to >= 0, as the reference does. */
+int mi_compressor_bank_set_sample_rate(mi_compressor_bank_t *bank, uint32_t channel, uint32_t sample_rate);
+int mi_compressor_bank_set_mode(mi_compressor_bank_t *bank, uint32_t channel, uint32_t mode);
+int mi_compressor_bank_set_threshold(mi_compressor_bank_t *bank, uint32_t channel, float attack, float release);
+int mi_compressor_bank_set_boost_threshold(mi_compressor_bank_t *bank, uint32_t channel, float boost);
+int mi_compressor_bank_set_timings(mi_compressor_bank_t *bank, uint32_t channel, float attack, float release);
+int mi_compressor_bank_set_hold(mi_compressor_bank_t *bank, uint32_t channel, float hold);
+int mi_compressor_bank_set_knee(mi_compressor_bank_t *bank, uint32_t channel, float knee);
+int mi_compressor_bank_set_ratio(mi_compressor_bank_t *bank, uint32_t channel, float ratio);
+/* update_settings() of every channel with an update pending; the changed stretch of the parameter table goes to the device
+ * (and the call waits for it).  The process entries run it first, as the reference's do.  On a stream being captured a
+ * pending update is refused (MI_ESTATE): call it before the capture.  clear(): envelope, peak and hold counter to zero. */
+int mi_compressor_bank_update_settings(mi_compressor_bank_t *bank, void *stream);
+int mi_compressor_bank_clear(mi_compressor_bank_t *bank, void *stream);
+/* What the last update_settings() computed for the channel (HOST memory); fEnvelope, fPeak, nHoldCounter of the channel as
+ * the work enqueued on `stream` leaves them (HOST memory, each may be NULL; waits for the stream) */
+int mi_compressor_bank_get_params(const mi_compressor_bank_t *bank, uint32_t channel, mi_compressor_params_t *params);
+int mi_compressor_bank_get_state(mi_compressor_bank_t *bank, uint32_t channel, float *envelope, float *peak, uint32_t *hold,
+                                 void *stream);
+/* process(out, env, in, samples), :222-267: gain receives the VCA gain, env (NULL: not wanted) the envelope.  gain or env
+ * may be the input rows (in place, same stride); gain and env differ. */
+int mi_compressor_bank_process(mi_compressor_bank_t *bank, float *gain, float *env, const float *in, size_t count,
+                               size_t gain_stride, size_t env_stride, size_t in_stride, void *stream);
+/* dst = audio * gain(sc) in the same launch: process() on the sidechain rows sc followed by one float32 multiply, bit for
+ * bit.  dst may be audio or sc (same stride). */
+int mi_compressor_bank_process_apply(mi_compressor_bank_t *bank, float *dst, const float *audio, const float *sc, size_t count,
+                                     size_t dst_stride, size_t audio_stride, size_t sc_stride, void *stream);
+/* curve(out, in, dots), :313-334: out = gain(|in|) |in| of every channel's curve, stateless; update_settings() first */
+int mi_compressor_bank_curve(mi_compressor_bank_t *bank, float *out, const float *in, size_t dots, size_t out_stride,
+                             size_t in_stride, void *stream);
+
 /*
  * mi_splitter_bank: lsp::dspu::SpectralSplitter for `channels` channels sharing the settings
  * (util/SpectralSplitter.h:62-250, src/main/util/SpectralSplitter.cpp:62-361) -- the engine of lsp::dspu::FFTCrossover.

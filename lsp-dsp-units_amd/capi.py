@@ -34,6 +34,24 @@ class BiquadX1(ctypes.Structure):
     _fields_ = [(n, c_float) for n in ("b0", "b1", "b2", "a1", "a2", "p0", "p1", "p2")]
 
 
+class CompressorKnee(ctypes.Structure):
+    """mi_compressor_knee_t == dsp::compressor_knee_t layout."""
+    _fields_ = [("start", c_float), ("end", c_float), ("gain", c_float), ("herm", c_float * 3), ("tilt", c_float * 2)]
+
+
+class CompressorParams(ctypes.Structure):
+    """mi_compressor_params_t: what Compressor::update_settings computes."""
+    _fields_ = [("tau_attack", c_float), ("tau_release", c_float), ("release_threshold", c_float), ("hold", c_uint32),
+                ("k", CompressorKnee * 2)]
+
+
+class CompressorSettings(ctypes.Structure):
+    """mi_compressor_settings_t: the values of Compressor's setters."""
+    _fields_ = [("sample_rate", c_uint32), ("mode", c_uint32)] + \
+               [(n, c_float) for n in ("attack_threshold", "release_threshold", "boost_threshold", "attack", "release",
+                                       "hold", "knee", "ratio")]
+
+
 # name -> (restype, argtypes); every symbol declared in include/mi_dspu.h must be listed here
 # (tests/test_abi.py parses the header and checks both directions).
 PROTOTYPES = {
@@ -209,6 +227,24 @@ PROTOTYPES = {
     "mi_oversampler_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p]),
     "mi_oversampler_bank_get_filter": (c_int, [c_void_p, POINTER(FilterParams), POINTER(c_uint32)]),
     "mi_oversampler_coefficients": (c_int, [c_uint32, POINTER(c_float), POINTER(c_size_t)]),
+    "mi_compressor_compute_params": (c_int, [POINTER(CompressorSettings), POINTER(CompressorParams)]),
+    "mi_compressor_bank_create": (c_int, [POINTER(c_void_p), c_uint32]),
+    "mi_compressor_bank_destroy": (c_int, [c_void_p]),
+    "mi_compressor_bank_set_sample_rate": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_compressor_bank_set_mode": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_compressor_bank_set_threshold": (c_int, [c_void_p, c_uint32, c_float, c_float]),
+    "mi_compressor_bank_set_boost_threshold": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_compressor_bank_set_timings": (c_int, [c_void_p, c_uint32, c_float, c_float]),
+    "mi_compressor_bank_set_hold": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_compressor_bank_set_knee": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_compressor_bank_set_ratio": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_compressor_bank_update_settings": (c_int, [c_void_p, c_void_p]),
+    "mi_compressor_bank_clear": (c_int, [c_void_p, c_void_p]),
+    "mi_compressor_bank_get_params": (c_int, [c_void_p, c_uint32, POINTER(CompressorParams)]),
+    "mi_compressor_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(c_float), POINTER(c_float), POINTER(c_uint32), c_void_p]),
+    "mi_compressor_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_compressor_bank_process_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_compressor_bank_curve": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_splitter_bank_create": (c_int, [POINTER(c_void_p), c_uint32, c_uint32, c_uint32]),
     "mi_splitter_bank_destroy": (c_int, [c_void_p]),
     "mi_splitter_bank_set_rank": (c_int, [c_void_p, c_uint32]),

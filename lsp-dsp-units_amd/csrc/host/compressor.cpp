@@ -1,0 +1,391 @@
+// lsp::dspu::Compressor (src/main/dynamics/Compressor.cpp) on a mi_compressor_bank of one channel.  The class has no member
+// to hang the bank on (its 132 bytes are the reference's), so the bank and its staging buffers live in a table keyed by the
+// object's address: made at the first call that needs the device, dropped in destroy() and in construct().  Before every
+// device call the bank is handed the object's own fTau*, fReleaseThresh, nHold and sComp; process() also sends fEnvelope,
+// fPeak and nHoldCounter when they are not what it read back after the previous call (a subclass may write the protected
+// fields), and reads them back afterwards.  An object whose storage is released without destroy() or its destructor leaves
+// its entry behind until a Compressor is constructed at that address again.
+#include <lsp-plug.in/dsp-units/dynamics/Compressor.h>
+
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <new>
+#include <unordered_map>
+
+#include "compressor_bank.h"
+
+namespace lsp
+{
+namespace dspu
+{
+namespace
+{
+    struct compressor_impl
+    {
+        mi_compressor_bank_t *bank = nullptr;
+        float  *d_buf = nullptr;            // [2][cap]: the staged input (gain in place on it), the envelope
+        size_t  cap = 0;
+        float   e = 0.0f, peak = 0.0f;      // the follower's state as the device holds it: a fresh bank's, then what
+        uint32_t hold = 0;                  // process() read back
+
+        bool reserve(size_t n)
+        {
+            if (n <= cap)
+                return true;
+            mi_dspu_free(d_buf);
+            d_buf = nullptr;
+            cap = 0;
+            if (mi_dspu_malloc(reinterpret_cast<void **>(&d_buf), 2 * n * sizeof(float)) != MI_OK)
+                return false;
+            cap = n;
+            return true;
+        }
+    };
+
+    std::mutex g_lock;
+    std::unordered_map<const void *, compressor_impl *> &table()
+    {
+        static std::unordered_map<const void *, compressor_impl *> t;
+        return t;
+    }
+
+    compressor_impl *impl_of(const void *self, bool make)
+    {
+        std::lock_guard<std::mutex> guard(g_lock);
+        auto it = table().find(self);
+        if (it != table().end())
+            return it->second;
+        if (!make)
+            return nullptr;
+        compressor_impl *p = new (std::nothrow) compressor_impl();
+        if (p == nullptr)
+            return nullptr;
+        if (mi_compressor_bank_create(&p->bank, 1) != MI_OK)
+        {
+            delete p;
+            return nullptr;
+        }
+        table()[self] = p;
+        return p;
+    }
+
+    void drop(const void *self)
+    {
+        compressor_impl *p = nullptr;
+        {
+            std::lock_guard<std::mutex> guard(g_lock);
+            auto it = table().find(self);
+            if (it == table().end())
+                return;
+            p = it->second;
+            table().erase(it);
+        }
+        mi_compressor_bank_destroy(p->bank);
+        mi_dspu_free(p->d_buf);
+        delete p;
+    }
+
+    inline float knee_gain(float x, float lx, const dsp::compressor_knee_t &k)     // Compressor.cpp:302-307
+    {
+        return (x <= k.start) ? k.gain :
+               (x >= k.end) ? expf(lx * k.tilt[0] + k.tilt[1]) :
+               expf((k.herm[0] * lx + k.herm[1]) * lx + k.herm[2]);
+    }
+
+    inline float x2_gain(float x, const dsp::compressor_x2_t &c)                    // :297-309, x = |input|
+    {
+        if ((x <= c.k[0].start) && (x <= c.k[1].start))
+            return c.k[0].gain * c.k[1].gain;
+        const float lx = logf(x);
+        return knee_gain(x, lx, c.k[0]) * knee_gain(x, lx, c.k[1]);
+    }
+}
+
+Compressor::Compressor()  { construct(); }
+Compressor::~Compressor() { destroy(); }
+
+void Compressor::construct()                                    // Compressor.cpp:46-83
+{
+    drop(this);                                                 // whatever lived at this address before
+    fAttackThresh = 0.0f;
+    fReleaseThresh = 0.0f;
+    fBoostThresh = float(2.5119e-4);                            // GAIN_AMP_M_72_DB
+    fAttack = 0.0f;
+    fRelease = 0.0f;
+    fKnee = 0.0f;
+    fRatio = 1.0f;
+    fHold = 0.0f;
+    fEnvelope = 0.0f;
+    fPeak = 0.0f;
+    fTauAttack = 0.0f;
+    fTauRelease = 0.0f;
+    for (size_t i = 0; i < 2; ++i)
+    {
+        dsp::compressor_knee_t *k = &sComp.k[i];
+        k->start = 0.0f;
+        k->end = 0.0f;
+        k->gain = 1.0f;
+        k->herm[0] = k->herm[1] = k->herm[2] = 0.0f;
+        k->tilt[0] = k->tilt[1] = 0.0f;
+    }
+    nHold = 0;
+    nHoldCounter = 0;
+    nSampleRate = 0;
+    nMode = CM_DOWNWARD;
+    bUpdate = true;
+}
+
+void Compressor::destroy()                                      // :85-87
+{
+    drop(this);
+}
+
+void Compressor::update_settings()                              // :89-220
+{
+    if (!bUpdate)
+        return;
+    mi_compressor_settings_t s;
+    s.sample_rate = nSampleRate;
+    s.mode = nMode;
+    s.attack_threshold = fAttackThresh;
+    s.release_threshold = fReleaseThresh;
+    s.boost_threshold = fBoostThresh;
+    s.attack = fAttack;
+    s.release = fRelease;
+    s.hold = fHold;
+    s.knee = fKnee;
+    s.ratio = fRatio;
+    mi_compressor_params_t p;
+    mi_compressor_compute_params(&s, &p);
+    fTauAttack = p.tau_attack;
+    fTauRelease = p.tau_release;
+    nHold = p.hold;
+    static_assert(sizeof(sComp) == sizeof(p.k), "knee layouts");
+    memcpy(&sComp, p.k, sizeof(sComp));
+    bUpdate = false;
+}
+
+namespace
+{
+    // the object's computed fields as the bank's channel 0
+    bool hand_over(compressor_impl *p, float ta, float tr, float rt, uint32_t hold, const dsp::compressor_x2_t &c)
+    {
+        mi_compressor_params_t q;
+        q.tau_attack = ta;
+        q.tau_release = tr;
+        q.release_threshold = rt;
+        q.hold = hold;
+        memcpy(q.k, &c, sizeof(q.k));
+        return mi::compressor_bank_set_params(p->bank, 0, &q) == MI_OK;
+    }
+
+    // the object's follower state as the bank's, where the fields are not what the device holds
+    bool hand_over_state(compressor_impl *p, float e, float peak, uint32_t hold)
+    {
+        if (memcmp(&e, &p->e, sizeof(e)) == 0 && memcmp(&peak, &p->peak, sizeof(peak)) == 0 && hold == p->hold)
+            return true;
+        if (mi::compressor_bank_set_state(p->bank, 0, e, peak, hold, nullptr) != MI_OK)
+            return false;
+        p->e = e, p->peak = peak, p->hold = hold;
+        return true;
+    }
+}
+
+void Compressor::process(float *out, float *env, const float *in, size_t samples)      // :222-267
+{
+    update_settings();
+    compressor_impl *p = impl_of(this, true);
+    if (p == nullptr || samples == 0 || !p->reserve(samples) ||
+        !hand_over(p, fTauAttack, fTauRelease, fReleaseThresh, nHold, sComp) ||
+        !hand_over_state(p, fEnvelope, fPeak, uint32_t(nHoldCounter)))
+        return;
+    float *d_in = p->d_buf, *d_env = p->d_buf + p->cap;
+    if (mi_dspu_copy_h2d(d_in, in, samples * sizeof(float), nullptr) != MI_OK ||
+        mi_compressor_bank_process(p->bank, d_in, (env != nullptr) ? d_env : nullptr, d_in, samples, samples, samples, samples, nullptr) != MI_OK ||
+        mi_dspu_copy_d2h(out, d_in, samples * sizeof(float), nullptr) != MI_OK)
+        return;
+    if (env != nullptr && mi_dspu_copy_d2h(env, d_env, samples * sizeof(float), nullptr) != MI_OK)
+        return;
+    if (mi_compressor_bank_get_state(p->bank, 0, &p->e, &p->peak, &p->hold, nullptr) != MI_OK)
+        return;
+    fEnvelope = p->e, fPeak = p->peak, nHoldCounter = p->hold;
+}
+
+float Compressor::process(float *env, float in)                 // :269-311: one sample on the device
+{
+    float out = 0.0f, e = 0.0f;
+    process(&out, &e, &in, 1);
+    if (env != NULL)
+        *env = e;
+    return out;
+}
+
+void Compressor::curve(float *out, const float *in, size_t dots)                        // :313-316
+{
+    compressor_impl *p = impl_of(this, true);
+    if (p == nullptr || dots == 0 || !p->reserve(dots) ||
+        !hand_over(p, fTauAttack, fTauRelease, fReleaseThresh, nHold, sComp))
+        return;
+    if (mi_dspu_copy_h2d(p->d_buf, in, dots * sizeof(float), nullptr) == MI_OK &&
+        mi_compressor_bank_curve(p->bank, p->d_buf, p->d_buf, dots, dots, dots, nullptr) == MI_OK &&
+        mi_dspu_copy_d2h(out, p->d_buf, dots * sizeof(float), nullptr) == MI_OK)
+        mi_dspu_stream_synchronize(nullptr);
+}
+
+float Compressor::curve(float in)                               // :318-334
+{
+    const float x = fabsf(in);
+    return x2_gain(x, sComp) * x;
+}
+
+void Compressor::reduction(float *out, const float *in, size_t dots)                    // :336-340: the curve, as the reference
+{
+    update_settings();
+    curve(out, in, dots);
+}
+
+float Compressor::reduction(float in)                           // :342-360
+{
+    update_settings();
+    return x2_gain(fabsf(in), sComp);
+}
+
+void Compressor::set_attack_threshold(float threshold)          // :362-368
+{
+    if (fAttackThresh == threshold)
+        return;
+    fAttackThresh = threshold;
+    bUpdate = true;
+}
+
+void Compressor::set_release_threshold(float threshold)         // :370-376
+{
+    if (fReleaseThresh == threshold)
+        return;
+    fReleaseThresh = threshold;
+    bUpdate = true;
+}
+
+void Compressor::set_threshold(float attack, float release)     // :378-385
+{
+    if ((fAttackThresh == attack) && (fReleaseThresh == release))
+        return;
+    fAttackThresh = attack;
+    fReleaseThresh = release;
+    bUpdate = true;
+}
+
+void Compressor::set_boost_threshold(float boost)               // :387-393
+{
+    if (fBoostThresh == boost)
+        return;
+    fBoostThresh = boost;
+    bUpdate = true;
+}
+
+void Compressor::set_timings(float attack, float release)       // :395-402
+{
+    if ((fAttack == attack) && (fRelease == release))
+        return;
+    fAttack = attack;
+    fRelease = release;
+    bUpdate = true;
+}
+
+void Compressor::set_attack(float attack)                       // :404-410
+{
+    if (fAttack == attack)
+        return;
+    fAttack = attack;
+    bUpdate = true;
+}
+
+void Compressor::set_release(float release)                     // :412-418
+{
+    if (fRelease == release)
+        return;
+    fRelease = release;
+    bUpdate = true;
+}
+
+void Compressor::set_sample_rate(size_t sr)                     // :420-426
+{
+    if (sr == nSampleRate)
+        return;
+    nSampleRate = uint32_t(sr);
+    bUpdate = true;
+}
+
+void Compressor::set_knee(float knee)                           // :428-435
+{
+    knee = (knee < 0.0f) ? 0.0f : (knee > 1.0f) ? 1.0f : knee;
+    if (knee == fKnee)
+        return;
+    fKnee = knee;
+    bUpdate = true;
+}
+
+void Compressor::set_ratio(float ratio)                         // :437-443
+{
+    if (ratio == fRatio)
+        return;
+    bUpdate = true;
+    fRatio = ratio;
+}
+
+void Compressor::set_mode(size_t mode)                          // :445-452
+{
+    if (nMode == mode)
+        return;
+    nMode = uint32_t(mode);
+    bUpdate = true;
+}
+
+void Compressor::set_hold(float hold)                           // :454-461
+{
+    hold = (hold > 0.0f) ? hold : 0.0f;
+    if (hold == fHold)
+        return;
+    fHold = hold;
+    bUpdate = true;
+}
+
+void Compressor::dump(IStateDumper *v) const                    // :463-501
+{
+    v->write("fAttackThresh", fAttackThresh);
+    v->write("fReleaseThresh", fReleaseThresh);
+    v->write("fBoostThresh", fBoostThresh);
+    v->write("fAttack", fAttack);
+    v->write("fRelease", fRelease);
+    v->write("fKnee", fKnee);
+    v->write("fRatio", fRatio);
+    v->write("fHold", fHold);
+    v->write("fEnvelope", fEnvelope);
+    v->write("fPeak", fPeak);
+    v->write("fTauAttack", fTauAttack);
+    v->write("fTauRelease", fTauRelease);
+    v->begin_object("sComp", &sComp, sizeof(sComp));
+    {
+        v->begin_array("k", sComp.k, 2);
+        for (size_t i = 0; i < 2; ++i)
+        {
+            const dsp::compressor_knee_t *k = &sComp.k[i];
+            v->begin_object(k, sizeof(dsp::compressor_knee_t));
+            v->write("start", k->start);
+            v->write("end", k->end);
+            v->write("gain", k->gain);
+            v->writev("herm", k->herm, 3);
+            v->writev("tilt", k->tilt, 2);
+            v->end_object();
+        }
+        v->end_array();
+    }
+    v->end_array();                                             // the reference closes the sComp object as an array
+    v->write("nSampleRate", nSampleRate);
+    v->write("nMode", nMode);
+    v->write("bUpdate", bUpdate);
+}
+
+} // namespace dspu
+} // namespace lsp

@@ -56,6 +56,19 @@ namespace lsp
         // lsp-dsp-lib's resampling function type (TruePeakMeter keeps one): dst receives the oversampled src
         typedef void (*resampling_function_t)(float *dst, const float *src, size_t count);
 
+        // lsp-dsp-lib's compressor curve (Compressor keeps one): below start the constant gain, above end
+        // exp(tilt[0] ln x + tilt[1]), between them exp((herm[0] ln x + herm[1]) ln x + herm[2]); two knees multiply
+        struct compressor_knee_t
+        {
+            float start;
+            float end;
+            float gain;
+            float herm[3];
+            float tilt[2];
+        };
+        struct compressor_x2_t { compressor_knee_t k[2]; };
+        static_assert(sizeof(compressor_knee_t) == 32 && sizeof(compressor_x2_t) == 64, "lsp-dsp-lib layouts");
+
         // lsp-dsp-lib's per-thread context / init are no-ops here: there is no SIMD dispatch to select
         struct context_t { uint32_t top; uint32_t data[15]; };
         inline void init() {}

@@ -1,0 +1,315 @@
+"""Compressor without a device: update_settings() (mi_compressor_compute_params) against float64, the float32 restatement of
+the curve inside the derived gain bound, the follower restatement on a hand-checked vector, the mirror header (layout,
+names, dump order, setters) and the rounding contract of the follower's ISA."""
+import json
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import compressor_ref as cr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "lsp-dsp-units_amd")
+CSRC = os.path.join(PKG, "csrc")
+f32 = np.float32
+
+
+def _cases():
+    base = dict(sample_rate=48000, attack_threshold=0.1, release_threshold=0.05, attack=1.5, release=40.0, hold=2.7, ratio=4.0)
+    out = []
+    for knee in (1.0, 0.5):
+        out.append(dict(base, mode=cr.CM_DOWNWARD, boost_threshold=2.5119e-4, knee=knee))
+        out.append(dict(base, mode=cr.CM_UPWARD, boost_threshold=0.004, knee=knee))
+        out.append(dict(base, mode=cr.CM_BOOSTING, boost_threshold=2.0, knee=knee))       # fBoostThresh >= 1
+        out.append(dict(base, mode=cr.CM_BOOSTING, boost_threshold=0.25, knee=knee))      # fBoostThresh < 1
+    out.append(dict(base, mode=cr.CM_BOOSTING, boost_threshold=2.0, knee=0.7, ratio=1.0))     # the ratio limited to 1 + 1e-5
+    out += [cr.channel_settings(ch) for ch in range(24)]
+    return out
+
+
+@pytest.mark.parametrize("case", range(len(_cases())))
+def test_update_settings_against_float64(mi, case):
+    s = _cases()[case]
+    got = mi.CompressorBank.compute_params(**s)
+    assert got["hold"] == cr.hold_samples(s["sample_rate"], s["hold"])                  # nHold: exact
+    want = cr.params64(**s)
+    flat = cr.flatten(got)
+    knee_open = [flat["k%d.start" % j] < flat["k%d.end" % j] for j in range(2)]
+    for name, q in want.items():
+        if "herm" in name and not knee_open[int(name[1])]:
+            continue                    # start == end: no sample reaches the knee polynomial (it divides by zero there)
+        assert np.isfinite(q.v), (name, q.v)
+        assert abs(flat[name] - q.v) <= q.err, (s, name, flat[name], q.v, abs(flat[name] - q.v) / cr.U / max(abs(q.v), 1e-300), q.err)
+
+
+def test_fresh_parameters_and_limits(mi):
+    p = mi.CompressorBank.compute_params()                      # as constructed: rate 0, times 0 -> tau 1
+    assert p["tau_attack"] == 1.0 and p["tau_release"] == 1.0 and p["hold"] == 0
+    assert p["k"][1]["start"] == f32(1e10) and p["k"][1]["gain"] == 1.0
+
+
+def _level_ladder(C):
+    db = np.linspace(-96.0, 12.0, 1729)
+    x = (10.0 ** (db / 20.0)).astype(f32)
+    x[::7] *= -1.0
+    return np.tile(x, (C, 1))
+
+
+def test_float32_curve_is_inside_the_gain_bound(mi):
+    params = [mi.CompressorBank.compute_params(**s) for s in _cases()]
+    x = _level_ladder(len(params))
+    # the knee bounds themselves and their float32 neighbours: the branch is chosen on float32 on both sides
+    for c, p in enumerate(params):
+        edges = [p["k"][j][n] for j in range(2) for n in ("start", "end")]
+        for i, v in enumerate(edges):
+            for d, w in enumerate((np.nextafter(f32(v), f32(0)), f32(v), np.nextafter(f32(v), f32(np.inf)))):
+                x[c, 3 * i + d] = w
+    g32, g64, bound = cr.gain32(x, params), cr.gain64(x, params), cr.gain_bound(x, params)
+    assert np.all(np.isfinite(g64)) and np.all(g64 > 0)
+    err = np.abs(g32.astype(np.float64) - g64) / g64 / cr.U
+    assert np.all(err <= bound), (err.max(), (err / bound).max())
+    assert (err / bound).max() > 0.02                           # the bound is of the error's order, not a blanket
+    print("gain bound in u: median %.1f, max %.1f; float32 restatement at most %.2f of it" % (np.median(bound), bound.max(), (err / bound).max()))
+
+
+def test_follower_restatement_on_a_hand_checked_vector():
+    """ta = 0.5, tr = 0.25, release threshold 0.5, nHold = 2: every value below is exact in float32 and was worked out by hand.
+       s     d      branch                               e      peak   hold
+       1     1      attack, e >= peak: re-arm            0.5    0.5    2
+       1     0.5    attack, re-arm                       0.75   0.75   2
+       0.25  -0.5   hold countdown                       0.75   0.75   1
+       0.25  -0.5   hold countdown                       0.75   0.75   0
+       0.25  -0.5   release, e > 0.5: tau release        0.625  0.625  0
+       0.125 -0.5   release, e > 0.5: tau release        0.5    0.5    0
+       0     -0.5   release, e = 0.5 not above: tau att  0.25   0.25   0
+       0.25  0      d = 0 is an attack; e >= peak        0.25   0.25   2
+       0     -0.25  hold countdown                       0.25   0.25   1
+       0.75  0.5    attack, re-arm during the countdown  0.5    0.5    2
+       0     -0.5   hold countdown                       0.5    0.5    1
+       0     -0.5   hold countdown                       0.5    0.5    0"""
+    x = np.array([[1, 1, 0.25, 0.25, 0.25, 0.125, 0, 0.25, 0, 0.75, 0, 0]], f32)
+    env = [0.5, 0.75, 0.75, 0.75, 0.625, 0.5, 0.25, 0.25, 0.25, 0.5, 0.5, 0.5]
+    peak = env
+    hold = [2, 2, 1, 0, 0, 0, 0, 2, 1, 2, 1, 0]
+    st = cr.fresh_state(1)
+    got, taken = cr.follow(x, st, 0.5, 0.25, 0.5, 2)
+    assert got.shape == (1, 12) and got[0].tolist() == env
+    assert taken == {"attack": 4, "rearm": 4, "hold": 5, "release_above": 2, "release_below": 1}
+    assert (st["e"][0], st["peak"][0], st["hold"][0]) == (0.5, 0.5, 0)
+    st = cr.fresh_state(1)                                      # sample by sample: the state after every one
+    for i in range(12):
+        e, _ = cr.follow(x[:, i:i + 1], st, 0.5, 0.25, 0.5, 2)
+        assert (e[0, 0], st["e"][0], st["peak"][0], st["hold"][0]) == (env[i], env[i], peak[i], hold[i]), i
+    # the product rounds before the sum: tau = d = 1 + 2^-12 gives tau d = 1 + 2^-11 + 2^-24, which float32 rounds to
+    # 1 + 2^-11; from e = -1 the sum is then 2^-11 exactly, where a fused multiply-add would keep 2^-11 + 2^-24
+    t = f32(1.0 + 2.0 ** -12)
+    st = {"e": np.array([-1.0], f32), "peak": np.array([-1.0], f32), "hold": np.zeros(1, np.uint32)}
+    e, _ = cr.follow(np.array([[f32(2.0 ** -12)]], f32), st, t, t, 0.0, 0)
+    assert e[0, 0] == f32(2.0 ** -11)
+
+
+PROBE = r'''
+#include <lsp-plug.in/dsp-units/dynamics/Compressor.h>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+using lsp::dspu::Compressor;
+
+struct names: public lsp::dspu::IStateDumper
+{
+    std::vector<std::string> seen, closes;
+    void begin_object(const char *n, const void *, size_t) override    { seen.push_back(n); }
+    void begin_array(const char *n, const void *, size_t) override     { seen.push_back(n); }
+    void end_object() override                                         { closes.push_back("end_object"); }
+    void end_array() override                                          { closes.push_back("end_array"); }
+    void write(const char *n, bool) override                           { seen.push_back(n); }
+    void write(const char *n, unsigned int) override                   { seen.push_back(n); }
+    void write(const char *n, float) override                          { seen.push_back(n); }
+    void writev(const char *n, const float *, size_t) override         { seen.push_back(n); }
+};
+
+struct probe: public Compressor
+{
+    static size_t knee_size()   { return sizeof(comp_t); }
+    float tau_attack() const    { return fTauAttack; }
+    unsigned hold_samples() const { return nHold; }
+    float start0() const        { return sComp.k[0].start; }
+};
+
+// set(a); update; set(a) again; set(b): modified() after each of the three sets
+#define SETTER(label, a, b) \
+    do { m->a; int s1 = m->modified(); m->update_settings(); int s0 = m->modified(); m->a; int s2 = m->modified(); m->b; \
+         printf("setter_%s %d %d %d %d\n", label, s1, s0, s2, int(m->modified())); m->update_settings(); } while (0)
+
+int main()
+{
+    // the public surface, by address
+    void (Compressor::*p1)(float *, float *, const float *, size_t) = &Compressor::process;
+    float (Compressor::*p2)(float *, float) = &Compressor::process;
+    void (Compressor::*c1)(float *, const float *, size_t) = &Compressor::curve;
+    float (Compressor::*c2)(float) = &Compressor::curve;
+    void (Compressor::*r1)(float *, const float *, size_t) = &Compressor::reduction;
+    float (Compressor::*r2)(float) = &Compressor::reduction;
+    void (Compressor::*pc)() = &Compressor::construct;
+    void (Compressor::*pd)() = &Compressor::destroy;
+    void (Compressor::*pu)() = &Compressor::update_settings;
+    void (Compressor::*ss)(size_t) = &Compressor::set_sample_rate;
+    void (Compressor::*sm)(size_t) = &Compressor::set_mode;
+    void (Compressor::*pv)(lsp::dspu::IStateDumper *) const = &Compressor::dump;
+    (void)p1; (void)p2; (void)c1; (void)c2; (void)r1; (void)r2; (void)pc; (void)pd; (void)pu; (void)ss; (void)sm; (void)pv;
+    lsp::dsp::compressor_x2_t x2; lsp::dsp::compressor_knee_t *kn = &x2.k[1];
+    kn->start = kn->end = kn->gain = kn->herm[2] = kn->tilt[1] = 0.0f;
+
+    printf("sizeof %zu %zu %zu\n", sizeof(Compressor), probe::knee_size(), sizeof(lsp::dsp::compressor_knee_t));
+    printf("modes %d %d %d\n", int(lsp::dspu::CM_DOWNWARD), int(lsp::dspu::CM_UPWARD), int(lsp::dspu::CM_BOOSTING));
+
+    // construct() on raw memory, no device involved
+    void *raw = malloc(sizeof(Compressor));
+    memset(raw, 0xa5, sizeof(Compressor));
+    probe *m = reinterpret_cast<probe *>(raw);
+    m->construct();
+    printf("fresh %d %g %g %g %g %g %g %g %g %zu %zu\n", int(m->modified()), m->attack_threshold(), m->release_threshold(),
+           m->boost_threshold(), m->attack(), m->release(), m->knee(), m->ratio(), m->hold(), m->sample_rate(), m->mode());
+
+    SETTER("sample_rate", set_sample_rate(48000), set_sample_rate(44100));
+    SETTER("mode", set_mode(lsp::dspu::CM_UPWARD), set_mode(lsp::dspu::CM_DOWNWARD));
+    SETTER("attack_threshold", set_attack_threshold(0.25f), set_attack_threshold(0.125f));
+    SETTER("release_threshold", set_release_threshold(0.25f), set_release_threshold(0.0625f));
+    SETTER("threshold", set_threshold(0.5f, 0.25f), set_threshold(0.5f, 0.125f));
+    SETTER("boost_threshold", set_boost_threshold(0.01f), set_boost_threshold(0.02f));
+    SETTER("timings", set_timings(10.0f, 100.0f), set_timings(10.0f, 50.0f));
+    SETTER("attack", set_attack(5.0f), set_attack(6.0f));
+    SETTER("release", set_release(70.0f), set_release(80.0f));
+    SETTER("knee", set_knee(0.5f), set_knee(0.25f));
+    SETTER("ratio", set_ratio(4.0f), set_ratio(8.0f));
+    SETTER("hold", set_hold(3.0f), set_hold(4.0f));
+    // the limits: knee to [0, 1], hold to >= 0
+    m->set_knee(1.0f); m->update_settings(); m->set_knee(7.0f);
+    printf("limits %d %g", int(m->modified()), m->knee());
+    m->set_hold(0.0f); m->update_settings(); m->set_hold(-2.0f);
+    printf(" %d %g\n", int(m->modified()), m->hold());
+
+    // update_settings() and the scalar curve / reduction are host arithmetic
+    m->set_sample_rate(48000); m->set_mode(lsp::dspu::CM_DOWNWARD); m->set_threshold(0.25f, 0.125f); m->set_timings(1.0f, 10.0f);
+    m->set_knee(0.5f); m->set_ratio(4.0f); m->set_hold(2.0f);
+    printf("reduction %.9g %.9g %.9g", m->reduction(0.01f), m->reduction(1.0f), m->reduction(-0.25f));
+    printf(" %d\n", int(m->modified()));
+    printf("curve %.9g %.9g %.9g\n", m->curve(0.01f), m->curve(1.0f), m->curve(-0.25f));
+    printf("computed %.9g %u %.9g\n", m->tau_attack(), m->hold_samples(), m->start0());
+
+    names n;
+    m->dump(&n);
+    printf("dump");
+    for (const std::string &s: n.seen)
+        printf(" %s", s.c_str());
+    printf("\ncloses");
+    for (const std::string &s: n.closes)
+        printf(" %s", s.c_str());
+    printf("\n");
+    m->destroy();
+    free(raw);
+    return 0;
+}
+'''
+
+
+def _probe(tmp_path):
+    src = os.path.join(str(tmp_path), "comp_probe.cpp")
+    exe = os.path.join(str(tmp_path), "comp_probe")
+    with open(src, "w") as f:
+        f.write(PROBE)
+    subprocess.check_call(["g++", "-std=c++11", "-O1", "-Wall", "-I" + os.path.join(PKG, "include"), "-I" + os.path.join(ROOT, "include"),
+                           src, "-o", exe, "-L" + PKG, "-lmi_dspu", "-Wl,-rpath," + PKG, "-Wl,-rpath,/opt/rocm/lib"])
+    out = subprocess.check_output([exe]).decode().splitlines()
+    return {l.split()[0]: l.split()[1:] for l in out}
+
+
+def test_mirror_header_layout_dump_order_and_setters(mi, tmp_path):
+    r = _probe(tmp_path)
+    # 12 floats, sComp (2 x 8 floats), four uint32_t and a bool: 48 + 64 + 16 + 1, padded to a multiple of 4
+    assert r["sizeof"] == ["132", "64", "32"]
+    assert r["modes"] == ["0", "1", "2"]
+    assert r["fresh"] == ["1", "0", "0", "0.00025119", "0", "0", "0", "1", "0", "0", "0"]
+    for name in ("sample_rate", "mode", "attack_threshold", "release_threshold", "threshold", "boost_threshold", "timings",
+                 "attack", "release", "knee", "ratio", "hold"):
+        # a new value raises bUpdate, update_settings() drops it, the same value again leaves it down, another one raises it
+        assert r["setter_" + name] == ["1", "0", "0", "1"], name
+    assert r["limits"] == ["0", "1", "0", "0"]
+    keys = json.load(open(os.path.join(ROOT, "tests", "golden", "compressor_dump_keys.json")))
+    assert r["dump"] == keys["keys"]
+    assert r["closes"] == keys["closes"]                        # the reference closes sComp with end_array
+    # the class computes what the C entry computes, and its scalar forms are the curve of those parameters
+    s = dict(sample_rate=48000, mode=cr.CM_DOWNWARD, attack_threshold=0.25, release_threshold=0.125, boost_threshold=0.02,
+             attack=1.0, release=10.0, hold=2.0, knee=0.5, ratio=4.0)
+    p = mi.CompressorBank.compute_params(**s)
+    assert r["reduction"][3] == "0"                             # reduction() ran update_settings()
+    assert [f32(v) for v in r["computed"]] == [f32(p["tau_attack"]), f32(p["hold"]), f32(p["k"][0]["start"])]
+    x = np.array([[0.01, 1.0, -0.25]], f32)
+    g64, bound = cr.gain64(x, [p])[0], cr.gain_bound(x, [p])[0]
+    red = np.array([float(v) for v in r["reduction"][:3]])
+    cur = np.array([float(v) for v in r["curve"]])
+    assert np.all(np.abs(red - g64) <= bound * cr.U * g64)
+    assert np.all(np.abs(cur - g64 * np.abs(x[0])) <= (bound + 1) * cr.U * g64 * np.abs(x[0]))
+    assert red[0] == 1.0 and 0.3 < red[1] < 0.4                  # 0.25 ^ 0.75 = 0.354 at 0 dB, ratio 4
+
+
+def test_mirror_header_declares_the_reference_names():
+    text = open(os.path.join(PKG, "include", "lsp-plug.in", "dsp-units", "dynamics", "Compressor.h")).read()
+    text = re.sub(r"//.*", "", text)
+    fields = ("fAttackThresh", "fReleaseThresh", "fBoostThresh", "fAttack", "fRelease", "fKnee", "fRatio", "fHold", "fEnvelope",
+              "fPeak", "fTauAttack", "fTauRelease", "sComp", "nHold", "nHoldCounter", "nSampleRate", "nMode", "bUpdate")
+    for name in fields + ("comp_t", "compressor_mode_t", "CM_DOWNWARD", "CM_UPWARD", "CM_BOOSTING", "construct", "destroy",
+                          "modified", "update_settings", "attack_threshold", "set_attack_threshold", "release_threshold",
+                          "set_release_threshold", "set_threshold", "boost_threshold", "set_boost_threshold", "set_timings",
+                          "attack", "set_attack", "release", "set_release", "sample_rate", "set_sample_rate", "knee", "set_knee",
+                          "ratio", "set_ratio", "set_mode", "mode", "hold", "set_hold", "process", "curve", "reduction", "dump"):
+        assert re.search(r"\b%s\b" % name, text), name
+    prot = text[text.index("protected:"):text.index("public:")]
+    pos = [prot.index(" " + n + ";") for n in fields]
+    assert pos == sorted(pos), "the protected fields are not in the reference's order"
+
+
+def test_mirror_exports_the_reference_symbols(mi):
+    out = subprocess.check_output(["nm", "-D", "--defined-only", mi.LIB_PATH]).decode()
+    for sym in ("_ZN3lsp4dspu10CompressorC1Ev", "_ZN3lsp4dspu10CompressorD1Ev", "_ZN3lsp4dspu10Compressor9constructEv",
+                "_ZN3lsp4dspu10Compressor7destroyEv", "_ZN3lsp4dspu10Compressor15update_settingsEv",
+                "_ZN3lsp4dspu10Compressor7processEPfS2_PKfm", "_ZN3lsp4dspu10Compressor7processEPff",
+                "_ZN3lsp4dspu10Compressor5curveEPfPKfm", "_ZN3lsp4dspu10Compressor5curveEf",
+                "_ZN3lsp4dspu10Compressor9reductionEPfPKfm", "_ZN3lsp4dspu10Compressor9reductionEf",
+                "_ZN3lsp4dspu10Compressor13set_thresholdEff", "_ZN3lsp4dspu10Compressor11set_timingsEff",
+                "_ZN3lsp4dspu10Compressor15set_sample_rateEm", "_ZN3lsp4dspu10Compressor8set_modeEm",
+                "_ZN3lsp4dspu10Compressor8set_kneeEf", "_ZN3lsp4dspu10Compressor9set_ratioEf", "_ZN3lsp4dspu10Compressor8set_holdEf",
+                "_ZNK3lsp4dspu10Compressor4dumpEPNS0_12IStateDumperE"):
+        assert re.search(r" T %s$" % re.escape(sym), out, re.M), sym
+
+
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
+def test_follower_keeps_separate_multiplies_and_adds(tmp_path):
+    """The bits of the restatement need tau * d and e + ... rounded on their own: no fused multiply-add in any form in the
+    follower's body, under the Makefile's -ffp-contract=on."""
+    out = os.path.join(str(tmp_path), "compressor.s")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=on", "-w",
+                           "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-I" + os.path.join(PKG, "include"),
+                           "-S", "--offload-device-only", os.path.join(CSRC, "compressor.hip"), "-o", out])
+    bodies, cur = {}, None
+    for l in open(out).read().split("\n"):
+        m = re.match(r"^(_Z\w+):", l)
+        if m:
+            cur = m.group(1)
+            bodies[cur] = []
+        elif cur and (l.startswith(".Lfunc_end") or ".amdhsa_kernel" in l):
+            cur = None
+        elif cur:
+            bodies[cur].append(l.strip())
+    names = [n for n in bodies if "compressor_follow_tile" in n]
+    assert len(names) == 1, sorted(bodies)
+    ops = [l.split()[0] for l in bodies[names[0]] if l and not l.startswith((";", "."))]
+    assert len(ops) > 20
+    fused = [o for o in ops if o.startswith(("v_fma", "v_fmac", "v_mad_f", "v_mac_f"))]
+    assert not fused, fused
