@@ -960,6 +960,72 @@ int mi_compressor_bank_process_apply(mi_compressor_bank_t *bank, float *dst, con
 int mi_compressor_bank_curve(mi_compressor_bank_t *bank, float *out, const float *in, size_t dots, size_t out_stride,
                              size_t in_stride, void *stream);
 
+/* ---- sidechain bank (source selection, pre-amplification and the peak / RMS / low-pass / uniform detectors) ------------- */
+/*
+ * mi_sidechain_bank: `channels` x lsp::dspu::Sidechain (util/Sidechain.h:59-205, src/main/util/Sidechain.cpp), every channel
+ * with settings of its own: what produces the signal a compressor bank takes.  process() is the reference's block overload
+ * (:439-554): a source out of one or two inputs (:183-333), its magnitude times the gain, pushed into the channel's ring of
+ * capacity max(millis_to_samples(sr, max_reactivity), 1) + 0x200, and one of four detectors over it; every 0x2000 samples
+ * fRmsValue is formed anew from the ring (refresh_processing, :144-181, with its two partial sums where the window wraps).
+ * out, fRmsValue, nRefresh and the ring position are the reference's bit for bit in float32 (each product and each sum rounds
+ * once, the square root is correctly rounded); the sums of the refresh are taken serially, oldest sample first (DESIGN.md
+ * section 4).  Ring, fRmsValue, nRefresh and the ring position live on the device; the bank has no host positions, so its
+ * process calls can be captured into a graph and replayed.  Inputs are finite: NaN is out of scope.  Subnormals are kept.
+ * Rows of the sample buffers: [channels][stride].
+ */
+typedef struct mi_sidechain_bank mi_sidechain_bank_t;
+enum mi_sidechain_source { MI_SCS_MIDDLE = 0, MI_SCS_SIDE = 1, MI_SCS_LEFT = 2, MI_SCS_RIGHT = 3, MI_SCS_AMIN = 4, MI_SCS_AMAX = 5 };
+enum mi_sidechain_mode { MI_SCM_PEAK = 0, MI_SCM_RMS = 1, MI_SCM_LPF = 2, MI_SCM_UNIFORM = 3 };
+enum mi_sidechain_stereo_mode { MI_SCSM_STEREO = 0, MI_SCSM_MIDSIDE = 1 };
+enum mi_sidechain_flags { MI_SCF_MIDSIDE = 1, MI_SCF_UPDATE = 2, MI_SCF_CLEAR = 4 };        /* Sidechain::flags_t */
+/* nReactivity, fTau, 1.0f / nReactivity and the ring's capacity as update_settings() and set_sample_rate() compute them;
+ * nMode, nSource, nFlags and fGain as set */
+typedef struct { uint32_t reactivity; float tau, interval; uint32_t capacity, mode, source, flags; float gain; } mi_sidechain_params_t;
+/* The arithmetic of update_settings() (:119-131) and of set_sample_rate() (:88-93) in host float32: reactivity, tau, interval
+ * and capacity; mode, source and flags 0, gain 1.  A reactivity outside [0, max_reactivity] is MI_EINVAL.  No device needed. */
+int mi_sidechain_compute_params(uint32_t sample_rate, float max_reactivity, float reactivity, mi_sidechain_params_t *params);
+/* init(inputs, max_reactivity), :67-86, of every channel: MIDDLE, RMS, gain 1, sample rate and reactivity 0, an update and
+ * a clear pending.  inputs: 1 or 2 */
+int mi_sidechain_bank_create(mi_sidechain_bank_t **bank, uint32_t channels, uint32_t inputs, float max_reactivity_ms);
+int mi_sidechain_bank_destroy(mi_sidechain_bank_t *bank);
+/* The setters of one channel with the reference's rules (:88-117, Sidechain.h:146-175): set_sample_rate re-makes the ring
+ * (zeroed, position 0) and raises UPDATE and CLEAR; set_reactivity ignores an unchanged value and values outside
+ * [0, max_reactivity] and raises UPDATE (which forces a refresh at the next sample); set_stereo_mode raises CLEAR when the
+ * mode changes; set_mode zeroes fRmsValue WITHOUT a refresh when the mode changes; set_source and set_gain just set.
+ * Nothing reaches the device before update_settings().  A source above AMAX, a mode above UNIFORM and a stereo mode above
+ * MIDSIDE are MI_EINVAL. */
+int mi_sidechain_bank_set_sample_rate(mi_sidechain_bank_t *bank, uint32_t channel, uint32_t sample_rate);
+int mi_sidechain_bank_set_reactivity(mi_sidechain_bank_t *bank, uint32_t channel, float reactivity);
+int mi_sidechain_bank_set_stereo_mode(mi_sidechain_bank_t *bank, uint32_t channel, uint32_t mode);
+int mi_sidechain_bank_set_source(mi_sidechain_bank_t *bank, uint32_t channel, uint32_t source);
+int mi_sidechain_bank_set_mode(mi_sidechain_bank_t *bank, uint32_t channel, uint32_t mode);
+int mi_sidechain_bank_set_gain(mi_sidechain_bank_t *bank, uint32_t channel, float gain);
+/* clear(), :114-117: raises CLEAR of one channel, or of every channel (channel = UINT32_MAX).  At update_settings() it zeroes
+ * fRmsValue, nRefresh and the ring's samples; the ring position stays, as in the reference. */
+int mi_sidechain_bank_clear(mi_sidechain_bank_t *bank, uint32_t channel);
+/* update_settings(), :119-142, of every channel with something pending: the changed stretch of the parameter table and the
+ * changed state go to the device (and the call waits for them); rings grow, keeping the other channels' samples, when a
+ * sample rate asks for more.  The process entries run it first.  On a stream being captured pending work is refused
+ * (MI_ESTATE): call it before the capture. */
+int mi_sidechain_bank_update_settings(mi_sidechain_bank_t *bank, void *stream);
+/* The channel's parameters as the last update_settings() left them, flags with what is pending now (HOST memory); fRmsValue,
+ * nRefresh and the ring position (RawRingBuffer::position()) as the work enqueued on `stream` leaves them (HOST memory, each
+ * may be NULL; waits for the stream) */
+int mi_sidechain_bank_get_params(const mi_sidechain_bank_t *bank, uint32_t channel, mi_sidechain_params_t *params);
+int mi_sidechain_bank_get_state(mi_sidechain_bank_t *bank, uint32_t channel, float *rms_value, uint32_t *refresh, uint32_t *position,
+                                void *stream);
+/* process(out, in, samples), :439-554.  in1: the second input's rows, NULL for a bank of one input; in0 == NULL: silence, which
+ * still runs through gain, ring and detector.  out may be in0 or in1 (same stride). */
+int mi_sidechain_bank_process(mi_sidechain_bank_t *bank, float *out, const float *in0, const float *in1, size_t count,
+                              size_t out_stride, size_t in0_stride, size_t in1_stride, void *stream);
+/* The two halves of process() for a caller with a pre-equalizer between them: premix() writes the SIGNED selected source
+ * (psmin3 / psmax3 where process() takes pamin3 / pamax3), stateless; process_premixed() runs magnitude, gain, ring and detector
+ * on such rows.  process() equals premix() followed by process_premixed() bit for bit.  out may be an input (same stride). */
+int mi_sidechain_bank_premix(mi_sidechain_bank_t *bank, float *out, const float *in0, const float *in1, size_t count,
+                             size_t out_stride, size_t in0_stride, size_t in1_stride, void *stream);
+int mi_sidechain_bank_process_premixed(mi_sidechain_bank_t *bank, float *out, const float *in, size_t count, size_t out_stride,
+                                       size_t in_stride, void *stream);
+
 /*
  * mi_splitter_bank: lsp::dspu::SpectralSplitter for `channels` channels sharing the settings
  * (util/SpectralSplitter.h:62-250, src/main/util/SpectralSplitter.cpp:62-361) -- the engine of lsp::dspu::FFTCrossover.

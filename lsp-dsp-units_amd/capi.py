@@ -52,6 +52,12 @@ class CompressorSettings(ctypes.Structure):
                                        "hold", "knee", "ratio")]
 
 
+class SidechainParams(ctypes.Structure):
+    """mi_sidechain_params_t: what Sidechain::update_settings and set_sample_rate compute, and the settings beside them."""
+    _fields_ = [("reactivity", c_uint32), ("tau", c_float), ("interval", c_float), ("capacity", c_uint32), ("mode", c_uint32),
+                ("source", c_uint32), ("flags", c_uint32), ("gain", c_float)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/mi_dspu.h must be listed here
 # (tests/test_abi.py parses the header and checks both directions).
 PROTOTYPES = {
@@ -245,6 +251,22 @@ PROTOTYPES = {
     "mi_compressor_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_compressor_bank_process_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_compressor_bank_curve": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_sidechain_compute_params": (c_int, [c_uint32, c_float, c_float, POINTER(SidechainParams)]),
+    "mi_sidechain_bank_create": (c_int, [POINTER(c_void_p), c_uint32, c_uint32, c_float]),
+    "mi_sidechain_bank_destroy": (c_int, [c_void_p]),
+    "mi_sidechain_bank_set_sample_rate": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_sidechain_bank_set_reactivity": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_sidechain_bank_set_stereo_mode": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_sidechain_bank_set_source": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_sidechain_bank_set_mode": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_sidechain_bank_set_gain": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_sidechain_bank_clear": (c_int, [c_void_p, c_uint32]),
+    "mi_sidechain_bank_update_settings": (c_int, [c_void_p, c_void_p]),
+    "mi_sidechain_bank_get_params": (c_int, [c_void_p, c_uint32, POINTER(SidechainParams)]),
+    "mi_sidechain_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(c_float), POINTER(c_uint32), POINTER(c_uint32), c_void_p]),
+    "mi_sidechain_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_sidechain_bank_premix": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_sidechain_bank_process_premixed": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_splitter_bank_create": (c_int, [POINTER(c_void_p), c_uint32, c_uint32, c_uint32]),
     "mi_splitter_bank_destroy": (c_int, [c_void_p]),
     "mi_splitter_bank_set_rank": (c_int, [c_void_p, c_uint32]),

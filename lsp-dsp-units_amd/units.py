@@ -922,6 +922,109 @@ class CompressorBank:
             pass
 
 
+def _sidechain_dict(p):
+    return {"reactivity": p.reactivity, "tau": np.float32(p.tau), "interval": np.float32(p.interval), "capacity": p.capacity,
+            "mode": p.mode, "source": p.source, "flags": p.flags, "gain": np.float32(p.gain)}
+
+
+class SidechainBank:
+    """`channels` x lsp::dspu::Sidechain (mi_sidechain_bank_*): source selection, pre-amplification and the peak / RMS /
+    low-pass / uniform detectors, every channel with settings of its own."""
+    SCS_MIDDLE, SCS_SIDE, SCS_LEFT, SCS_RIGHT, SCS_AMIN, SCS_AMAX = range(6)
+    SCM_PEAK, SCM_RMS, SCM_LPF, SCM_UNIFORM = range(4)
+    SCSM_STEREO, SCSM_MIDSIDE = range(2)
+    SCF_MIDSIDE, SCF_UPDATE, SCF_CLEAR = 1, 2, 4
+    ALL = 0xFFFFFFFF
+
+    def __init__(self, channels, inputs=1, max_reactivity_ms=50.0):
+        h = c_void_p()
+        check(lib.mi_sidechain_bank_create(byref(h), channels, inputs, float(max_reactivity_ms)))
+        self.handle, self.channels, self.inputs = h, channels, inputs
+
+    @staticmethod
+    def compute_params(sample_rate, max_reactivity, reactivity):
+        """update_settings() and the ring's capacity of one sidechain on the host (mi_sidechain_compute_params): no device needed."""
+        from .capi import SidechainParams
+        p = SidechainParams()
+        check(lib.mi_sidechain_compute_params(sample_rate, float(max_reactivity), float(reactivity), byref(p)))
+        return _sidechain_dict(p)
+
+    def set_sample_rate(self, channel, sr):
+        check(lib.mi_sidechain_bank_set_sample_rate(self.handle, channel, sr))
+
+    def set_reactivity(self, channel, reactivity):
+        check(lib.mi_sidechain_bank_set_reactivity(self.handle, channel, float(reactivity)))
+
+    def set_stereo_mode(self, channel, mode):
+        check(lib.mi_sidechain_bank_set_stereo_mode(self.handle, channel, mode))
+
+    def set_source(self, channel, source):
+        check(lib.mi_sidechain_bank_set_source(self.handle, channel, source))
+
+    def set_mode(self, channel, mode):
+        check(lib.mi_sidechain_bank_set_mode(self.handle, channel, mode))
+
+    def set_gain(self, channel, gain):
+        check(lib.mi_sidechain_bank_set_gain(self.handle, channel, float(gain)))
+
+    def configure(self, channel, sample_rate, reactivity, mode, source=0, stereo_mode=0, gain=1.0):
+        """Every setter of one channel."""
+        self.set_sample_rate(channel, sample_rate)
+        self.set_reactivity(channel, reactivity)
+        self.set_mode(channel, mode)
+        self.set_source(channel, source)
+        self.set_stereo_mode(channel, stereo_mode)
+        self.set_gain(channel, gain)
+
+    def clear(self, channel=ALL):
+        check(lib.mi_sidechain_bank_clear(self.handle, channel))
+
+    def update_settings(self, stream=None):
+        check(lib.mi_sidechain_bank_update_settings(self.handle, _stream(stream)))
+
+    def get_params(self, channel):
+        from .capi import SidechainParams
+        p = SidechainParams()
+        check(lib.mi_sidechain_bank_get_params(self.handle, channel, byref(p)))
+        return _sidechain_dict(p)
+
+    def get_state(self, channel, stream=None):
+        """(fRmsValue as numpy float32, nRefresh, the ring position) of the channel."""
+        v, r, h = c_float(), c_uint32(), c_uint32()
+        check(lib.mi_sidechain_bank_get_state(self.handle, channel, byref(v), byref(r), byref(h), _stream(stream)))
+        return np.float32(v.value), r.value, h.value
+
+    def process(self, out, in0, in1, count, out_stride=None, in0_stride=None, in1_stride=None, stream=None):
+        """process(out, in, samples): in1 None for one input, in0 None for silence; out may be an input (in place)."""
+        check(lib.mi_sidechain_bank_process(self.handle, _ptr(out), None if in0 is None else _ptr(in0), None if in1 is None else _ptr(in1),
+                                            count, count if out_stride is None else out_stride,
+                                            count if in0_stride is None else in0_stride,
+                                            count if in1_stride is None else in1_stride, _stream(stream)))
+
+    def premix(self, out, in0, in1, count, out_stride=None, in0_stride=None, in1_stride=None, stream=None):
+        """The signed selected source, before magnitude and gain."""
+        check(lib.mi_sidechain_bank_premix(self.handle, _ptr(out), None if in0 is None else _ptr(in0), None if in1 is None else _ptr(in1),
+                                           count, count if out_stride is None else out_stride,
+                                           count if in0_stride is None else in0_stride,
+                                           count if in1_stride is None else in1_stride, _stream(stream)))
+
+    def process_premixed(self, out, inp, count, out_stride=None, in_stride=None, stream=None):
+        """Magnitude, gain, ring and detector on rows that premix() wrote."""
+        check(lib.mi_sidechain_bank_process_premixed(self.handle, _ptr(out), _ptr(inp), count, count if out_stride is None else out_stride,
+                                                     count if in_stride is None else in_stride, _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            lib.mi_sidechain_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class LoudnessBank:
     """`meters` x lsp::dspu::LoudnessMeter(channels) sharing one configuration (mi_loudness_bank_*)."""
     WEIGHT_NONE, WEIGHT_A, WEIGHT_B, WEIGHT_C, WEIGHT_D, WEIGHT_K = range(6)
