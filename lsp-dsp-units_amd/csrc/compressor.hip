@@ -5,17 +5,17 @@
 // The follower is a serial recurrence over (fEnvelope, fPeak, nHoldCounter) whose branch depends on the running value: one
 // lane per channel, the state in registers for the whole call and in a device array between calls (no host positions, so
 // calls can be captured into a graph and replayed).  The gain curve is element-wise.  compressor_kernel runs both in one
-// launch: a workgroup owns GROUP channels and walks their rows in tiles of TILE samples through LDS, two buffers:
-//     wave 0           the follower over tile k, lane c on row c, the envelope written over the input in LDS
-//     waves 1 .. GROUP one row each: the gain of tile k - 1 from its envelope and the stores (16 bytes per lane where the
-//                      rows allow it), then the load of tile k + 1 into the buffer just emptied
-// one barrier per tile.  A tile is in LDS before anything of it is stored and tile k + 1 is loaded after tile k - 1 was
-// stored, so gain, env and dst may each be the input row.  The follower's tau * d and e + ... round once each (no fused
-// multiply-add): compressor_follow_tile is a function of its own so that its instructions can be looked at
-// (tests/test_compressor_host.py), and the envelope matches tests/compressor_ref.py bit for bit.
+// launch on the tile walk of tile_chain_device.h: the chain is the follower, the envelope written over the input in LDS;
+// prepare is the load of the input; emit is the gain from the envelope and the stores, so gain, env and dst may each be
+// the input row.  The follower's tau * d and e + ... round once each (no fused multiply-add): compressor_follow_tile is a
+// function of its own so that its instructions can be looked at (tests/test_compressor_host.py), and the envelope matches
+// tests/compressor_ref.py bit for bit.
 //
 // Inputs are finite: NaN is out of scope.  Subnormal envelopes are kept (the float32 denormal mode is on).
 #include "compressor_bank.h"
+#include "tile_chain_device.h"
+
+#include <lsp-plug.in/dsp-units/units.h>
 
 #include <cmath>
 #include <new>
@@ -25,24 +25,17 @@
 
 namespace
 {
-    constexpr int GROUP   = 4;                  // channels of a workgroup: 1024 channels are 256 workgroups, one per CU
-    constexpr int TILE    = 256;                // samples of a row per trip through LDS
-    constexpr int ROW     = TILE + 4;           // floats between rows in LDS: lane c's 16-byte reads start at bank 4c
-    constexpr int HELPERS = GROUP * 64;         // one wave per row for loads, gain and stores
-    constexpr int BLOCK   = 64 + HELPERS;
-    constexpr int BATCH   = 8;                  // samples the follower reads ahead of its chain
+    using namespace mi_tile_chain;
+    using lsp::dspu::millis_to_samples;
+
     constexpr int CURVE_BLOCK = 256;
 
     enum { VEC_IN = 1, VEC_GAIN = 2, VEC_ENV = 4, VEC_AUDIO = 8 };
 
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) float lds_float;
-    typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
-
     struct follow_state { float e, peak; uint32_t hold; };
     struct device_state { float e, peak; uint32_t hold, pad; };     // [channels] between calls
 
-    // Compressor.cpp:231-256 over samples [0, n) of one row in LDS, in place: row[i] becomes the envelope
+    // Compressor.cpp:231-256, one sample
     __device__ __forceinline__ void follow_step(float s, float &e, float &peak, uint32_t &hold, float ta, float tr, float rt,
                                                 uint32_t nhold)
     {
@@ -57,35 +50,13 @@ namespace
         hold = held ? hold - 1 : rearm ? nhold : hold;
     }
 
+    // ... over samples [0, n) of one row in LDS, in place: row[i] becomes the envelope
     __device__ __noinline__ follow_state compressor_follow_tile(lds_float *row, uint32_t n, follow_state s, float ta, float tr,
                                                                 float rt, uint32_t nhold)
     {
         float e = s.e, peak = s.peak;
-        uint32_t hold = s.hold, i = 0;
-        if (n >= BATCH)
-        {
-            f32x4 a = *reinterpret_cast<lds_f32x4 *>(row), b = *reinterpret_cast<lds_f32x4 *>(row + 4);
-            for (; i + BATCH <= n; i += BATCH)
-            {
-                float v[BATCH] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };
-                const uint32_t next = (i + 2 * BATCH <= n) ? i + BATCH : i;    // the next batch, before this one's chain
-                a = *reinterpret_cast<lds_f32x4 *>(row + next);
-                b = *reinterpret_cast<lds_f32x4 *>(row + next + 4);
-                #pragma unroll
-                for (int j = 0; j < BATCH; ++j)
-                {
-                    follow_step(v[j], e, peak, hold, ta, tr, rt, nhold);
-                    v[j] = e;
-                }
-                *reinterpret_cast<lds_f32x4 *>(row + i) = f32x4{ v[0], v[1], v[2], v[3] };
-                *reinterpret_cast<lds_f32x4 *>(row + i + 4) = f32x4{ v[4], v[5], v[6], v[7] };
-            }
-        }
-        for (; i < n; ++i)
-        {
-            follow_step(row[i], e, peak, hold, ta, tr, rt, nhold);
-            row[i] = e;
-        }
+        uint32_t hold = s.hold;
+        chain_batches(row, 0, n, [&](float v) { follow_step(v, e, peak, hold, ta, tr, rt, nhold); return e; });
         return follow_state{ e, peak, hold };
     }
 
@@ -115,27 +86,21 @@ namespace
                                                                uint32_t vec)
     {
         __shared__ __attribute__((aligned(16))) float tile[2][GROUP][ROW];
-        const int tid = threadIdx.x, lane = tid & 63;
-        const bool follower = tid < 64;
-        const uint32_t ch0 = blockIdx.x * GROUP;
-        const uint32_t tiles = (count + TILE - 1) / TILE;
+        const role me = my_role(channels);
+        const uint32_t r = me.r, ch = me.ch, c = me.c;
 
-        // the follower's lane: its channel's state and taus; a helper: its row (one per wave) and its four samples of a tile
-        const uint32_t r = follower ? uint32_t(lane) : uint32_t(__builtin_amdgcn_readfirstlane((tid >> 6) - 1));
-        const uint32_t ch = ch0 + r;
-        const bool valid = r < uint32_t(GROUP) && ch < channels;
-        const uint32_t c = uint32_t(lane) * 4;
+        // the follower's lane: its channel's state and taus; a helper: its row's knees
         follow_state fs = { 0.0f, 0.0f, 0 };
         float ta = 0.0f, tr = 0.0f, rt = 0.0f;
         uint32_t nhold = 0;
         mi_compressor_knee_t k0 = {}, k1 = {};
-        if (valid && follower)
+        if (me.valid && me.chain)
         {
             const device_state s = state[ch];
             fs = follow_state{ s.e, s.peak, s.hold };
             ta = params[ch].tau_attack, tr = params[ch].tau_release, rt = params[ch].release_threshold, nhold = params[ch].hold;
         }
-        else if (valid)
+        else if (me.valid)
             k0 = params[ch].k[0], k1 = params[ch].k[1];
         const float *xs = in + size_t(ch) * in_stride;
         const float *as = (audio != nullptr) ? audio + size_t(ch) * audio_stride : nullptr;
@@ -144,96 +109,57 @@ namespace
 
         auto load_tile = [&](uint32_t k)
         {
-            const uint32_t t0 = k * TILE, n = (count - t0 < uint32_t(TILE)) ? count - t0 : uint32_t(TILE);
+            const extent t = tile_extent(count, k);
             float *l = &tile[k & 1][r][c];
-            if ((vec & VEC_IN) && c + 4 <= n)
-                *reinterpret_cast<float4 *>(l) = *reinterpret_cast<const float4 *>(xs + t0 + c);
+            if ((vec & VEC_IN) && c + 4 <= t.n)
+                *reinterpret_cast<float4 *>(l) = *reinterpret_cast<const float4 *>(xs + t.t0 + c);
             else
             {
                 #pragma unroll
                 for (uint32_t j = 0; j < 4; ++j)
-                    if (c + j < n)
-                        l[j] = xs[t0 + c + j];
+                    if (c + j < t.n)
+                        l[j] = xs[t.t0 + c + j];
             }
         };
         auto emit_tile = [&](uint32_t k)
         {
-            const uint32_t t0 = k * TILE, n = (count - t0 < uint32_t(TILE)) ? count - t0 : uint32_t(TILE);
-            if (c >= n)
+            const extent t = tile_extent(count, k);
+            if (c >= t.n)
                 return;
             const float4 e4 = *reinterpret_cast<const float4 *>(&tile[k & 1][r][c]);
             const float e[4] = { e4.x, e4.y, e4.z, e4.w };
-            const bool whole = c + 4 <= n;
             float g[4];
             #pragma unroll
             for (uint32_t j = 0; j < 4; ++j)
-                g[j] = (c + j < n) ? x2_gain(e[j], k0, k1) : 0.0f;
+                g[j] = (c + j < t.n) ? x2_gain(e[j], k0, k1) : 0.0f;
             if (as != nullptr)
             {
                 float a[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-                if ((vec & VEC_AUDIO) && whole)
+                if ((vec & VEC_AUDIO) && c + 4 <= t.n)
                 {
-                    const float4 a4 = *reinterpret_cast<const float4 *>(as + t0 + c);
+                    const float4 a4 = *reinterpret_cast<const float4 *>(as + t.t0 + c);
                     a[0] = a4.x, a[1] = a4.y, a[2] = a4.z, a[3] = a4.w;
                 }
                 else
                 {
                     #pragma unroll
                     for (uint32_t j = 0; j < 4; ++j)
-                        if (c + j < n)
-                            a[j] = as[t0 + c + j];
+                        if (c + j < t.n)
+                            a[j] = as[t.t0 + c + j];
                 }
                 #pragma unroll
                 for (uint32_t j = 0; j < 4; ++j)
                     g[j] = a[j] * g[j];
             }
-            if ((vec & VEC_GAIN) && whole)
-                *reinterpret_cast<float4 *>(gs + t0 + c) = make_float4(g[0], g[1], g[2], g[3]);
-            else
-            {
-                #pragma unroll
-                for (uint32_t j = 0; j < 4; ++j)
-                    if (c + j < n)
-                        gs[t0 + c + j] = g[j];
-            }
-            if (es == nullptr)
-                return;
-            if ((vec & VEC_ENV) && whole)
-                *reinterpret_cast<float4 *>(es + t0 + c) = e4;
-            else
-            {
-                #pragma unroll
-                for (uint32_t j = 0; j < 4; ++j)
-                    if (c + j < n)
-                        es[t0 + c + j] = e[j];
-            }
+            store_quad(gs + t.t0 + c, g, vec & VEC_GAIN, c, t.n);
+            if (es != nullptr)
+                store_quad(es + t.t0 + c, e, vec & VEC_ENV, c, t.n);
         };
 
-        if (valid && !follower)
-            load_tile(0);
-        __syncthreads();
-        for (uint32_t k = 0; k < tiles; ++k)
-        {
-            if (follower)
-            {
-                if (valid)
-                {
-                    const uint32_t t0 = k * TILE, n = (count - t0 < uint32_t(TILE)) ? count - t0 : uint32_t(TILE);
-                    fs = compressor_follow_tile((lds_float *)&tile[k & 1][r][0], n, fs, ta, tr, rt, nhold);
-                }
-            }
-            else if (valid)
-            {
-                if (k > 0)
-                    emit_tile(k - 1);
-                if (k + 1 < tiles)
-                    load_tile(k + 1);
-            }
-            __syncthreads();
-        }
-        if (valid && !follower)
-            emit_tile(tiles - 1);
-        if (valid && follower)
+        MI_TILE_CHAIN_WALK(me, count, k, load_tile(k),
+                           fs = compressor_follow_tile((lds_float *)&tile[k & 1][r][0], tile_extent(count, k).n, fs, ta, tr, rt, nhold),
+                           emit_tile(k));
+        if (me.valid && me.chain)
             state[ch] = device_state{ fs.e, fs.peak, fs.hold, 0 };
     }
 
@@ -257,8 +183,6 @@ namespace
         p[1] = k0 - 2.0f * p[0] * x0;
         p[2] = y0 - (p[0] * x0 + p[1]) * x0;
     }
-
-    inline float millis_to_samples(float sr, float time) { return (time * 0.001f) * sr; }       // units.h:116-119
 
     void knee(mi_compressor_knee_t &k, float start, float end, float gain, float tilt0, float tilt1)
     {
@@ -337,20 +261,6 @@ namespace
         p.k[0].gain = p.k[1].gain = 1.0f;
         return p;
     }
-
-    bool aligned16(const void *p, size_t stride, uint32_t channels)
-    {
-        return p != nullptr && (reinterpret_cast<uintptr_t>(p) & 15u) == 0 && (channels == 1 || (stride & 3u) == 0);
-    }
-
-    int capturing(hipStream_t st, bool *yes)
-    {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (st != nullptr)
-            MI_HIP_CHECK(hipStreamIsCapturing(st, &cs));
-        *yes = cs != hipStreamCaptureStatusNone;
-        return MI_OK;
-    }
 } // namespace
 
 struct mi_compressor_bank
@@ -359,21 +269,13 @@ struct mi_compressor_bank
     std::vector<mi_compressor_settings_t>   cfg;            // the setters' values
     std::vector<uint8_t>                    update;         // bUpdate of every channel
     std::vector<mi_compressor_params_t>     params;         // what update_settings computed
-    uint32_t                                up_lo = 0, up_hi = 0;   // channels [up_lo, up_hi) differ from the device table
+    mi::dirty_range                         up;             // where params differs from the device table
     mi_compressor_params_t                 *d_params = nullptr;     // [channels]
     device_state                           *d_state = nullptr;      // [channels]
 };
 
 namespace
 {
-    void touch(mi_compressor_bank *b, uint32_t ch)
-    {
-        if (b->up_lo == b->up_hi)
-            b->up_lo = ch, b->up_hi = ch + 1;
-        else
-            b->up_lo = (ch < b->up_lo) ? ch : b->up_lo, b->up_hi = (ch + 1 > b->up_hi) ? ch + 1 : b->up_hi;
-    }
-
     // update_settings of every channel whose bUpdate is set; the changed stretch of the table goes to the device
     int comp_update(mi_compressor_bank *b, hipStream_t st)
     {
@@ -383,27 +285,16 @@ namespace
                 continue;
             compute_params(b->cfg[ch], b->params[ch]);
             b->update[ch] = 0;
-            touch(b, ch);
+            b->up.touch(ch);
         }
-        if (b->up_lo == b->up_hi)
-            return MI_OK;
-        bool cap = false;
-        const int r = capturing(st, &cap);
-        if (r != MI_OK)
-            return r;
-        MI_REQUIRE(!cap, MI_ESTATE, "mi_compressor_bank: changed settings are sent to the device; call update_settings() before capturing");
-        MI_HIP_CHECK(hipMemcpyAsync(b->d_params + b->up_lo, b->params.data() + b->up_lo,
-                                    size_t(b->up_hi - b->up_lo) * sizeof(mi_compressor_params_t), hipMemcpyHostToDevice, st));
-        MI_HIP_CHECK(hipStreamSynchronize(st));                 // the host table may change again after this returns
-        b->up_lo = b->up_hi = 0;
-        return MI_OK;
+        return mi::upload_dirty("mi_compressor_bank", b->d_params, b->params.data(), b->up, st);
     }
 
     int comp_launch(mi_compressor_bank *b, float *gain, float *env, const float *in, const float *audio, size_t count,
                     size_t gain_stride, size_t env_stride, size_t in_stride, size_t audio_stride, hipStream_t st)
     {
-        const uint32_t vec = (aligned16(in, in_stride, b->channels) ? VEC_IN : 0) | (aligned16(gain, gain_stride, b->channels) ? VEC_GAIN : 0) |
-                             (aligned16(env, env_stride, b->channels) ? VEC_ENV : 0) | (aligned16(audio, audio_stride, b->channels) ? VEC_AUDIO : 0);
+        const uint32_t vec = (mi::aligned16(in, in_stride, b->channels) ? VEC_IN : 0) | (mi::aligned16(gain, gain_stride, b->channels) ? VEC_GAIN : 0) |
+                             (mi::aligned16(env, env_stride, b->channels) ? VEC_ENV : 0) | (mi::aligned16(audio, audio_stride, b->channels) ? VEC_AUDIO : 0);
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         mi::take_profile_events(&ev0, &ev1);
         MI_LAUNCH(compressor_kernel, dim3((b->channels + GROUP - 1) / GROUP), dim3(BLOCK), 0, st, ev0, ev1, gain, env, in, audio,
@@ -422,17 +313,14 @@ namespace mi
             return MI_OK;
         b->params[channel] = *p;
         b->update[channel] = 0;
-        touch(b, channel);
+        b->up.touch(channel);
         return MI_OK;
     }
 
     int compressor_bank_set_state(mi_compressor_bank_t *b, uint32_t channel, float envelope, float peak, uint32_t hold, hipStream_t st)
     {
         MI_REQUIRE(b != nullptr && channel < b->channels, MI_EINVAL, "compressor_bank_set_state: bad argument");
-        const device_state s = { envelope, peak, hold, 0 };
-        MI_HIP_CHECK(hipMemcpyAsync(b->d_state + channel, &s, sizeof(s), hipMemcpyHostToDevice, st));
-        MI_HIP_CHECK(hipStreamSynchronize(st));                 // `s` is gone after this returns
-        return MI_OK;
+        return mi::write_state(b->d_state + channel, device_state{ envelope, peak, hold, 0 }, st);
     }
 }
 
@@ -480,14 +368,9 @@ int mi_compressor_bank_destroy(mi_compressor_bank_t *b)
     return MI_OK;
 }
 
-#define MI_COMP_SETTER(name) \
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_compressor_bank_" name ": NULL bank"); \
-    MI_REQUIRE(channel < b->channels, MI_EINVAL, "mi_compressor_bank_" name ": channel %u out of range", channel); \
-    mi_compressor_settings_t &c = b->cfg[channel]
-
 int mi_compressor_bank_set_sample_rate(mi_compressor_bank_t *b, uint32_t channel, uint32_t sample_rate)    // :420-426
 {
-    MI_COMP_SETTER("set_sample_rate");
+    MI_BANK_SETTER("compressor", "set_sample_rate");
     if (c.sample_rate == sample_rate)
         return MI_OK;
     c.sample_rate = sample_rate;
@@ -497,7 +380,7 @@ int mi_compressor_bank_set_sample_rate(mi_compressor_bank_t *b, uint32_t channel
 
 int mi_compressor_bank_set_mode(mi_compressor_bank_t *b, uint32_t channel, uint32_t mode)                  // :445-452
 {
-    MI_COMP_SETTER("set_mode");
+    MI_BANK_SETTER("compressor", "set_mode");
     if (c.mode == mode)
         return MI_OK;
     c.mode = mode;
@@ -507,7 +390,7 @@ int mi_compressor_bank_set_mode(mi_compressor_bank_t *b, uint32_t channel, uint3
 
 int mi_compressor_bank_set_threshold(mi_compressor_bank_t *b, uint32_t channel, float attack, float release)   // :378-385
 {
-    MI_COMP_SETTER("set_threshold");
+    MI_BANK_SETTER("compressor", "set_threshold");
     if (c.attack_threshold == attack && c.release_threshold == release)
         return MI_OK;
     c.attack_threshold = attack, c.release_threshold = release;
@@ -517,7 +400,7 @@ int mi_compressor_bank_set_threshold(mi_compressor_bank_t *b, uint32_t channel, 
 
 int mi_compressor_bank_set_boost_threshold(mi_compressor_bank_t *b, uint32_t channel, float boost)        // :387-393
 {
-    MI_COMP_SETTER("set_boost_threshold");
+    MI_BANK_SETTER("compressor", "set_boost_threshold");
     if (c.boost_threshold == boost)
         return MI_OK;
     c.boost_threshold = boost;
@@ -527,7 +410,7 @@ int mi_compressor_bank_set_boost_threshold(mi_compressor_bank_t *b, uint32_t cha
 
 int mi_compressor_bank_set_timings(mi_compressor_bank_t *b, uint32_t channel, float attack, float release)     // :395-402
 {
-    MI_COMP_SETTER("set_timings");
+    MI_BANK_SETTER("compressor", "set_timings");
     if (c.attack == attack && c.release == release)
         return MI_OK;
     c.attack = attack, c.release = release;
@@ -537,7 +420,7 @@ int mi_compressor_bank_set_timings(mi_compressor_bank_t *b, uint32_t channel, fl
 
 int mi_compressor_bank_set_hold(mi_compressor_bank_t *b, uint32_t channel, float hold)                    // :454-461
 {
-    MI_COMP_SETTER("set_hold");
+    MI_BANK_SETTER("compressor", "set_hold");
     hold = (hold > 0.0f) ? hold : 0.0f;
     if (c.hold == hold)
         return MI_OK;
@@ -548,7 +431,7 @@ int mi_compressor_bank_set_hold(mi_compressor_bank_t *b, uint32_t channel, float
 
 int mi_compressor_bank_set_knee(mi_compressor_bank_t *b, uint32_t channel, float knee)                    // :428-435
 {
-    MI_COMP_SETTER("set_knee");
+    MI_BANK_SETTER("compressor", "set_knee");
     knee = (knee < 0.0f) ? 0.0f : (knee > 1.0f) ? 1.0f : knee;
     if (c.knee == knee)
         return MI_OK;
@@ -559,15 +442,13 @@ int mi_compressor_bank_set_knee(mi_compressor_bank_t *b, uint32_t channel, float
 
 int mi_compressor_bank_set_ratio(mi_compressor_bank_t *b, uint32_t channel, float ratio)                  // :437-443
 {
-    MI_COMP_SETTER("set_ratio");
+    MI_BANK_SETTER("compressor", "set_ratio");
     if (c.ratio == ratio)
         return MI_OK;
     c.ratio = ratio;
     b->update[channel] = 1;
     return MI_OK;
 }
-
-#undef MI_COMP_SETTER
 
 int mi_compressor_bank_update_settings(mi_compressor_bank_t *b, void *stream)                              // :89-220
 {
@@ -595,10 +476,10 @@ int mi_compressor_bank_get_state(mi_compressor_bank_t *b, uint32_t channel, floa
 {
     MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_compressor_bank_get_state: NULL bank");
     MI_REQUIRE(channel < b->channels, MI_EINVAL, "mi_compressor_bank_get_state: channel %u out of range", channel);
-    hipStream_t st = mi::as_stream(stream);
     device_state s;
-    MI_HIP_CHECK(hipMemcpyAsync(&s, b->d_state + channel, sizeof(s), hipMemcpyDeviceToHost, st));
-    MI_HIP_CHECK(hipStreamSynchronize(st));
+    const int r = mi::read_state(&s, b->d_state + channel, mi::as_stream(stream));
+    if (r != MI_OK)
+        return r;
     if (envelope != nullptr) *envelope = s.e;
     if (peak != nullptr) *peak = s.peak;
     if (hold != nullptr) *hold = s.hold;

@@ -7,6 +7,7 @@
 // reads them back afterwards.  An object whose storage is released without destroy() or its destructor leaves its entry
 // behind until a Sidechain is constructed at that address again.
 #include <lsp-plug.in/dsp-units/util/Sidechain.h>
+#include <lsp-plug.in/dsp-units/units.h>
 
 #include <cmath>
 #include <cstddef>
@@ -117,8 +118,6 @@ namespace
             #pragma GCC diagnostic pop
         }
     };
-
-    inline float millis_to_samples(float sr, float time) { return (time * 0.001f) * sr; }       // units.h:116-119
 }
 
 Sidechain::Sidechain()  { construct(); }

@@ -88,14 +88,7 @@ namespace mi_lanczos
     }
 
     // What clears state or allocates cannot go into a graph: the banks ask, refuse, and name the call to make beforehand.
-    inline int capturing(hipStream_t st, bool *yes)
-    {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (st != nullptr)
-            MI_HIP_CHECK(hipStreamIsCapturing(st, &cs));
-        *yes = cs != hipStreamCaptureStatusNone;
-        return MI_OK;
-    }
+    using mi::capturing;
 } // namespace mi_lanczos
 
 // lin[TAPS + p] = input p of the tile that starts at xs[t0], zero beyond its n inputs; PT values per thread

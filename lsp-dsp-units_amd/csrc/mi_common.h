@@ -184,3 +184,80 @@ namespace mi
 
 #define MI_REQUIRE(cond, code, ...)                                                     \
     do { if (!(cond)) return ::mi::fail((code), __VA_ARGS__); } while (0)
+
+// Host helpers that several banks share (below the macros they use).
+namespace mi
+{
+    // rows that start at p, `stride` floats apart, can be read and written 16 bytes at a time
+    inline bool aligned16(const void *p, size_t stride, uint32_t channels)
+    {
+        return p != nullptr && (reinterpret_cast<uintptr_t>(p) & 15u) == 0 && (channels == 1 || (stride & 3u) == 0);
+    }
+
+    // What clears state, allocates or copies from host memory cannot go into a graph: the banks ask and refuse.
+    inline int capturing(hipStream_t st, bool *yes)
+    {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (st != nullptr)
+            MI_HIP_CHECK(hipStreamIsCapturing(st, &cs));
+        *yes = cs != hipStreamCaptureStatusNone;
+        return MI_OK;
+    }
+
+    // One element of a bank's device state, to and from the host, synchronised: the host's copy may go away after either.
+    template <class S> int read_state(S *host, const S *dev, hipStream_t st)
+    {
+        MI_HIP_CHECK(hipMemcpyAsync(host, dev, sizeof(S), hipMemcpyDeviceToHost, st));
+        MI_HIP_CHECK(hipStreamSynchronize(st));
+        return MI_OK;
+    }
+    template <class S> int write_state(S *dev, const S &host, hipStream_t st)
+    {
+        MI_HIP_CHECK(hipMemcpyAsync(dev, &host, sizeof(S), hipMemcpyHostToDevice, st));
+        MI_HIP_CHECK(hipStreamSynchronize(st));
+        return MI_OK;
+    }
+
+    // A bank's per-channel parameter table lives on the host and on the device; channels [lo, hi) differ between the two.
+    struct dirty_range
+    {
+        uint32_t lo = 0, hi = 0;
+        bool any() const { return lo != hi; }
+        void touch(uint32_t ch)
+        {
+            if (lo == hi)
+                lo = ch, hi = ch + 1;
+            else
+                lo = (ch < lo) ? ch : lo, hi = (ch + 1 > hi) ? ch + 1 : hi;
+        }
+    };
+    // `bank` (its name in messages) is about to send changed settings to the device on st
+    inline int refuse_capture(const char *bank, hipStream_t st)
+    {
+        bool cap = false;
+        const int r = capturing(st, &cap);
+        if (r != MI_OK)
+            return r;
+        MI_REQUIRE(!cap, MI_ESTATE, "%s: changed settings are sent to the device; call update_settings() before capturing", bank);
+        return MI_OK;
+    }
+    // the changed stretch of the table goes to the device, outside a capture
+    template <class P> int upload_dirty(const char *bank, P *dev, const P *host, dirty_range &up, hipStream_t st)
+    {
+        if (!up.any())
+            return MI_OK;
+        const int r = refuse_capture(bank, st);
+        if (r != MI_OK)
+            return r;
+        MI_HIP_CHECK(hipMemcpyAsync(dev + up.lo, host + up.lo, size_t(up.hi - up.lo) * sizeof(P), hipMemcpyHostToDevice, st));
+        MI_HIP_CHECK(hipStreamSynchronize(st));                 // the host table may change again after this returns
+        up = dirty_range();
+        return MI_OK;
+    }
+} // namespace mi
+
+// The opening of a per-channel setter mi_<bank>_bank_<name>(b, channel, ...): the checks, then c = the channel's settings.
+#define MI_BANK_SETTER(bank, name) \
+    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_" bank "_bank_" name ": NULL bank"); \
+    MI_REQUIRE(channel < b->channels, MI_EINVAL, "mi_" bank "_bank_" name ": channel %u out of range", channel); \
+    auto &c = b->cfg[channel]

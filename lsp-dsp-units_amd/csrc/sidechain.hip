@@ -6,21 +6,23 @@
 // The window detectors are rms += x[i]^2 - x[i - N]^2 (RMS) and rms += x[i] - x[i - N] (UNIFORM): the increment d[i] does not
 // depend on rms, so every lane can form it, and what is left of the recurrence is ONE dependent add per sample, in the
 // reference's order.  The low-pass is rms += tau * (x - rms): three dependent operations.  sidechain_kernel runs everything
-// in one launch: a workgroup owns GROUP channels and walks their rows in tiles of TILE samples through LDS, two buffers:
-//     wave 0           the chain over tile k, lane c on row c, d[i] overwritten by the running fRmsValue in LDS
-//     waves 1 .. GROUP one row each: tile k - 1 out of LDS through * interval, the square root or the clamp into `out`, then
-//                      tile k + 1: loads, source, |.| * gain, the samples into the ring, last = x[i - N] (out of the same tile
-//                      where N allows it, out of the ring otherwise), d[i] into the buffer just emptied, and -- where one of the
-//                      tile's samples is the 0x2000th -- the refresh sum over the ring, beside the chain, handed over in LDS
-// one barrier per tile.  A tile is in LDS before anything of it is stored and tile k + 1 is loaded after tile k - 1 was
-// stored, so `out` may be an input row.  The ring in device memory is the reference's (capacity, position), so the refresh
-// sum splits where the reference's splits.  A row's ring is written and read by ONE wave (its helper), whose stores and loads
+// in one launch on the tile walk of tile_chain_device.h:
+//     chain            d[i] overwritten by the running fRmsValue in LDS
+//     emit             a tile out of LDS through * interval, the square root or the clamp into `out`
+//     prepare          loads, source, |.| * gain, the samples into the ring, last = x[i - N] (out of the same tile where N allows
+//                      it, out of the ring otherwise), d[i] into LDS, and -- where one of the tile's samples is the 0x2000th --
+//                      the refresh sum over the ring, beside the chain, handed over in LDS
+// By the walk's invariant `out` may be an input row.  The ring in device memory is the reference's (capacity, position), so
+// the refresh sum splits where the reference's splits.  A row's ring is written and read by ONE wave (its helper), whose stores and loads
 // reach memory in program order; the capacity exceeds N by 0x200 > TILE, so a tile's samples never overwrite a sample the
 // same tile still needs.  Every product and every sum rounds once (no fused multiply-add), the square root is correctly
 // rounded (sqrt_rn): out, fRmsValue, nRefresh and the position match tests/sidechain_ref.py bit for bit.
 //
 // Inputs are finite: NaN is out of scope.  Subnormals are kept (the float32 denormal mode is on).
 #include "sidechain_bank.h"
+#include "tile_chain_device.h"
+
+#include <lsp-plug.in/dsp-units/units.h>
 
 #include <cmath>
 #include <new>
@@ -30,12 +32,9 @@
 
 namespace
 {
-    constexpr int GROUP   = 4;                  // channels of a workgroup: 1024 channels are 256 workgroups, one per CU
-    constexpr int TILE    = 256;                // samples of a row per trip through LDS
-    constexpr int ROW     = TILE + 4;           // floats between rows in LDS: lane c's 16-byte reads start at bank 4c
-    constexpr int HELPERS = GROUP * 64;         // one wave per row
-    constexpr int BLOCK   = 64 + HELPERS;
-    constexpr int BATCH   = 8;                  // samples the chain reads ahead of itself
+    using namespace mi_tile_chain;
+    using lsp::dspu::millis_to_samples;
+
     constexpr int MIX_BLOCK = 256;
     constexpr uint32_t REFRESH_RATE = 0x2000;   // Sidechain.cpp:31
     constexpr uint32_t RING_EXTRA   = 0x200;    // BLOCK_SIZE, Sidechain.cpp:30: what the ring holds beyond the longest window
@@ -45,9 +44,6 @@ namespace
     enum { VEC_OUT = 1, VEC_IN0 = 2, VEC_IN1 = 4 };
     enum { P_RING = 1, P_ZERO_RMS = 2 };        // pending beside nFlags: the ring re-made, set_mode's fRmsValue = 0
 
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) float lds_float;
-    typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
     typedef __attribute__((address_space(1))) float global_float;      // a pointer out of memory is generic to the compiler otherwise
 
     struct device_state { float rms; uint32_t refresh, head, pad; };     // [channels] between calls
@@ -109,31 +105,12 @@ namespace
     // :522-537)
     template <bool LPF> __device__ __forceinline__ float chain_run(lds_float *row, uint32_t i, uint32_t to, float rms, float tau)
     {
-        for (; i < to && (i & 3u) != 0; ++i)
-            row[i] = rms = chain_step<LPF>(row[i], rms, tau);
-        if (i + BATCH <= to)
-        {
-            f32x4 a = *reinterpret_cast<lds_f32x4 *>(row + i), b = *reinterpret_cast<lds_f32x4 *>(row + i + 4);
-            for (; i + BATCH <= to; i += BATCH)
-            {
-                float v[BATCH] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };
-                const uint32_t next = (i + 2 * BATCH <= to) ? i + BATCH : i;   // the next batch, before this one's chain
-                a = *reinterpret_cast<lds_f32x4 *>(row + next);
-                b = *reinterpret_cast<lds_f32x4 *>(row + next + 4);
-                #pragma unroll
-                for (int j = 0; j < BATCH; ++j)
-                    v[j] = rms = chain_step<LPF>(v[j], rms, tau);
-                *reinterpret_cast<lds_f32x4 *>(row + i) = f32x4{ v[0], v[1], v[2], v[3] };
-                *reinterpret_cast<lds_f32x4 *>(row + i + 4) = f32x4{ v[4], v[5], v[6], v[7] };
-            }
-        }
-        for (; i < to; ++i)
-            row[i] = rms = chain_step<LPF>(row[i], rms, tau);
+        chain_batches(row, i, to, [&](float v) { return rms = chain_step<LPF>(v, rms, tau); });
         return rms;
     }
 
     // One tile of one channel: the refresh (refresh_processing() before sample `ridx`: `rval` replaces fRmsValue) and the
-    // detector's recurrence.  A function of its own so that its instructions can be looked at.
+    // detector's recurrence.  A function of its own so that its instructions can be looked at (tests/test_sidechain_host.py).
     __device__ __noinline__ float sidechain_chain_tile(lds_float *row, uint32_t n, float rms, uint32_t mode, float tau,
                                                        uint32_t ridx, float rval)
     {
@@ -161,16 +138,9 @@ namespace
         __shared__ __attribute__((aligned(16))) float xs[GROUP][TILE];          // a helper's own: the tile's samples, the refresh's terms
         __shared__ uint32_t r_idx[2][GROUP];
         __shared__ float r_val[2][GROUP];
-        const int tid = threadIdx.x, lane = tid & 63;
-        const bool chain = tid < 64;
-        const uint32_t ch0 = blockIdx.x * GROUP;
-        const uint32_t tiles = (count + TILE - 1) / TILE;
-
-        // the chain's lane: its channel's state; a helper: its row (one per wave) and its four samples of a tile
-        const uint32_t r = chain ? uint32_t(lane) : uint32_t(__builtin_amdgcn_readfirstlane((tid >> 6) - 1));
-        const uint32_t ch = ch0 + r;
-        const bool valid = r < uint32_t(GROUP) && ch < channels;
-        const uint32_t c = uint32_t(lane) * 4;
+        const role me = my_role(channels);
+        const bool valid = me.valid;
+        const uint32_t lane = me.lane, r = me.r, ch = me.ch, c = me.c;
         mi_sidechain_params_t p = {};
         device_state s0 = {};
         if (valid)
@@ -199,7 +169,7 @@ namespace
                 #pragma unroll
                 for (uint32_t j = 0; j < 4; ++j)
                 {
-                    const uint32_t idx = uint32_t(lane) + 64 * j;
+                    const uint32_t idx = lane + 64 * j;
                     if (idx < m)
                     {
                         const float q = ring[start + base + idx];
@@ -221,8 +191,8 @@ namespace
 
         auto prepare = [&](uint32_t k)
         {
-            const uint32_t t0 = k * TILE, n = (count - t0 < uint32_t(TILE)) ? count - t0 : uint32_t(TILE);
-            const uint32_t buf = k & 1;
+            const extent t = tile_extent(count, k);
+            const uint32_t t0 = t.t0, n = t.n, buf = k & 1;
             // the source, its magnitude, the gain (:183-333, :449-450)
             float x[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
             if (c < n)
@@ -311,8 +281,8 @@ namespace
 
         auto emit = [&](uint32_t k)
         {
-            const uint32_t t0 = k * TILE, n = (count - t0 < uint32_t(TILE)) ? count - t0 : uint32_t(TILE);
-            if (c >= n)
+            const extent t = tile_extent(count, k);
+            if (c >= t.n)
                 return;
             const float4 v4 = *reinterpret_cast<const float4 *>(&tile[k & 1][r][c]);
             float y[4] = { v4.x, v4.y, v4.z, v4.w };
@@ -330,42 +300,14 @@ namespace
                 else if (mode == MI_SCM_LPF)
                     y[j] = (v > 0.0f) ? v : 0.0f;                                   // :478
             }
-            if ((vec & VEC_OUT) && c + 4 <= n)
-                *reinterpret_cast<float4 *>(os + t0 + c) = make_float4(y[0], y[1], y[2], y[3]);
-            else
-            {
-                #pragma unroll
-                for (uint32_t j = 0; j < 4; ++j)
-                    if (c + j < n)
-                        os[t0 + c + j] = y[j];
-            }
+            store_quad(os + t.t0 + c, y, vec & VEC_OUT, c, t.n);
         };
 
-        if (valid && !chain)
-            prepare(0);
-        __syncthreads();
-        for (uint32_t k = 0; k < tiles; ++k)
-        {
-            if (chain)
-            {
-                if (valid)
-                {
-                    const uint32_t t0 = k * TILE, n = (count - t0 < uint32_t(TILE)) ? count - t0 : uint32_t(TILE);
-                    rms = sidechain_chain_tile((lds_float *)&tile[k & 1][r][0], n, rms, mode, p.tau, r_idx[k & 1][r], r_val[k & 1][r]);
-                }
-            }
-            else if (valid)
-            {
-                if (k > 0)
-                    emit(k - 1);
-                if (k + 1 < tiles)
-                    prepare(k + 1);
-            }
-            __syncthreads();
-        }
-        if (valid && !chain)
-            emit(tiles - 1);
-        if (valid && chain)
+        MI_TILE_CHAIN_WALK(me, count, k, prepare(k),
+                           rms = sidechain_chain_tile((lds_float *)&tile[k & 1][r][0], tile_extent(count, k).n, rms, mode, p.tau,
+                                                      r_idx[k & 1][r], r_val[k & 1][r]),
+                           emit(k));
+        if (valid && me.chain)
         {
             // nRefresh after `count` samples (count > 0): it is taken modulo REFRESH_RATE only when a sample follows (:455-459)
             const uint32_t refresh = (R0 + count - 1) % REFRESH_RATE + 1;
@@ -388,8 +330,6 @@ namespace
         const float b = (two != 0 && in1 != nullptr) ? in1[size_t(ch) * in1_stride + i] : 0.0f;
         out[size_t(ch) * out_stride + i] = pick_source(a, b, sel);
     }
-
-    inline float millis_to_samples(float sr, float time) { return (time * 0.001f) * sr; }       // units.h:116-119
 
     // set_sample_rate(), :92: lsp_max(millis_to_samples(sr, fMaxReactivity), 1) + BLOCK_SIZE in float, then size_t
     uint32_t ring_capacity(uint32_t sample_rate, float max_reactivity)
@@ -417,20 +357,6 @@ namespace
         return p;
     }
 
-    bool aligned16(const void *p, size_t stride, uint32_t channels)
-    {
-        return p != nullptr && (reinterpret_cast<uintptr_t>(p) & 15u) == 0 && (channels == 1 || (stride & 3u) == 0);
-    }
-
-    int capturing(hipStream_t st, bool *yes)
-    {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (st != nullptr)
-            MI_HIP_CHECK(hipStreamIsCapturing(st, &cs));
-        *yes = cs != hipStreamCaptureStatusNone;
-        return MI_OK;
-    }
-
     struct channel_cfg { uint32_t sample_rate; float reactivity; uint32_t mode, source, flags; float gain; };
 } // namespace
 
@@ -441,7 +367,7 @@ struct mi_sidechain_bank
     std::vector<channel_cfg>                cfg;            // the setters' values; flags: nFlags
     std::vector<uint8_t>                    pend;           // P_* of every channel
     std::vector<mi_sidechain_params_t>      params;         // what update_settings computed
-    uint32_t                                up_lo = 0, up_hi = 0;   // channels [up_lo, up_hi) differ from the device table
+    mi::dirty_range                         up;             // where params differs from the device table
     bool                                    work = true;    // some channel has flags or pend set
     mi_sidechain_params_t                  *d_params = nullptr;     // [channels]
     device_state                           *d_state = nullptr;      // [channels]
@@ -452,14 +378,6 @@ struct mi_sidechain_bank
 
 namespace
 {
-    void touch(mi_sidechain_bank *b, uint32_t ch)
-    {
-        if (b->up_lo == b->up_hi)
-            b->up_lo = ch, b->up_hi = ch + 1;
-        else
-            b->up_lo = (ch < b->up_lo) ? ch : b->up_lo, b->up_hi = (ch + 1 > b->up_hi) ? ch + 1 : b->up_hi;
-    }
-
     // rings of `stride` floats: the old rows are kept, what is new is zero
     int grow_rings(mi_sidechain_bank *b, size_t stride, hipStream_t st)
     {
@@ -486,13 +404,11 @@ namespace
     // update_settings(), :119-142, of every channel with something pending, and what the setters left for the device
     int sc_update(mi_sidechain_bank *b, hipStream_t st)
     {
-        if (!b->work && b->up_lo == b->up_hi)
+        if (!b->work && !b->up.any())
             return MI_OK;
-        bool cap = false;
-        const int r = capturing(st, &cap);
+        const int r = mi::refuse_capture("mi_sidechain_bank", st);
         if (r != MI_OK)
             return r;
-        MI_REQUIRE(!cap, MI_ESTATE, "mi_sidechain_bank: changed settings are sent to the device; call update_settings() before capturing");
         if (b->work)
         {
             size_t need = b->ring_stride;
@@ -533,31 +449,25 @@ namespace
                     MI_HIP_CHECK(hipMemsetAsync(b->d_ring + size_t(ch) * b->ring_stride, 0, b->ring_stride * sizeof(float), st));
                 c.flags &= MI_SCF_MIDSIDE;
                 b->pend[ch] = 0;
-                touch(b, ch);
+                b->up.touch(ch);
             }
             MI_HIP_CHECK(hipMemcpyAsync(b->d_state, hs.data(), hs.size() * sizeof(device_state), hipMemcpyHostToDevice, st));
             MI_HIP_CHECK(hipStreamSynchronize(st));                     // `hs` is gone after this returns
             b->work = false;
         }
-        if (b->up_lo == b->up_hi)
-            return MI_OK;
-        for (uint32_t ch = b->up_lo; ch < b->up_hi; ++ch)
+        for (uint32_t ch = b->up.lo; ch < b->up.hi; ++ch)
         {
             const channel_cfg &c = b->cfg[ch];
             b->params[ch].mode = c.mode, b->params[ch].source = c.source, b->params[ch].flags = c.flags & MI_SCF_MIDSIDE, b->params[ch].gain = c.gain;
         }
-        MI_HIP_CHECK(hipMemcpyAsync(b->d_params + b->up_lo, b->params.data() + b->up_lo,
-                                    size_t(b->up_hi - b->up_lo) * sizeof(mi_sidechain_params_t), hipMemcpyHostToDevice, st));
-        MI_HIP_CHECK(hipStreamSynchronize(st));                 // the host table may change again after this returns
-        b->up_lo = b->up_hi = 0;
-        return MI_OK;
+        return mi::upload_dirty("mi_sidechain_bank", b->d_params, b->params.data(), b->up, st);
     }
 
     int sc_launch(mi_sidechain_bank *b, float *out, const float *in0, const float *in1, size_t count, size_t out_stride,
                   size_t in0_stride, size_t in1_stride, bool two, hipStream_t st)
     {
-        const uint32_t vec = (aligned16(out, out_stride, b->channels) ? VEC_OUT : 0) | (aligned16(in0, in0_stride, b->channels) ? VEC_IN0 : 0) |
-                             (aligned16(in1, in1_stride, b->channels) ? VEC_IN1 : 0);
+        const uint32_t vec = (mi::aligned16(out, out_stride, b->channels) ? VEC_OUT : 0) | (mi::aligned16(in0, in0_stride, b->channels) ? VEC_IN0 : 0) |
+                             (mi::aligned16(in1, in1_stride, b->channels) ? VEC_IN1 : 0);
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         mi::take_profile_events(&ev0, &ev1);
         MI_LAUNCH(sidechain_kernel, dim3((b->channels + GROUP - 1) / GROUP), dim3(BLOCK), 0, st, ev0, ev1, out, in0, in1, out_stride,
@@ -600,7 +510,7 @@ namespace mi
         c.flags = p->flags & MI_SCF_MIDSIDE;
         b->pend[channel] = ring ? P_RING : 0;
         b->work = b->work || ring;
-        touch(b, channel);
+        b->up.touch(channel);
         return MI_OK;
     }
 
@@ -614,9 +524,7 @@ namespace mi
         const device_state s = { rms_value, (refresh < REFRESH_RATE) ? refresh : REFRESH_RATE, position % b->params[channel].capacity, 0 };
         if (zero_ring)
             MI_HIP_CHECK(hipMemsetAsync(b->d_ring + size_t(channel) * b->ring_stride, 0, b->ring_stride * sizeof(float), st));
-        MI_HIP_CHECK(hipMemcpyAsync(b->d_state + channel, &s, sizeof(s), hipMemcpyHostToDevice, st));
-        MI_HIP_CHECK(hipStreamSynchronize(st));                 // `s` is gone after this returns
-        return MI_OK;
+        return mi::write_state(b->d_state + channel, s, st);
     }
 }
 
@@ -649,7 +557,7 @@ int mi_sidechain_bank_create(mi_sidechain_bank_t **bank, uint32_t channels, uint
     b->cfg.assign(channels, channel_cfg{ 0, 0.0f, MI_SCM_RMS, MI_SCS_MIDDLE, MI_SCF_UPDATE | MI_SCF_CLEAR, 1.0f });
     b->pend.assign(channels, P_RING);                           // a ring for the sample rate 0 until one is set
     b->params.assign(channels, fresh_params());
-    b->up_lo = 0, b->up_hi = channels;
+    b->up.lo = 0, b->up.hi = channels;
     hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_params), size_t(channels) * sizeof(mi_sidechain_params_t));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_state), size_t(channels) * sizeof(device_state));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_desc), sizeof(ring_desc));
@@ -673,14 +581,9 @@ int mi_sidechain_bank_destroy(mi_sidechain_bank_t *b)
     return MI_OK;
 }
 
-#define MI_SC_SETTER(name) \
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_sidechain_bank_" name ": NULL bank"); \
-    MI_REQUIRE(channel < b->channels, MI_EINVAL, "mi_sidechain_bank_" name ": channel %u out of range", channel); \
-    channel_cfg &c = b->cfg[channel]
-
 int mi_sidechain_bank_set_sample_rate(mi_sidechain_bank_t *b, uint32_t channel, uint32_t sample_rate)     // :88-93
 {
-    MI_SC_SETTER("set_sample_rate");
+    MI_BANK_SETTER("sidechain", "set_sample_rate");
     const uint32_t cap = ring_capacity(sample_rate, b->max_reactivity);
     MI_REQUIRE(cap > 0, MI_EINVAL, "mi_sidechain_bank_set_sample_rate: %g ms at %u Hz are too long", double(b->max_reactivity), sample_rate);
     c.sample_rate = sample_rate;
@@ -693,7 +596,7 @@ int mi_sidechain_bank_set_sample_rate(mi_sidechain_bank_t *b, uint32_t channel, 
 
 int mi_sidechain_bank_set_reactivity(mi_sidechain_bank_t *b, uint32_t channel, float reactivity)          // :95-103
 {
-    MI_SC_SETTER("set_reactivity");
+    MI_BANK_SETTER("sidechain", "set_reactivity");
     if (c.reactivity == reactivity || !(reactivity >= 0.0f) || reactivity > b->max_reactivity)
         return MI_OK;
     c.reactivity = reactivity;
@@ -704,7 +607,7 @@ int mi_sidechain_bank_set_reactivity(mi_sidechain_bank_t *b, uint32_t channel, f
 
 int mi_sidechain_bank_set_stereo_mode(mi_sidechain_bank_t *b, uint32_t channel, uint32_t mode)            // :105-112
 {
-    MI_SC_SETTER("set_stereo_mode");
+    MI_BANK_SETTER("sidechain", "set_stereo_mode");
     MI_REQUIRE(mode <= MI_SCSM_MIDSIDE, MI_EINVAL, "mi_sidechain_bank_set_stereo_mode: mode %u", mode);
     const uint32_t old = (c.flags & MI_SCF_MIDSIDE) ? MI_SCSM_MIDSIDE : MI_SCSM_STEREO;
     if (old == mode)
@@ -716,39 +619,37 @@ int mi_sidechain_bank_set_stereo_mode(mi_sidechain_bank_t *b, uint32_t channel, 
 
 int mi_sidechain_bank_set_source(mi_sidechain_bank_t *b, uint32_t channel, uint32_t source)               // Sidechain.h:146-149
 {
-    MI_SC_SETTER("set_source");
+    MI_BANK_SETTER("sidechain", "set_source");
     MI_REQUIRE(source <= MI_SCS_AMAX, MI_EINVAL, "mi_sidechain_bank_set_source: source %u", source);
     if (c.source == source)
         return MI_OK;
     c.source = source;
-    touch(b, channel);
+    b->up.touch(channel);
     return MI_OK;
 }
 
 int mi_sidechain_bank_set_mode(mi_sidechain_bank_t *b, uint32_t channel, uint32_t mode)                   // Sidechain.h:160-166
 {
-    MI_SC_SETTER("set_mode");
+    MI_BANK_SETTER("sidechain", "set_mode");
     MI_REQUIRE(mode <= MI_SCM_UNIFORM, MI_EINVAL, "mi_sidechain_bank_set_mode: mode %u", mode);
     if (c.mode == mode)
         return MI_OK;
     c.mode = mode;
     b->pend[channel] |= P_ZERO_RMS;                             // fRmsValue = 0, no refresh
     b->work = true;
-    touch(b, channel);
+    b->up.touch(channel);
     return MI_OK;
 }
 
 int mi_sidechain_bank_set_gain(mi_sidechain_bank_t *b, uint32_t channel, float gain)                      // Sidechain.h:172-175
 {
-    MI_SC_SETTER("set_gain");
+    MI_BANK_SETTER("sidechain", "set_gain");
     if (memcmp(&c.gain, &gain, sizeof(gain)) == 0)
         return MI_OK;
     c.gain = gain;
-    touch(b, channel);
+    b->up.touch(channel);
     return MI_OK;
 }
-
-#undef MI_SC_SETTER
 
 int mi_sidechain_bank_clear(mi_sidechain_bank_t *b, uint32_t channel)                                     // :114-117
 {
@@ -782,10 +683,10 @@ int mi_sidechain_bank_get_state(mi_sidechain_bank_t *b, uint32_t channel, float 
 {
     MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_sidechain_bank_get_state: NULL bank");
     MI_REQUIRE(channel < b->channels, MI_EINVAL, "mi_sidechain_bank_get_state: channel %u out of range", channel);
-    hipStream_t st = mi::as_stream(stream);
     device_state s;
-    MI_HIP_CHECK(hipMemcpyAsync(&s, b->d_state + channel, sizeof(s), hipMemcpyDeviceToHost, st));
-    MI_HIP_CHECK(hipStreamSynchronize(st));
+    const int r = mi::read_state(&s, b->d_state + channel, mi::as_stream(stream));
+    if (r != MI_OK)
+        return r;
     if (rms_value != nullptr) *rms_value = s.rms;
     if (refresh != nullptr) *refresh = s.refresh;
     if (position != nullptr) *position = s.head;

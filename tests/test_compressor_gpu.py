@@ -13,7 +13,7 @@ import compressor_ref as cr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "lsp-dsp-units_amd")
-T, G = 256, 4                           # compressor.hip: samples of a tile, channels of a workgroup
+T, G = 256, 4                           # tile_chain_device.h: samples of a tile, channels of a workgroup
 f32 = np.float32
 
 

@@ -10,10 +10,10 @@ import numpy as np
 import pytest
 
 import compressor_ref as cr
+import isa_rounding
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "lsp-dsp-units_amd")
-CSRC = os.path.join(PKG, "csrc")
 f32 = np.float32
 
 
@@ -293,23 +293,4 @@ def test_mirror_exports_the_reference_symbols(mi):
 def test_follower_keeps_separate_multiplies_and_adds(tmp_path):
     """The bits of the restatement need tau * d and e + ... rounded on their own: no fused multiply-add in any form in the
     follower's body, under the Makefile's -ffp-contract=on."""
-    out = os.path.join(str(tmp_path), "compressor.s")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=on", "-w",
-                           "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-I" + os.path.join(PKG, "include"),
-                           "-S", "--offload-device-only", os.path.join(CSRC, "compressor.hip"), "-o", out])
-    bodies, cur = {}, None
-    for l in open(out).read().split("\n"):
-        m = re.match(r"^(_Z\w+):", l)
-        if m:
-            cur = m.group(1)
-            bodies[cur] = []
-        elif cur and (l.startswith(".Lfunc_end") or ".amdhsa_kernel" in l):
-            cur = None
-        elif cur:
-            bodies[cur].append(l.strip())
-    names = [n for n in bodies if "compressor_follow_tile" in n]
-    assert len(names) == 1, sorted(bodies)
-    ops = [l.split()[0] for l in bodies[names[0]] if l and not l.startswith((";", "."))]
-    assert len(ops) > 20
-    fused = [o for o in ops if o.startswith(("v_fma", "v_fmac", "v_mad_f", "v_mac_f"))]
-    assert not fused, fused
+    isa_rounding.assert_separate_multiplies_and_adds(tmp_path, "compressor.hip", "compressor_follow_tile")

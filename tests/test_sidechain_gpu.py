@@ -15,7 +15,7 @@ import sidechain_ref as sr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "lsp-dsp-units_amd")
-T, G = 256, 4                           # sidechain.hip: samples of a tile, channels of a workgroup
+T, G = 256, 4                           # tile_chain_device.h: samples of a tile, channels of a workgroup
 f32 = np.float32
 RATE, MAX_MS, N_MAX = 48000, 10.0, 480  # the banks of most tests: 10 ms at 48 kHz, rings of 992 samples
 LENGTHS = (1, T - 1, T, T + 1, N_MAX)   # last = x[i - N] out of the same tile, across the straddle, out of the ring

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import isa_rounding
 import sidechain_ref as sr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -386,3 +387,10 @@ def test_mirrors_export_the_references_symbols(mi):
                 "_ZNK3lsp4dspu13RawRingBuffer9remainingEm", "_ZN3lsp4dspu13RawRingBuffer4fillEf",
                 "_ZNK3lsp4dspu13RawRingBuffer4dumpEPNS0_12IStateDumperE"):
         assert re.search(r" T %s$" % re.escape(sym), out, re.M), sym
+
+
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
+def test_chain_keeps_separate_multiplies_and_adds(tmp_path):
+    """The bits of the restatement need the low-pass's tau * (x - rms) and rms + ... rounded on their own: no fused multiply-add
+    in any form in the chain's body, under the Makefile's -ffp-contract=on."""
+    isa_rounding.assert_separate_multiplies_and_adds(tmp_path, "sidechain.hip", "sidechain_chain_tile")
