@@ -960,6 +960,109 @@ int mi_compressor_bank_process_apply(mi_compressor_bank_t *bank, float *dst, con
 int mi_compressor_bank_curve(mi_compressor_bank_t *bank, float *out, const float *in, size_t dots, size_t out_stride,
                              size_t in_stride, void *stream);
 
+/* ---- expander bank (envelope follower and one-knee gain curve with a floor or a ceiling) -------------------------------- */
+/*
+ * mi_expander_bank: `channels` x lsp::dspu::Expander (dynamics/Expander.h:40-283, src/main/dynamics/Expander.cpp), every
+ * channel with settings and a mode of its own.  process() is the reference's: the Compressor's envelope follower (:252-284),
+ * then Expander::amplification(float) (:375-407), which stands for dsp::uexpander_x1_gain / dexpander_x1_gain of the absent
+ * lsp-dsp-lib.  Envelope, peak and hold counter are the reference's bit for bit in float32; the gain is within the bound
+ * DESIGN.md section 3.12 derives.  State on the device, no positions: calls can be captured and replayed.  Inputs are
+ * finite; subnormal envelopes are kept.  Rows of the sample buffers: [channels][stride].
+ */
+typedef struct mi_expander_bank mi_expander_bank_t;
+enum mi_expander_mode { MI_EM_DOWNWARD = 0, MI_EM_UPWARD = 1 };                           /* expander_mode_t */
+/* dsp::expander_knee_t of lsp-dsp-lib.  Upward: |x| is limited to threshold, above start the gain is exp(tilt[0] ln x +
+ * tilt[1]) from end on and exp((herm[0] ln x + herm[1]) ln x + herm[2]) below it, otherwise 1.  Downward: 0 below
+ * threshold, below end the tilt line up to start and the knee above it, otherwise 1. */
+typedef struct { float start, end, threshold, herm[3], tilt[2]; } mi_expander_knee_t;
+/* what update_settings() computes: fTauAttack, fTauRelease, fReleaseThresh as set, nHold, sExp, bUpward */
+typedef struct { float tau_attack, tau_release, release_threshold; uint32_t hold; mi_expander_knee_t k; uint32_t upward; } mi_expander_params_t;
+/* the setters' values: times in ms; mode is kept as the reference keeps it, upward or not */
+typedef struct
+{
+    uint32_t sample_rate, mode;
+    float attack_threshold, release_threshold, attack, release, hold, knee, ratio;
+} mi_expander_settings_t;
+/* update_settings(), :200-245, of one expander in host float32, with square_roots (:44-57) and the UPPER_ / LOWER_THRESHOLD
+ * limits.  No device needed. */
+int mi_expander_compute_params(const mi_expander_settings_t *settings, mi_expander_params_t *params);
+/* construct(), :70-101: every channel UPWARD, ratio 1, everything else 0, an update pending */
+int mi_expander_bank_create(mi_expander_bank_t **bank, uint32_t channels);
+int mi_expander_bank_destroy(mi_expander_bank_t *bank);
+/* The setters of one channel (:107-198): each returns early on an unchanged value.  set_hold limits to >= 0; nothing else
+ * is limited (set_knee is not, unlike the Compressor's).  set_mode compares "upward or not", as the reference does. */
+int mi_expander_bank_set_sample_rate(mi_expander_bank_t *bank, uint32_t channel, uint32_t sample_rate);
+int mi_expander_bank_set_mode(mi_expander_bank_t *bank, uint32_t channel, uint32_t mode);
+int mi_expander_bank_set_threshold(mi_expander_bank_t *bank, uint32_t channel, float attack, float release);
+int mi_expander_bank_set_timings(mi_expander_bank_t *bank, uint32_t channel, float attack, float release);
+int mi_expander_bank_set_hold(mi_expander_bank_t *bank, uint32_t channel, float hold);
+int mi_expander_bank_set_knee(mi_expander_bank_t *bank, uint32_t channel, float knee);
+int mi_expander_bank_set_ratio(mi_expander_bank_t *bank, uint32_t channel, float ratio);
+/* as mi_compressor_bank_update_settings / _clear / _get_params / _get_state */
+int mi_expander_bank_update_settings(mi_expander_bank_t *bank, void *stream);
+int mi_expander_bank_clear(mi_expander_bank_t *bank, void *stream);
+int mi_expander_bank_get_params(const mi_expander_bank_t *bank, uint32_t channel, mi_expander_params_t *params);
+int mi_expander_bank_get_state(mi_expander_bank_t *bank, uint32_t channel, float *envelope, float *peak, uint32_t *hold,
+                               void *stream);
+/* process(out, env, in, samples), :247-292; gain or env may be the input rows (same stride); gain and env differ */
+int mi_expander_bank_process(mi_expander_bank_t *bank, float *gain, float *env, const float *in, size_t count,
+                             size_t gain_stride, size_t env_stride, size_t in_stride, void *stream);
+/* dst = audio * gain(sc) in the same launch; dst may be audio or sc (same stride) */
+int mi_expander_bank_process_apply(mi_expander_bank_t *bank, float *dst, const float *audio, const float *sc, size_t count,
+                                   size_t dst_stride, size_t audio_stride, size_t sc_stride, void *stream);
+/* curve(out, in, dots), as the scalar overload :333-365 states it, stateless; update_settings() first */
+int mi_expander_bank_curve(mi_expander_bank_t *bank, float *out, const float *in, size_t dots, size_t out_stride,
+                           size_t in_stride, void *stream);
+
+/* ---- gate bank (envelope follower, two cubic curves and the hysteresis between them) ------------------------------------ */
+/*
+ * mi_gate_bank: `channels` x lsp::dspu::Gate (dynamics/Gate.h:34-288, src/main/dynamics/Gate.cpp), every channel with
+ * settings of its own.  process() restates the block overload (:267-367): the follower without a release threshold, and per
+ * sample the curve in force, open (0) or close (1).  When the envelope leaves the curve in force (above sCurves[0].sKnee.end
+ * on curve 0, below sCurves[1].sKnee.start on curve 1) the reference runs the follower a second time on the same input
+ * sample under the other curve; that sample's envelope and gain are the second step's.  The arithmetic is that of the
+ * reference's out-of-place call whichever buffers alias.  ONE DIFFERENCE: a sample is stepped again at most once, then the
+ * walk advances; with close start <= open end and taus in [0, 1] the reference never does more, with inverted thresholds
+ * it may not return.  Unlike Gate::process, the bank's process entries apply pending settings first.
+ * Envelope, peak, hold counter and curve index bit for bit; the gain within the bound section 3.13 derives.
+ */
+typedef struct mi_gate_bank mi_gate_bank_t;
+/* dsp::gate_knee_t of lsp-dsp-lib: gain_start up to start, gain_end from end on, between them
+ * exp(((herm[0] ln x + herm[1]) ln x + herm[2]) ln x + herm[3]) */
+typedef struct { float start, end, gain_start, gain_end, herm[4]; } mi_gate_knee_t;
+/* what update_settings() computes: fTauAttack, fTauRelease, nHold, sCurves[0..1].sKnee */
+typedef struct { float tau_attack, tau_release; uint32_t hold, reserved; mi_gate_knee_t k[2]; } mi_gate_params_t;
+/* the setters' values: [0] the open curve, [1] the close curve; times in ms */
+typedef struct { uint32_t sample_rate; float threshold[2], zone[2], reduction, attack, release, hold; } mi_gate_settings_t;
+/* update_settings(), :180-205, in host float32; interpolation::hermite_cubic with its double intermediates on float32
+ * differences and products (interpolation.cpp:112-131).  A zone of 1 gives non-finite coefficients that no sample reaches.
+ * No device needed. */
+int mi_gate_compute_params(const mi_gate_settings_t *settings, mi_gate_params_t *params);
+/* construct(), :41-74: both zones 1, everything else 0, curve 0, an update pending */
+int mi_gate_bank_create(mi_gate_bank_t **bank, uint32_t channels);
+int mi_gate_bank_destroy(mi_gate_bank_t *bank);
+/* The setters of one channel (:80-178): early return on unchanged values; set_hold limits to >= 0, nothing else is limited */
+int mi_gate_bank_set_sample_rate(mi_gate_bank_t *bank, uint32_t channel, uint32_t sample_rate);
+int mi_gate_bank_set_threshold(mi_gate_bank_t *bank, uint32_t channel, float open, float close);
+int mi_gate_bank_set_zone(mi_gate_bank_t *bank, uint32_t channel, float open, float close);
+int mi_gate_bank_set_reduction(mi_gate_bank_t *bank, uint32_t channel, float reduction);
+int mi_gate_bank_set_timings(mi_gate_bank_t *bank, uint32_t channel, float attack, float release);
+int mi_gate_bank_set_hold(mi_gate_bank_t *bank, uint32_t channel, float hold);
+int mi_gate_bank_update_settings(mi_gate_bank_t *bank, void *stream);
+/* clear(): envelope, peak, hold counter and curve index to zero */
+int mi_gate_bank_clear(mi_gate_bank_t *bank, void *stream);
+int mi_gate_bank_get_params(const mi_gate_bank_t *bank, uint32_t channel, mi_gate_params_t *params);
+/* fEnvelope, fPeak, nHoldCounter, nCurve of the channel (HOST memory, each may be NULL; waits for the stream) */
+int mi_gate_bank_get_state(mi_gate_bank_t *bank, uint32_t channel, float *envelope, float *peak, uint32_t *hold,
+                           uint32_t *curve, void *stream);
+int mi_gate_bank_process(mi_gate_bank_t *bank, float *gain, float *env, const float *in, size_t count,
+                         size_t gain_stride, size_t env_stride, size_t in_stride, void *stream);
+int mi_gate_bank_process_apply(mi_gate_bank_t *bank, float *dst, const float *audio, const float *sc, size_t count,
+                               size_t dst_stride, size_t audio_stride, size_t sc_stride, void *stream);
+/* curve(out, in, dots, hyst), :207-226: the open curve, or with hyst != 0 the close curve, stateless */
+int mi_gate_bank_curve(mi_gate_bank_t *bank, float *out, const float *in, size_t dots, int hyst, size_t out_stride,
+                       size_t in_stride, void *stream);
+
 /* ---- sidechain bank (source selection, pre-amplification and the peak / RMS / low-pass / uniform detectors) ------------- */
 /*
  * mi_sidechain_bank: `channels` x lsp::dspu::Sidechain (util/Sidechain.h:59-205, src/main/util/Sidechain.cpp), every channel

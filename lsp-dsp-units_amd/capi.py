@@ -52,6 +52,39 @@ class CompressorSettings(ctypes.Structure):
                                        "hold", "knee", "ratio")]
 
 
+class ExpanderKnee(ctypes.Structure):
+    """mi_expander_knee_t == dsp::expander_knee_t layout."""
+    _fields_ = [("start", c_float), ("end", c_float), ("threshold", c_float), ("herm", c_float * 3), ("tilt", c_float * 2)]
+
+
+class ExpanderParams(ctypes.Structure):
+    """mi_expander_params_t: what Expander::update_settings computes."""
+    _fields_ = [("tau_attack", c_float), ("tau_release", c_float), ("release_threshold", c_float), ("hold", c_uint32),
+                ("k", ExpanderKnee), ("upward", c_uint32)]
+
+
+class ExpanderSettings(ctypes.Structure):
+    """mi_expander_settings_t: the values of Expander's setters."""
+    _fields_ = [("sample_rate", c_uint32), ("mode", c_uint32)] + \
+               [(n, c_float) for n in ("attack_threshold", "release_threshold", "attack", "release", "hold", "knee", "ratio")]
+
+
+class GateKnee(ctypes.Structure):
+    """mi_gate_knee_t == dsp::gate_knee_t layout."""
+    _fields_ = [("start", c_float), ("end", c_float), ("gain_start", c_float), ("gain_end", c_float), ("herm", c_float * 4)]
+
+
+class GateParams(ctypes.Structure):
+    """mi_gate_params_t: what Gate::update_settings computes."""
+    _fields_ = [("tau_attack", c_float), ("tau_release", c_float), ("hold", c_uint32), ("reserved", c_uint32), ("k", GateKnee * 2)]
+
+
+class GateSettings(ctypes.Structure):
+    """mi_gate_settings_t: the values of Gate's setters; [0] the open curve, [1] the close curve."""
+    _fields_ = [("sample_rate", c_uint32), ("threshold", c_float * 2), ("zone", c_float * 2), ("reduction", c_float),
+                ("attack", c_float), ("release", c_float), ("hold", c_float)]
+
+
 class SidechainParams(ctypes.Structure):
     """mi_sidechain_params_t: what Sidechain::update_settings and set_sample_rate compute, and the settings beside them."""
     _fields_ = [("reactivity", c_uint32), ("tau", c_float), ("interval", c_float), ("capacity", c_uint32), ("mode", c_uint32),
@@ -251,6 +284,39 @@ PROTOTYPES = {
     "mi_compressor_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_compressor_bank_process_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_compressor_bank_curve": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_expander_compute_params": (c_int, [POINTER(ExpanderSettings), POINTER(ExpanderParams)]),
+    "mi_expander_bank_create": (c_int, [POINTER(c_void_p), c_uint32]),
+    "mi_expander_bank_destroy": (c_int, [c_void_p]),
+    "mi_expander_bank_set_sample_rate": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_expander_bank_set_mode": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_expander_bank_set_threshold": (c_int, [c_void_p, c_uint32, c_float, c_float]),
+    "mi_expander_bank_set_timings": (c_int, [c_void_p, c_uint32, c_float, c_float]),
+    "mi_expander_bank_set_hold": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_expander_bank_set_knee": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_expander_bank_set_ratio": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_expander_bank_update_settings": (c_int, [c_void_p, c_void_p]),
+    "mi_expander_bank_clear": (c_int, [c_void_p, c_void_p]),
+    "mi_expander_bank_get_params": (c_int, [c_void_p, c_uint32, POINTER(ExpanderParams)]),
+    "mi_expander_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(c_float), POINTER(c_float), POINTER(c_uint32), c_void_p]),
+    "mi_expander_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_expander_bank_process_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_expander_bank_curve": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_gate_compute_params": (c_int, [POINTER(GateSettings), POINTER(GateParams)]),
+    "mi_gate_bank_create": (c_int, [POINTER(c_void_p), c_uint32]),
+    "mi_gate_bank_destroy": (c_int, [c_void_p]),
+    "mi_gate_bank_set_sample_rate": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_gate_bank_set_threshold": (c_int, [c_void_p, c_uint32, c_float, c_float]),
+    "mi_gate_bank_set_zone": (c_int, [c_void_p, c_uint32, c_float, c_float]),
+    "mi_gate_bank_set_reduction": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_gate_bank_set_timings": (c_int, [c_void_p, c_uint32, c_float, c_float]),
+    "mi_gate_bank_set_hold": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_gate_bank_update_settings": (c_int, [c_void_p, c_void_p]),
+    "mi_gate_bank_clear": (c_int, [c_void_p, c_void_p]),
+    "mi_gate_bank_get_params": (c_int, [c_void_p, c_uint32, POINTER(GateParams)]),
+    "mi_gate_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(c_float), POINTER(c_float), POINTER(c_uint32), POINTER(c_uint32), c_void_p]),
+    "mi_gate_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_gate_bank_process_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_gate_bank_curve": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_size_t, c_size_t, c_void_p]),
     "mi_sidechain_compute_params": (c_int, [c_uint32, c_float, c_float, POINTER(SidechainParams)]),
     "mi_sidechain_bank_create": (c_int, [POINTER(c_void_p), c_uint32, c_uint32, c_float]),
     "mi_sidechain_bank_destroy": (c_int, [c_void_p]),

@@ -69,6 +69,29 @@ namespace lsp
         struct compressor_x2_t { compressor_knee_t k[2]; };
         static_assert(sizeof(compressor_knee_t) == 32 && sizeof(compressor_x2_t) == 64, "lsp-dsp-lib layouts");
 
+        // lsp-dsp-lib's expander curve (Expander keeps one): a tilt line exp(tilt[0] ln x + tilt[1]) and a knee
+        // exp((herm[0] ln x + herm[1]) ln x + herm[2]) between start and end; threshold is the ceiling of the level (upward)
+        // or the level below which the gain is 0 (downward)
+        struct expander_knee_t
+        {
+            float start;
+            float end;
+            float threshold;
+            float herm[3];
+            float tilt[2];
+        };
+        // lsp-dsp-lib's gate curve (Gate keeps two): gain_start up to start, gain_end from end on, between them
+        // exp(((herm[0] ln x + herm[1]) ln x + herm[2]) ln x + herm[3])
+        struct gate_knee_t
+        {
+            float start;
+            float end;
+            float gain_start;
+            float gain_end;
+            float herm[4];
+        };
+        static_assert(sizeof(expander_knee_t) == 32 && sizeof(gate_knee_t) == 32, "lsp-dsp-lib layouts");
+
         // lsp-dsp-lib's per-thread context / init are no-ops here: there is no SIMD dispatch to select
         struct context_t { uint32_t top; uint32_t data[15]; };
         inline void init() {}

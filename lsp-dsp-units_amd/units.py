@@ -922,6 +922,182 @@ class CompressorBank:
             pass
 
 
+class _DynamicsBank:
+    """What ExpanderBank and GateBank share with each other: the calls of mi_<unit>_bank_* that have one signature."""
+    UNIT = None
+
+    def __init__(self, channels):
+        h = c_void_p()
+        check(self._fn("create")(byref(h), channels))
+        self.handle, self.channels = h, channels
+
+    @classmethod
+    def _fn(cls, name):
+        return getattr(lib, "mi_%s_bank_%s" % (cls.UNIT, name))
+
+    def set_sample_rate(self, channel, sr):
+        check(self._fn("set_sample_rate")(self.handle, channel, sr))
+
+    def set_timings(self, channel, attack, release):
+        check(self._fn("set_timings")(self.handle, channel, attack, release))
+
+    def set_hold(self, channel, hold):
+        check(self._fn("set_hold")(self.handle, channel, hold))
+
+    def update_settings(self, stream=None):
+        check(self._fn("update_settings")(self.handle, _stream(stream)))
+
+    def clear(self, stream=None):
+        check(self._fn("clear")(self.handle, _stream(stream)))
+
+    def process(self, gain, env, inp, count, gain_stride=None, env_stride=None, in_stride=None, stream=None):
+        """process(out, env, in, samples); env may be None, gain or env may be inp (in place)."""
+        check(self._fn("process")(self.handle, _ptr(gain), None if env is None else _ptr(env), _ptr(inp), count,
+                                  count if gain_stride is None else gain_stride, count if env_stride is None else env_stride,
+                                  count if in_stride is None else in_stride, _stream(stream)))
+
+    def process_apply(self, out, audio, sc, count, out_stride=None, audio_stride=None, sc_stride=None, stream=None):
+        """out = audio * gain(sc) in one launch; out may be audio or sc."""
+        check(self._fn("process_apply")(self.handle, _ptr(out), _ptr(audio), _ptr(sc), count,
+                                        count if out_stride is None else out_stride,
+                                        count if audio_stride is None else audio_stride,
+                                        count if sc_stride is None else sc_stride, _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            self._fn("destroy")(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _expander_dict(p):
+    return {"tau_attack": p.tau_attack, "tau_release": p.tau_release, "release_threshold": p.release_threshold, "hold": p.hold,
+            "upward": p.upward,
+            "k": {"start": p.k.start, "end": p.k.end, "threshold": p.k.threshold, "herm": np.array(p.k.herm[:], np.float32),
+                  "tilt": np.array(p.k.tilt[:], np.float32)}}
+
+
+class ExpanderBank(_DynamicsBank):
+    """`channels` x lsp::dspu::Expander (mi_expander_bank_*): envelope follower and one-knee gain curve, upward or downward,
+    every channel with settings of its own."""
+    UNIT = "expander"
+    EM_DOWNWARD, EM_UPWARD = range(2)
+
+    @staticmethod
+    def compute_params(sample_rate=0, mode=1, attack_threshold=0.0, release_threshold=0.0, attack=0.0, release=0.0, hold=0.0,
+                       knee=0.0, ratio=1.0):
+        """update_settings() of one expander on the host (mi_expander_compute_params): no device needed."""
+        from .capi import ExpanderParams, ExpanderSettings
+        s = ExpanderSettings(sample_rate, mode, attack_threshold, release_threshold, attack, release, hold, knee, ratio)
+        p = ExpanderParams()
+        check(lib.mi_expander_compute_params(byref(s), byref(p)))
+        return _expander_dict(p)
+
+    def set_mode(self, channel, mode):
+        check(lib.mi_expander_bank_set_mode(self.handle, channel, mode))
+
+    def set_threshold(self, channel, attack, release):
+        check(lib.mi_expander_bank_set_threshold(self.handle, channel, attack, release))
+
+    def set_knee(self, channel, knee):
+        check(lib.mi_expander_bank_set_knee(self.handle, channel, knee))
+
+    def set_ratio(self, channel, ratio):
+        check(lib.mi_expander_bank_set_ratio(self.handle, channel, ratio))
+
+    def configure(self, channel, sample_rate, mode, attack_threshold, release_threshold, attack, release, hold, knee, ratio):
+        """Every setter of one channel."""
+        self.set_sample_rate(channel, sample_rate)
+        self.set_mode(channel, mode)
+        self.set_threshold(channel, attack_threshold, release_threshold)
+        self.set_timings(channel, attack, release)
+        self.set_hold(channel, hold)
+        self.set_knee(channel, knee)
+        self.set_ratio(channel, ratio)
+
+    def get_params(self, channel):
+        from .capi import ExpanderParams
+        p = ExpanderParams()
+        check(lib.mi_expander_bank_get_params(self.handle, channel, byref(p)))
+        return _expander_dict(p)
+
+    def get_state(self, channel, stream=None):
+        """(fEnvelope, fPeak, nHoldCounter) of the channel; the envelope and the peak as numpy float32."""
+        e, p, h = c_float(), c_float(), c_uint32()
+        check(lib.mi_expander_bank_get_state(self.handle, channel, byref(e), byref(p), byref(h), _stream(stream)))
+        return np.float32(e.value), np.float32(p.value), h.value
+
+    def curve(self, out, inp, dots, out_stride=None, in_stride=None, stream=None):
+        """curve(out, in, dots) of every channel."""
+        check(lib.mi_expander_bank_curve(self.handle, _ptr(out), _ptr(inp), dots, dots if out_stride is None else out_stride,
+                                         dots if in_stride is None else in_stride, _stream(stream)))
+
+
+def _gate_dict(p):
+    return {"tau_attack": p.tau_attack, "tau_release": p.tau_release, "hold": p.hold,
+            "k": [{"start": k.start, "end": k.end, "gain_start": k.gain_start, "gain_end": k.gain_end,
+                   "herm": np.array(k.herm[:], np.float32)} for k in p.k]}
+
+
+class GateBank(_DynamicsBank):
+    """`channels` x lsp::dspu::Gate (mi_gate_bank_*): envelope follower, an open and a close curve and the hysteresis between
+    them, every channel with settings of its own."""
+    UNIT = "gate"
+
+    @staticmethod
+    def compute_params(sample_rate=0, open_threshold=0.0, close_threshold=0.0, open_zone=1.0, close_zone=1.0, reduction=0.0,
+                       attack=0.0, release=0.0, hold=0.0):
+        """update_settings() of one gate on the host (mi_gate_compute_params): no device needed."""
+        from .capi import GateParams, GateSettings
+        s = GateSettings(sample_rate, (c_float * 2)(open_threshold, close_threshold), (c_float * 2)(open_zone, close_zone),
+                         reduction, attack, release, hold)
+        p = GateParams()
+        check(lib.mi_gate_compute_params(byref(s), byref(p)))
+        return _gate_dict(p)
+
+    def set_threshold(self, channel, open, close):
+        check(lib.mi_gate_bank_set_threshold(self.handle, channel, open, close))
+
+    def set_zone(self, channel, open, close):
+        check(lib.mi_gate_bank_set_zone(self.handle, channel, open, close))
+
+    def set_reduction(self, channel, reduction):
+        check(lib.mi_gate_bank_set_reduction(self.handle, channel, reduction))
+
+    def configure(self, channel, sample_rate, open_threshold, close_threshold, open_zone, close_zone, reduction, attack, release,
+                  hold):
+        """Every setter of one channel."""
+        self.set_sample_rate(channel, sample_rate)
+        self.set_threshold(channel, open_threshold, close_threshold)
+        self.set_zone(channel, open_zone, close_zone)
+        self.set_reduction(channel, reduction)
+        self.set_timings(channel, attack, release)
+        self.set_hold(channel, hold)
+
+    def get_params(self, channel):
+        from .capi import GateParams
+        p = GateParams()
+        check(lib.mi_gate_bank_get_params(self.handle, channel, byref(p)))
+        return _gate_dict(p)
+
+    def get_state(self, channel, stream=None):
+        """(fEnvelope, fPeak, nHoldCounter, nCurve) of the channel; the envelope and the peak as numpy float32."""
+        e, p, h, c = c_float(), c_float(), c_uint32(), c_uint32()
+        check(lib.mi_gate_bank_get_state(self.handle, channel, byref(e), byref(p), byref(h), byref(c), _stream(stream)))
+        return np.float32(e.value), np.float32(p.value), h.value, c.value
+
+    def curve(self, out, inp, dots, hyst=False, out_stride=None, in_stride=None, stream=None):
+        """curve(out, in, dots, hyst) of every channel: the open curve, with hyst the close curve."""
+        check(lib.mi_gate_bank_curve(self.handle, _ptr(out), _ptr(inp), dots, 1 if hyst else 0,
+                                     dots if out_stride is None else out_stride, dots if in_stride is None else in_stride,
+                                     _stream(stream)))
+
+
 def _sidechain_dict(p):
     return {"reactivity": p.reactivity, "tau": np.float32(p.tau), "interval": np.float32(p.interval), "capacity": p.capacity,
             "mode": p.mode, "source": p.source, "flags": p.flags, "gain": np.float32(p.gain)}
