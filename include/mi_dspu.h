@@ -1063,6 +1063,81 @@ int mi_gate_bank_process_apply(mi_gate_bank_t *bank, float *dst, const float *au
 int mi_gate_bank_curve(mi_gate_bank_t *bank, float *out, const float *in, size_t dots, int hyst, size_t out_stride,
                        size_t in_stride, void *stream);
 
+/* ---- dynamic processor bank (envelope follower with level-dependent reaction times, curve through up to four dots) ------ */
+/*
+ * mi_dynproc_bank: `channels` x lsp::dspu::DynamicProcessor (dynamics/DynamicProcessor.h:42-333,
+ * src/main/dynamics/DynamicProcessor.cpp), every channel with settings of its own.  process() is the reference's block overload
+ * (:397-442): the follower over (fEnvelope, fPeak, nHoldCounter) whose tau is looked up per sample from the envelope BEFORE the
+ * step (solve_reaction, :195-202), then the array reduction() (:562-584): |e| limited to [GAIN_AMP_MIN = 1e-6, 1e10], the sum
+ * of spline_amp (:173-183) over the channel's splines in the reference's order, expf of it.  The scalar reduction(float), curve
+ * and model limit at 1e-10 instead (FLOAT_SAT_M_INF); curve and model here are the array forms (:474-496, :518-540), which do
+ * so too.  Envelope, peak and hold counter are the reference's bit for bit in float32; the gain is within the bound DESIGN.md
+ * section 3.14 derives; no spline enabled gives exactly 1.  State on the device, no positions: calls can be captured and
+ * replayed.  Inputs are finite.  Rows of the sample buffers: [channels][stride].
+ */
+typedef struct mi_dynproc_bank mi_dynproc_bank_t;
+#define MI_DYNPROC_DOTS   4                                                                 /* DYNAMIC_PROCESSOR_DOTS */
+#define MI_DYNPROC_RANGES 5                                                                 /* DYNAMIC_PROCESSOR_RANGES */
+typedef struct { float input, output, knee; } mi_dynproc_dot_t;                             /* dyndot_t: a negative field is "off" */
+/* spline_t (DynamicProcessor.h:49-58): up to knee_start makeup + pre_ratio (ln x - thresh), from knee_stop on makeup +
+ * post_ratio (ln x - thresh), between them (herm[0] ln x + herm[1]) ln x + herm[2]; herm[3] is never written */
+typedef struct { float pre_ratio, post_ratio, knee_start, knee_stop, thresh, makeup, herm[4]; } mi_dynproc_spline_t;
+typedef struct { float level, tau; } mi_dynproc_reaction_t;                                 /* reaction_t, sorted by level */
+/* what update_settings() computes: fCount[CT_SPLINES / CT_ATTACK / CT_RELEASE], nHold, vAttack, vRelease, vSplines; entries
+ * from the count on are zero */
+typedef struct
+{
+    uint32_t splines, attacks, releases, hold;
+    mi_dynproc_reaction_t attack[MI_DYNPROC_RANGES], release[MI_DYNPROC_RANGES];
+    mi_dynproc_spline_t spline[MI_DYNPROC_DOTS];
+} mi_dynproc_params_t;
+/* the setters' values: times in ms; a negative level switches the range above it off */
+typedef struct
+{
+    uint32_t sample_rate;
+    float hold, in_ratio, out_ratio;
+    mi_dynproc_dot_t dot[MI_DYNPROC_DOTS];
+    float attack_level[MI_DYNPROC_DOTS], release_level[MI_DYNPROC_DOTS];
+    float attack_time[MI_DYNPROC_RANGES], release_time[MI_DYNPROC_RANGES];
+} mi_dynproc_settings_t;
+/* update_settings(), :339-395, of one processor in host float32 with sort_reactions (:204-227), sort_splines (:229-285) and
+ * interpolation::hermite_quadratic (interpolation.cpp:103-109).  Two dots with one input divide by zero, as in the reference.
+ * No device needed. */
+int mi_dynproc_compute_params(const mi_dynproc_settings_t *settings, mi_dynproc_params_t *params);
+/* construct(), :43-74: both ratios 1, everything else 0 -- so all four dots are ON at (0, 0, 0), which update_settings() cannot
+ * evaluate to finite numbers (logf(0), 0 / 0), as in the reference: set every dot before use.  An update is pending. */
+int mi_dynproc_bank_create(mi_dynproc_bank_t **bank, uint32_t channels);
+int mi_dynproc_bank_destroy(mi_dynproc_bank_t *bank);
+/* The setters of one channel (:80-171, :287-337): each returns early on an unchanged value; an id out of range is MI_EINVAL
+ * (the reference ignores it).  set_hold limits to >= 0.  set_dot with dot == NULL switches the dot off (-1, -1, -1). */
+int mi_dynproc_bank_set_sample_rate(mi_dynproc_bank_t *bank, uint32_t channel, uint32_t sample_rate);
+int mi_dynproc_bank_set_in_ratio(mi_dynproc_bank_t *bank, uint32_t channel, float ratio);
+int mi_dynproc_bank_set_out_ratio(mi_dynproc_bank_t *bank, uint32_t channel, float ratio);
+int mi_dynproc_bank_set_dot(mi_dynproc_bank_t *bank, uint32_t channel, uint32_t id, const mi_dynproc_dot_t *dot);
+int mi_dynproc_bank_set_attack_level(mi_dynproc_bank_t *bank, uint32_t channel, uint32_t id, float level);
+int mi_dynproc_bank_set_release_level(mi_dynproc_bank_t *bank, uint32_t channel, uint32_t id, float level);
+int mi_dynproc_bank_set_attack_time(mi_dynproc_bank_t *bank, uint32_t channel, uint32_t id, float time);
+int mi_dynproc_bank_set_release_time(mi_dynproc_bank_t *bank, uint32_t channel, uint32_t id, float time);
+int mi_dynproc_bank_set_hold(mi_dynproc_bank_t *bank, uint32_t channel, float hold);
+/* as mi_compressor_bank_update_settings / _clear / _get_params / _get_state */
+int mi_dynproc_bank_update_settings(mi_dynproc_bank_t *bank, void *stream);
+int mi_dynproc_bank_clear(mi_dynproc_bank_t *bank, void *stream);
+int mi_dynproc_bank_get_params(const mi_dynproc_bank_t *bank, uint32_t channel, mi_dynproc_params_t *params);
+int mi_dynproc_bank_get_state(mi_dynproc_bank_t *bank, uint32_t channel, float *envelope, float *peak, uint32_t *hold,
+                              void *stream);
+/* process(out, env, in, samples), :397-442; gain or env may be the input rows (same stride); gain and env differ */
+int mi_dynproc_bank_process(mi_dynproc_bank_t *bank, float *gain, float *env, const float *in, size_t count,
+                            size_t gain_stride, size_t env_stride, size_t in_stride, void *stream);
+/* dst = audio * gain(sc) in the same launch; dst may be audio or sc (same stride) */
+int mi_dynproc_bank_process_apply(mi_dynproc_bank_t *bank, float *dst, const float *audio, const float *sc, size_t count,
+                                  size_t dst_stride, size_t audio_stride, size_t sc_stride, void *stream);
+/* curve(out, in, dots), :474-496, and model(out, in, dots), :518-540 (the curve without its knees: spline_model, :185-193):
+ * out = gain(|in|) |in| with |in| limited to [1e-10, 1e10], stateless; update_settings() first */
+int mi_dynproc_bank_curve(mi_dynproc_bank_t *bank, float *out, const float *in, size_t dots, size_t out_stride,
+                          size_t in_stride, void *stream);
+int mi_dynproc_bank_model(mi_dynproc_bank_t *bank, float *out, const float *in, size_t dots, size_t out_stride,
+                          size_t in_stride, void *stream);
+
 /* ---- sidechain bank (source selection, pre-amplification and the peak / RMS / low-pass / uniform detectors) ------------- */
 /*
  * mi_sidechain_bank: `channels` x lsp::dspu::Sidechain (util/Sidechain.h:59-205, src/main/util/Sidechain.cpp), every channel

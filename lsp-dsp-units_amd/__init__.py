@@ -12,7 +12,7 @@ Import with ``importlib.import_module("lsp-dsp-units_amd")`` (the directory
 name carries the reference's name and is not a Python identifier).
 """
 from .capi import LIB_PATH, MiError, check, lib          # noqa: F401
-from .units import (AnalyzerBank, BiquadBank, Comm, CompressorBank, ConvolverBank, CrossoverBank, DelayBank, DeviceBuffer, DynFilterBank, EqualizerBank,  # noqa: F401
+from .units import (AnalyzerBank, BiquadBank, Comm, CompressorBank, ConvolverBank, CrossoverBank, DelayBank, DeviceBuffer, DynFilterBank, DynamicProcessorBank, EqualizerBank,  # noqa: F401
                     ExpanderBank, GateBank, ILUFSBank, LoudnessBank, OversamplerBank,
                     RingBank, SidechainBank,
                     SpectralBank, SplitterBank, TruePeakBank, crossover_fft_mask,

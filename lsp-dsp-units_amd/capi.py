@@ -85,6 +85,35 @@ class GateSettings(ctypes.Structure):
                 ("attack", c_float), ("release", c_float), ("hold", c_float)]
 
 
+class DynprocDot(ctypes.Structure):
+    """mi_dynproc_dot_t == dyndot_t layout."""
+    _fields_ = [("input", c_float), ("output", c_float), ("knee", c_float)]
+
+
+class DynprocSpline(ctypes.Structure):
+    """mi_dynproc_spline_t == DynamicProcessor::spline_t layout."""
+    _fields_ = [(n, c_float) for n in ("pre_ratio", "post_ratio", "knee_start", "knee_stop", "thresh", "makeup")] + \
+               [("herm", c_float * 4)]
+
+
+class DynprocReaction(ctypes.Structure):
+    """mi_dynproc_reaction_t == DynamicProcessor::reaction_t layout."""
+    _fields_ = [("level", c_float), ("tau", c_float)]
+
+
+class DynprocParams(ctypes.Structure):
+    """mi_dynproc_params_t: what DynamicProcessor::update_settings computes."""
+    _fields_ = [("splines", c_uint32), ("attacks", c_uint32), ("releases", c_uint32), ("hold", c_uint32),
+                ("attack", DynprocReaction * 5), ("release", DynprocReaction * 5), ("spline", DynprocSpline * 4)]
+
+
+class DynprocSettings(ctypes.Structure):
+    """mi_dynproc_settings_t: the values of DynamicProcessor's setters."""
+    _fields_ = [("sample_rate", c_uint32), ("hold", c_float), ("in_ratio", c_float), ("out_ratio", c_float),
+                ("dot", DynprocDot * 4), ("attack_level", c_float * 4), ("release_level", c_float * 4),
+                ("attack_time", c_float * 5), ("release_time", c_float * 5)]
+
+
 class SidechainParams(ctypes.Structure):
     """mi_sidechain_params_t: what Sidechain::update_settings and set_sample_rate compute, and the settings beside them."""
     _fields_ = [("reactivity", c_uint32), ("tau", c_float), ("interval", c_float), ("capacity", c_uint32), ("mode", c_uint32),
@@ -317,6 +346,26 @@ PROTOTYPES = {
     "mi_gate_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_gate_bank_process_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_gate_bank_curve": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_size_t, c_size_t, c_void_p]),
+    "mi_dynproc_compute_params": (c_int, [POINTER(DynprocSettings), POINTER(DynprocParams)]),
+    "mi_dynproc_bank_create": (c_int, [POINTER(c_void_p), c_uint32]),
+    "mi_dynproc_bank_destroy": (c_int, [c_void_p]),
+    "mi_dynproc_bank_set_sample_rate": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_dynproc_bank_set_in_ratio": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_dynproc_bank_set_out_ratio": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_dynproc_bank_set_dot": (c_int, [c_void_p, c_uint32, c_uint32, POINTER(DynprocDot)]),
+    "mi_dynproc_bank_set_attack_level": (c_int, [c_void_p, c_uint32, c_uint32, c_float]),
+    "mi_dynproc_bank_set_release_level": (c_int, [c_void_p, c_uint32, c_uint32, c_float]),
+    "mi_dynproc_bank_set_attack_time": (c_int, [c_void_p, c_uint32, c_uint32, c_float]),
+    "mi_dynproc_bank_set_release_time": (c_int, [c_void_p, c_uint32, c_uint32, c_float]),
+    "mi_dynproc_bank_set_hold": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_dynproc_bank_update_settings": (c_int, [c_void_p, c_void_p]),
+    "mi_dynproc_bank_clear": (c_int, [c_void_p, c_void_p]),
+    "mi_dynproc_bank_get_params": (c_int, [c_void_p, c_uint32, POINTER(DynprocParams)]),
+    "mi_dynproc_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(c_float), POINTER(c_float), POINTER(c_uint32), c_void_p]),
+    "mi_dynproc_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_dynproc_bank_process_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_dynproc_bank_curve": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_dynproc_bank_model": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_sidechain_compute_params": (c_int, [c_uint32, c_float, c_float, POINTER(SidechainParams)]),
     "mi_sidechain_bank_create": (c_int, [POINTER(c_void_p), c_uint32, c_uint32, c_float]),
     "mi_sidechain_bank_destroy": (c_int, [c_void_p]),

@@ -1098,6 +1098,111 @@ class GateBank(_DynamicsBank):
                                      _stream(stream)))
 
 
+def _dynproc_dict(p):
+    """Entries [0, count) of the three tables, float32."""
+    return {"hold": p.hold,
+            "attack": [{"level": np.float32(r.level), "tau": np.float32(r.tau)} for r in p.attack[:p.attacks]],
+            "release": [{"level": np.float32(r.level), "tau": np.float32(r.tau)} for r in p.release[:p.releases]],
+            "splines": [dict([(n, np.float32(getattr(s, n))) for n in ("pre_ratio", "post_ratio", "knee_start", "knee_stop",
+                                                                       "thresh", "makeup")] +
+                             [("herm", np.array(s.herm[:], np.float32))]) for s in p.spline[:p.splines]]}
+
+
+class DynamicProcessorBank(_DynamicsBank):
+    """`channels` x lsp::dspu::DynamicProcessor (mi_dynproc_bank_*): envelope follower whose attack and release times depend
+    on the level of the envelope, and a gain curve through up to four dots with a knee each; every channel with settings of
+    its own.  A fresh channel has four dots at (0, 0, 0) that cannot be evaluated: configure() sets all of them."""
+    UNIT = "dynproc"
+    DOTS, RANGES = 4, 5
+    set_timings = None                      # the reference has none: times are per range, set_attack_time / set_release_time
+
+    @staticmethod
+    def _settings(sample_rate=0, hold=0.0, in_ratio=1.0, out_ratio=1.0, dots=(), attack_levels=(), release_levels=(),
+                  attack_times=(0.0,), release_times=(0.0,)):
+        """dots: up to four (input, output, knee) or None (off); levels: up to four, None or negative is off; times: up to
+        five in ms, [0] the default, [i + 1] from level i on.  What is not given is off (dots, levels) or 0 (times)."""
+        from .capi import DynprocDot, DynprocSettings
+        pad = lambda v, n, fill: [fill if x is None else x for x in list(v)] + [fill] * (n - len(v))
+        s = DynprocSettings(sample_rate, hold, in_ratio, out_ratio)
+        for i, d in enumerate(pad(dots, 4, (-1.0, -1.0, -1.0))):
+            s.dot[i] = DynprocDot(*d)
+        s.attack_level[:] = pad(attack_levels, 4, -1.0)
+        s.release_level[:] = pad(release_levels, 4, -1.0)
+        s.attack_time[:] = pad(attack_times, 5, 0.0)
+        s.release_time[:] = pad(release_times, 5, 0.0)
+        return s
+
+    @classmethod
+    def compute_params(cls, **settings):
+        """update_settings() of one processor on the host (mi_dynproc_compute_params): no device needed.  Keywords as
+        configure()."""
+        from .capi import DynprocParams
+        s, p = cls._settings(**settings), DynprocParams()
+        check(lib.mi_dynproc_compute_params(byref(s), byref(p)))
+        return _dynproc_dict(p)
+
+    def set_in_ratio(self, channel, ratio):
+        check(lib.mi_dynproc_bank_set_in_ratio(self.handle, channel, ratio))
+
+    def set_out_ratio(self, channel, ratio):
+        check(lib.mi_dynproc_bank_set_out_ratio(self.handle, channel, ratio))
+
+    def set_dot(self, channel, id, dot):
+        """dot: (input, output, knee), or None to switch it off."""
+        from .capi import DynprocDot
+        check(lib.mi_dynproc_bank_set_dot(self.handle, channel, id, None if dot is None else byref(DynprocDot(*dot))))
+
+    def set_attack_level(self, channel, id, level):
+        check(lib.mi_dynproc_bank_set_attack_level(self.handle, channel, id, level))
+
+    def set_release_level(self, channel, id, level):
+        check(lib.mi_dynproc_bank_set_release_level(self.handle, channel, id, level))
+
+    def set_attack_time(self, channel, id, time):
+        check(lib.mi_dynproc_bank_set_attack_time(self.handle, channel, id, time))
+
+    def set_release_time(self, channel, id, time):
+        check(lib.mi_dynproc_bank_set_release_time(self.handle, channel, id, time))
+
+    def configure(self, channel, **settings):
+        """Every setter of one channel; keywords as _settings()."""
+        s = self._settings(**settings)
+        self.set_sample_rate(channel, s.sample_rate)
+        self.set_hold(channel, s.hold)
+        self.set_in_ratio(channel, s.in_ratio)
+        self.set_out_ratio(channel, s.out_ratio)
+        for i in range(self.DOTS):
+            d = s.dot[i]
+            self.set_dot(channel, i, None if d.input < 0 and d.output < 0 and d.knee < 0 else (d.input, d.output, d.knee))
+            self.set_attack_level(channel, i, s.attack_level[i])
+            self.set_release_level(channel, i, s.release_level[i])
+        for i in range(self.RANGES):
+            self.set_attack_time(channel, i, s.attack_time[i])
+            self.set_release_time(channel, i, s.release_time[i])
+
+    def get_params(self, channel):
+        from .capi import DynprocParams
+        p = DynprocParams()
+        check(lib.mi_dynproc_bank_get_params(self.handle, channel, byref(p)))
+        return _dynproc_dict(p)
+
+    def get_state(self, channel, stream=None):
+        """(fEnvelope, fPeak, nHoldCounter) of the channel; the envelope and the peak as numpy float32."""
+        e, p, h = c_float(), c_float(), c_uint32()
+        check(lib.mi_dynproc_bank_get_state(self.handle, channel, byref(e), byref(p), byref(h), _stream(stream)))
+        return np.float32(e.value), np.float32(p.value), h.value
+
+    def curve(self, out, inp, dots, out_stride=None, in_stride=None, stream=None):
+        """curve(out, in, dots) of every channel: out = gain(|in|) |in|."""
+        check(lib.mi_dynproc_bank_curve(self.handle, _ptr(out), _ptr(inp), dots, dots if out_stride is None else out_stride,
+                                        dots if in_stride is None else in_stride, _stream(stream)))
+
+    def model(self, out, inp, dots, out_stride=None, in_stride=None, stream=None):
+        """model(out, in, dots) of every channel: the curve without its knees."""
+        check(lib.mi_dynproc_bank_model(self.handle, _ptr(out), _ptr(inp), dots, dots if out_stride is None else out_stride,
+                                        dots if in_stride is None else in_stride, _stream(stream)))
+
+
 def _sidechain_dict(p):
     return {"reactivity": p.reactivity, "tau": np.float32(p.tau), "interval": np.float32(p.interval), "capacity": p.capacity,
             "mode": p.mode, "source": p.source, "flags": p.flags, "gain": np.float32(p.gain)}
