@@ -205,14 +205,32 @@ namespace mi
     }
 
     // One element of a bank's device state, to and from the host, synchronised: the host's copy may go away after either.
+    // Not on a stream that is being captured: synchronising is not allowed there and would end the capture behind the
+    // caller's back, so both ask first and refuse.
+    inline int refuse_state_access(hipStream_t st)
+    {
+        bool cap = false;
+        const int r = capturing(st, &cap);
+        if (r != MI_OK)
+            return r;
+        MI_REQUIRE(!cap, MI_ESTATE, "a bank's state is read and written with a synchronised copy; get_state() / set_state() cannot "
+                                    "be called on a stream that is being captured");
+        return MI_OK;
+    }
     template <class S> int read_state(S *host, const S *dev, hipStream_t st)
     {
+        const int r = refuse_state_access(st);
+        if (r != MI_OK)
+            return r;
         MI_HIP_CHECK(hipMemcpyAsync(host, dev, sizeof(S), hipMemcpyDeviceToHost, st));
         MI_HIP_CHECK(hipStreamSynchronize(st));
         return MI_OK;
     }
     template <class S> int write_state(S *dev, const S &host, hipStream_t st)
     {
+        const int r = refuse_state_access(st);
+        if (r != MI_OK)
+            return r;
         MI_HIP_CHECK(hipMemcpyAsync(dev, &host, sizeof(S), hipMemcpyHostToDevice, st));
         MI_HIP_CHECK(hipStreamSynchronize(st));
         return MI_OK;

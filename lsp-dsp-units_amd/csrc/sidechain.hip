@@ -518,7 +518,9 @@ namespace mi
                                  bool zero_ring, hipStream_t st)
     {
         MI_REQUIRE(b != nullptr && channel < b->channels, MI_EINVAL, "sidechain_bank_set_state: bad argument");
-        const int r = sc_update(b, st);
+        int r = mi::refuse_state_access(st);                        // before the ring's memset below could go into a capture
+        if (r == MI_OK)
+            r = sc_update(b, st);
         if (r != MI_OK)
             return r;
         const device_state s = { rms_value, (refresh < REFRESH_RATE) ? refresh : REFRESH_RATE, position % b->params[channel].capacity, 0 };

@@ -1,6 +1,9 @@
 """Every entry point of every bank called on a live bank with zeros / NULL for all other arguments: MI_OK or a negative
 code, never a crash; the bank can still be destroyed.  Child process, so that a crash is reported by name."""
+import ctypes
+import importlib
 import os
+import re
 import subprocess
 import sys
 
@@ -28,6 +31,14 @@ banks = {
     "mi_splitter_bank_": lambda: gpu.SplitterBank(C, 10, 2),
     "mi_crossover_bank_": lambda: gpu.CrossoverBank(C, 3),
     "mi_equalizer_bank_": lambda: gpu.EqualizerBank(C, 4, 9),
+    "mi_dynfilter_bank_": lambda: gpu.DynFilterBank(C, 2),
+    "mi_truepeak_bank_": lambda: gpu.TruePeakBank(C),
+    "mi_oversampler_bank_": lambda: gpu.OversamplerBank(C),
+    "mi_compressor_bank_": lambda: gpu.CompressorBank(C),
+    "mi_sidechain_bank_": lambda: gpu.SidechainBank(C),
+    "mi_expander_bank_": lambda: gpu.ExpanderBank(C),
+    "mi_gate_bank_": lambda: gpu.GateBank(C),
+    "mi_dynproc_bank_": lambda: gpu.DynamicProcessorBank(C),
 }
 bad, n = [], 0
 for prefix, make in banks.items():
@@ -57,5 +68,13 @@ sys.exit(1 if bad else 0)
 def test_zero_arguments_on_live_banks_never_crash(gpu):
     r = subprocess.run([sys.executable, "-c", CHILD % ROOT], capture_output=True, text=True, timeout=900)
     calls = [ln.split()[1] for ln in r.stdout.splitlines() if ln.startswith("CALL")]
-    assert len(calls) > 80, (r.stdout[-2000:], r.stderr[-2000:])
     assert r.returncode == 0, "last call: %s\n%s\n%s" % (calls[-1] if calls else None, r.stdout[-1500:], r.stderr[-1500:])
+    # every prefix of the child's table made a call, and every entry point the table makes eligible was called once
+    prefixes = re.findall(r'"(mi_[a-z]+_bank_)": lambda', CHILD)
+    assert len(set(prefixes)) == len(prefixes) >= 19
+    capi = importlib.import_module("lsp-dsp-units_amd.capi")
+    eligible = [name for name, (res, _) in capi.PROTOTYPES.items()
+                if name.startswith(tuple(prefixes)) and not name.endswith(("_create", "_destroy")) and res is ctypes.c_int]
+    for p in prefixes:
+        assert any(c.startswith(p) for c in calls), p
+    assert sorted(calls) == sorted(eligible), (len(calls), len(eligible), sorted(set(eligible) ^ set(calls)))

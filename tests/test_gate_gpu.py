@@ -499,3 +499,80 @@ def test_graph_capture_replays_direct_calls(gpu):
     bank.close()
     twin.close()
     gpu.check(gpu.lib.mi_dspu_stream_destroy(st))
+
+
+@pytest.mark.gpu
+def test_changed_setting_inside_a_capture_is_refused(gpu):
+    """A setter leaves an upload to the next call.  On a capturing stream that call -- process() or update_settings() -- answers
+    MI_ESTATE and names update_settings(), changes nothing on the device and leaves the capture valid; the next eager process()
+    applies the setting to the state from before the capture."""
+    C, n = 5, T + 100
+    st = ctypes.c_void_p()
+    gpu.check(gpu.lib.mi_dspu_stream_create(ctypes.byref(st)))
+    bank, params = _bank(gpu, C)
+    state = gr.fresh_state(C)
+    x0, x1 = gr.bursts(80, C, n), gr.bursts(81, C, n)
+    d0, d1 = gpu.DeviceBuffer.from_host(x0), gpu.DeviceBuffer.from_host(x1)
+    dg, de = gpu.DeviceBuffer((C, n)), gpu.DeviceBuffer((C, n))
+    bank.process(dg, de, d0, n, stream=st.value)
+    env0 = de.download(stream=st.value)
+    assert _bits_equal(env0, _follow(x0, state, params)[0])
+    before = _state(bank, C)
+    gpu.check(gpu.lib.mi_dspu_graph_begin_capture(st))
+    bank.set_threshold(0, 0.2, 0.08)
+    bank.set_timings(3, 0.3, 0.12)
+    for call in (lambda: bank.process(dg, de, d1, n, stream=st.value), lambda: bank.update_settings(stream=st.value)):
+        with pytest.raises(gpu.MiError) as e:
+            call()
+        assert e.value.code == -5 and "update_settings" in str(e.value)
+    gpu.check(gpu.lib.mi_dspu_memset(ctypes.c_void_p(dg.ptr), 0, 16, st))          # (so that the capture is not empty)
+    exe = ctypes.c_void_p()
+    gpu.check(gpu.lib.mi_dspu_graph_end_capture(st, ctypes.byref(exe)))             # ends and instantiates normally
+    assert exe.value
+    gpu.lib.mi_dspu_graph_destroy(exe)
+    # nothing changed on the device: the state, and the envelope rows no refused call wrote to
+    assert _same_state(_state(bank, C), before) and _same_state(before, state)
+    assert _bits_equal(de.download(stream=st.value), env0)
+    bank.process(dg, de, d1, n, stream=st.value)
+    new = [bank.get_params(ch) for ch in range(C)]
+    assert new[0]["k"][0]["end"] != params[0]["k"][0]["end"] and new[3]["tau_attack"] != params[3]["tau_attack"]
+    want, which = _follow(x1, state, new)                                               # the state carried over, the new parameters apply
+    assert _bits_equal(de.download(stream=st.value), want)
+    assert _same_state(_state(bank, C), state)
+    _check_gain(dg.download(stream=st.value), want, which, new, "after the refused capture")
+    bank.close()
+    gpu.check(gpu.lib.mi_dspu_stream_destroy(st))
+
+
+@pytest.mark.gpu
+def test_state_access_inside_a_capture_is_refused(gpu):
+    """get_state() ends in a synchronisation, which a capturing stream does not allow: it answers MI_ESTATE with a message and
+    leaves the capture valid -- a process() captured after it replays three times with the bits of an eager twin."""
+    C, n = 5, T + 100
+    st = ctypes.c_void_p()
+    gpu.check(gpu.lib.mi_dspu_stream_create(ctypes.byref(st)))
+    bank, params = _bank(gpu, C)
+    twin, _ = _bank(gpu, C)
+    x = gr.bursts(82, C, n)
+    d = gpu.DeviceBuffer.from_host(x)
+    g, e, tg, te = (gpu.DeviceBuffer((C, n)) for _ in range(4))
+    gpu.check(gpu.lib.mi_dspu_graph_begin_capture(st))
+    with pytest.raises(gpu.MiError) as err:
+        bank.get_state(2, stream=st.value)
+    assert err.value.code == -5 and "captured" in str(err.value)
+    bank.process(g, e, d, n, stream=st.value)
+    exe = ctypes.c_void_p()
+    gpu.check(gpu.lib.mi_dspu_graph_end_capture(st, ctypes.byref(exe)))
+    ref = gr.fresh_state(C)
+    for rep in range(3):
+        gpu.check(gpu.lib.mi_dspu_graph_launch(exe, st))
+        twin.process(tg, te, d, n, stream=st.value)
+        got = [b.download(stream=st.value) for b in (g, e)]
+        direct = [b.download(stream=st.value) for b in (tg, te)]
+        assert all(_bits_equal(a, b) for a, b in zip(got, direct)), rep
+        assert _bits_equal(got[1], _follow(x, ref, params)[0]), rep                # the state advances on every replay
+    assert _same_state(_state(bank, C), ref)                                        # ... and can be read again after the capture
+    gpu.lib.mi_dspu_graph_destroy(exe)
+    bank.close()
+    twin.close()
+    gpu.check(gpu.lib.mi_dspu_stream_destroy(st))

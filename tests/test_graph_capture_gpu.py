@@ -19,10 +19,11 @@ pytestmark = pytest.mark.gpu
 
 
 class Case:
-    """make() -> bank; call(bank, d_in, d_outs, n, stream); in_shape / out_shapes for one call."""
-    def __init__(self, name, make, call, in_shape, out_shapes, min_period=1):
+    """make() -> bank; call(bank, d_in, d_outs, n, stream); in_shape / out_shapes for one call; prep(x) -> x shapes a call's
+    random input on the host where not all of it is signal."""
+    def __init__(self, name, make, call, in_shape, out_shapes, min_period=1, prep=None):
         self.name, self.make, self.call = name, make, call
-        self.in_shape, self.out_shapes, self.min_period = in_shape, out_shapes, min_period
+        self.in_shape, self.out_shapes, self.min_period, self.prep = in_shape, out_shapes, min_period, prep
 
 
 def _stream():
@@ -37,6 +38,8 @@ def _run(gpu, case, max_k=12, replays=3, seed=77):
     st = s.value
     rng = np.random.default_rng(seed)
     xs = [(rng.standard_normal(case.in_shape) * 0.25).astype(np.float32) for _ in range(max_k)]
+    if case.prep is not None:
+        xs = [case.prep(x) for x in xs]
     refused = []
     accepted = None
     for K in range(1, max_k + 1):
@@ -229,6 +232,71 @@ def test_banks_without_positions_replay_any_run(gpu):
 
     K = _run(gpu, Case("crossover", make_xo, lambda b, x, o, st: b.process(o, x, n, stream=st), (C, n), [(C, n)] * 3))
     assert K == 1
+
+    # dynamic filters: two filters in series; the input's rows C .. 2C - 1 are the per-sample gain of both (0.1 .. 10)
+    def make_df(st):
+        df = gpu.DynFilterBank(C, 2)
+        df.set_sample_rate(48000)
+        df.set_params(0, fd.FLT_BT_RLC_BELL, 2, 1200.0, 5000.0, 1.0, 0.6)
+        df.set_params(1, fd.FLT_BT_BWC_LOPASS, 2, 3000.0, 3000.0, 1.0, 0.6)
+        df.set_filter_active(0); df.set_filter_active(1)
+        return df
+
+    def call_df(b, x, o, st):
+        gain = x.ptr + C * n * 4
+        b.process(0, o[0], x.ptr, gain, n, stream=st)
+        b.process(1, o[1], o[0], gain, n, stream=st)
+
+    def gain_rows(x):
+        x[C:] = np.exp(np.clip(4.0 * x[C:], -2.3, 2.3))
+        return x
+
+    K = _run(gpu, Case("dynamic filters", make_df, call_df, (2 * C, n), [(C, n)] * 2, prep=gain_rows))
+    assert K == 1
+
+
+def test_dynamic_filters_pending_clear_is_refused_under_capture(gpu):
+    """A fresh bank's first process() clears every filter's memory; captured, that memset would run again at every replay, so
+    process() answers MI_ESTATE on a capturing stream until one eager call has been made."""
+    C, n = 8, 4096
+    st = ctypes.c_void_p()
+    gpu.check(gpu.lib.mi_dspu_stream_create(ctypes.byref(st)))
+    bank = gpu.DynFilterBank(C, 2)
+    bank.set_sample_rate(48000)
+    bank.set_params(0, fd.FLT_BT_RLC_BELL, 2, 1200.0, 5000.0, 1.0, 0.6)
+    bank.set_filter_active(0)
+    rng = np.random.default_rng(78)
+    x = gpu.DeviceBuffer.from_host((rng.standard_normal((C, n)) * 0.25).astype(np.float32))
+    g = gpu.DeviceBuffer.from_host(np.exp(rng.uniform(-1.0, 1.0, (C, n))).astype(np.float32))
+    y, t = gpu.DeviceBuffer((C, n)), gpu.DeviceBuffer((C, n))
+    gpu.check(gpu.lib.mi_dspu_graph_begin_capture(st))
+    with pytest.raises(gpu.MiError) as e:
+        bank.process(0, y, x, g, n, stream=st.value)
+    assert e.value.code == -5 and "eager call" in str(e.value)
+    gpu.check(gpu.lib.mi_dspu_memset(ctypes.c_void_p(y.ptr), 0, 16, st))           # (so that the capture is not empty)
+    exe = ctypes.c_void_p()
+    gpu.check(gpu.lib.mi_dspu_graph_end_capture(st, ctypes.byref(exe)))
+    gpu.lib.mi_dspu_graph_destroy(exe)
+    bank.process(0, y, x, g, n, stream=st.value)                                    # the eager call: the clear happens here
+    first = y.download(stream=st.value)
+    gpu.check(gpu.lib.mi_dspu_graph_begin_capture(st))
+    bank.process(0, y, x, g, n, stream=st.value)                                    # accepted now
+    gpu.check(gpu.lib.mi_dspu_graph_end_capture(st, ctypes.byref(exe)))
+    twin = gpu.DynFilterBank(C, 2)
+    twin.set_sample_rate(48000)
+    twin.set_params(0, fd.FLT_BT_RLC_BELL, 2, 1200.0, 5000.0, 1.0, 0.6)
+    twin.set_filter_active(0)
+    twin.process(0, t, x, g, n, stream=st.value)
+    np.testing.assert_array_equal(first, t.download(stream=st.value))               # the refused call left the memory alone
+    assert np.isfinite(first).all() and np.abs(first).max() > 0.0
+    for rep in range(2):
+        gpu.check(gpu.lib.mi_dspu_graph_launch(exe, st))
+        twin.process(0, t, x, g, n, stream=st.value)
+        np.testing.assert_array_equal(y.download(stream=st.value), t.download(stream=st.value), err_msg="replay %d" % rep)
+    gpu.lib.mi_dspu_graph_destroy(exe)
+    bank.close()
+    twin.close()
+    gpu.check(gpu.lib.mi_dspu_stream_destroy(st))
 
 
 def test_capture_behind_the_librarys_back_is_refused(gpu):

@@ -3,6 +3,10 @@ import numpy as np
 import pytest
 
 from oracle import filter_design as fd
+import compressor_ref as cr
+import dynproc_ref as dr
+import expander_ref as er
+import gate_ref as gr
 import workloads as wl
 
 pytestmark = pytest.mark.gpu
@@ -56,6 +60,30 @@ def _cycle(gpu, kind):
         for i, f in enumerate((500.0, 4000.0)):
             b.set_slope(i, 2); b.set_frequency(i, f)
         b.process([y, gpu.DeviceBuffer((C, n)), gpu.DeviceBuffer((C, n))], x, n)
+    elif kind == "dynfilter":
+        b = gpu.DynFilterBank(C, 2); b.set_sample_rate(48000)
+        b.set_params(1, fd.FLT_BT_RLC_BELL, 2, 1200.0, 5000.0, 1.0, 0.6); b.set_filter_active(1)
+        b.process(1, y, x, gpu.DeviceBuffer.from_host(np.full((C, n), 1.5, np.float32)), n)
+    elif kind == "truepeak":
+        b = gpu.TruePeakBank(C); b.set_sample_rate(48000)       # few enough rows for the bank to own a halo buffer
+        b.process(y, x, n); b.process_max(gpu.DeviceBuffer((C,)), x, n)
+    elif kind == "oversampler":
+        b = gpu.OversamplerBank(C); b.set_mode(b.MODES["8X16BIT"]); b.set_sample_rate(48000); b.update_settings()
+        b.process(y, x, n)                                      # no reserve(): the scratch grows inside the call
+    elif kind in ("compressor", "expander", "gate", "dynproc"):
+        cls, settings = {"compressor": (gpu.CompressorBank, cr.channel_settings), "expander": (gpu.ExpanderBank, er.channel_settings),
+                         "gate": (gpu.GateBank, gr.channel_settings), "dynproc": (gpu.DynamicProcessorBank, dr.channel_settings)}[kind]
+        b = cls(C)
+        for c in range(C):
+            b.configure(c, **settings(c))
+        b.process(y, gpu.DeviceBuffer((C, n)), x, n)
+    elif kind == "sidechain":
+        b = gpu.SidechainBank(C, 1, 2000.0)                     # rings of 2 s: 3 MiB for the bank, so a ring that stays shows
+        for c in range(C):
+            b.configure(c, 48000, 5.0 + c, b.SCM_RMS)
+        b.process(y, x, None, n)
+        b.set_sample_rate(0, 96000); b.set_reactivity(0, 20.0)  # a longer ring: all rings are re-made, the old ones freed
+        b.process(y, x, None, n)
     else:
         b = gpu.EqualizerBank(C, 4, 10); b.set_mode(2); b.set_sample_rate(48000)
         for c in range(C):
@@ -65,7 +93,8 @@ def _cycle(gpu, kind):
 
 
 @pytest.mark.parametrize("kind", ["biquad", "convolver", "spectral", "analyzer", "delay", "ring", "loudness", "ilufs",
-                                  "splitter", "crossover", "equalizer"])
+                                  "splitter", "crossover", "equalizer", "dynfilter", "truepeak", "oversampler", "compressor",
+                                  "sidechain", "expander", "gate", "dynproc"])
 def test_create_use_destroy_returns_device_memory(gpu, kind):
     for _ in range(3):                      # first objects: code objects, allocator pools, the shared twiddle table
         _cycle(gpu, kind)

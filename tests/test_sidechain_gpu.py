@@ -347,6 +347,84 @@ def test_graph_capture_replays_direct_calls(gpu):
 
 
 @pytest.mark.gpu
+def test_changed_setting_inside_a_capture_is_refused(gpu):
+    """A setter leaves work to the next call.  On a capturing stream that call -- process() or update_settings() -- answers
+    MI_ESTATE and names update_settings(), changes nothing on the device and leaves the capture valid; the next eager process()
+    applies the setting to the ring and the state from before the capture."""
+    C, n = 5, T + 100
+    st = ctypes.c_void_p()
+    gpu.check(gpu.lib.mi_dspu_stream_create(ctypes.byref(st)))
+    bank, params, ref = _bank(gpu, [_settings(ch) for ch in range(C)])
+    x0, x1 = _signal(80, C, n), _signal(81, C, n)
+    d0, d1 = gpu.DeviceBuffer.from_host(x0), gpu.DeviceBuffer.from_host(x1)
+    out = gpu.DeviceBuffer((C, n))
+    bank.process(out, d0, None, n, stream=st.value)
+    out0 = out.download(stream=st.value)
+    assert _bits_equal(out0, ref.process(x0)[0])
+    before = _state(bank)
+    gpu.check(gpu.lib.mi_dspu_graph_begin_capture(st))
+    bank.set_reactivity(0, _ms(100))
+    bank.set_gain(1, -0.75)
+    bank.set_mode(2, sr.SCM_UNIFORM)
+    for call in (lambda: bank.process(out, d1, None, n, stream=st.value), lambda: bank.update_settings(stream=st.value)):
+        with pytest.raises(gpu.MiError) as e:
+            call()
+        assert e.value.code == -5 and "update_settings" in str(e.value)
+    gpu.check(gpu.lib.mi_dspu_memset(ctypes.c_void_p(out.ptr), 0, 16, st))         # (so that the capture is not empty)
+    exe = ctypes.c_void_p()
+    gpu.check(gpu.lib.mi_dspu_graph_end_capture(st, ctypes.byref(exe)))             # ends and instantiates normally
+    assert exe.value
+    gpu.lib.mi_dspu_graph_destroy(exe)
+    # nothing changed on the device: the state, and the rows no refused call wrote to
+    after = _state(bank)
+    assert all(np.array_equal(after[k], before[k]) for k in before) and _same_state(bank, ref)
+    assert _bits_equal(out.download(stream=st.value), out0)
+    bank.process(out, d1, None, n, stream=st.value)
+    new = [bank.get_params(ch) for ch in range(C)]
+    assert new[0]["reactivity"] == 100 != params[0]["reactivity"] and new[1]["gain"] == f32(-0.75)
+    assert new[2]["mode"] == sr.SCM_UNIFORM != params[2]["mode"]
+    ref.set_mode(2, sr.SCM_UNIFORM)
+    ref.set_params(new)
+    ref.updated(0)
+    assert _bits_equal(out.download(stream=st.value), ref.process(x1)[0])           # the ring and the state carried over
+    assert _same_state(bank, ref)
+    bank.close()
+    gpu.check(gpu.lib.mi_dspu_stream_destroy(st))
+
+
+@pytest.mark.gpu
+def test_state_access_inside_a_capture_is_refused(gpu):
+    """get_state() ends in a synchronisation, which a capturing stream does not allow: it answers MI_ESTATE with a message and
+    leaves the capture valid -- a process() captured after it replays three times with the bits of an eager twin."""
+    C, n = 5, T + 100
+    st = ctypes.c_void_p()
+    gpu.check(gpu.lib.mi_dspu_stream_create(ctypes.byref(st)))
+    settings = [_settings(ch) for ch in range(C)]
+    bank, params, ref = _bank(gpu, settings)
+    twin, _, _ = _bank(gpu, settings)
+    x = _signal(82, C, n)
+    d = gpu.DeviceBuffer.from_host(x)
+    o, t = gpu.DeviceBuffer((C, n)), gpu.DeviceBuffer((C, n))
+    gpu.check(gpu.lib.mi_dspu_graph_begin_capture(st))
+    with pytest.raises(gpu.MiError) as err:
+        bank.get_state(2, stream=st.value)
+    assert err.value.code == -5 and "captured" in str(err.value)
+    bank.process(o, d, None, n, stream=st.value)
+    exe = ctypes.c_void_p()
+    gpu.check(gpu.lib.mi_dspu_graph_end_capture(st, ctypes.byref(exe)))
+    for rep in range(3):
+        gpu.check(gpu.lib.mi_dspu_graph_launch(exe, st))
+        twin.process(t, d, None, n, stream=st.value)
+        got, direct = o.download(stream=st.value), t.download(stream=st.value)
+        assert _bits_equal(got, direct) and _bits_equal(got, ref.process(x)[0]), rep    # the state advances on every replay
+    assert _same_state(bank, ref)                                                   # ... and can be read again after the capture
+    gpu.lib.mi_dspu_graph_destroy(exe)
+    bank.close()
+    twin.close()
+    gpu.check(gpu.lib.mi_dspu_stream_destroy(st))
+
+
+@pytest.mark.gpu
 def test_sidechain_feeds_the_compressor_on_the_device(gpu):
     C, n = G + 1, 3 * T + 7
     bank, params, ref = _bank(gpu, [_settings(ch, mode=(sr.SCM_RMS, sr.SCM_LPF, sr.SCM_PEAK, sr.SCM_UNIFORM)[ch % 4], n=48) for ch in range(C)])
