@@ -6,12 +6,20 @@ designer in filter_design.py).  Only tests/, __graft_entry__.smoke() and the
 cpu_baseline leg of bench.py may import this package; the product
 (lsp-dsp-units_amd/) never does.
 
-The reference itself cannot be built in this environment: its arithmetic core
+The reference as a whole cannot be built in this environment: its arithmetic core
 (lsp-dsp-lib 1.0.36) and lsp-common-lib/lsp-runtime-lib/lsp-lltl-lib/lsp-test-fw
-are un-vendored (modules.mk:23-51, fetched by `make fetch`) and absent, so there
-is no oracle/_ref build.  Each restated function cites the reference file:line
-it follows and is pinned against the reference's own unit-test expectations
-(tests/test_oracle_*.py).
+are un-vendored (modules.mk:23-51, fetched by `make fetch`) and absent.  Each
+restated function cites the reference file:line it follows and is pinned against
+the reference's own unit-test expectations (tests/test_oracle_*.py).
+
+Four classes are built from the reference's own text, because their logic lives
+in their .cpp files and not in the absent libraries: Compressor, Expander, Gate
+and DynamicProcessor (Makefile -> _ref/dyn_ref, with the stand-in headers of
+ref_shim/ and the driver dyn_driver.cpp; _ref/ is never committed).  That pins
+their followers, hold, hysteresis, update_settings and scalar gain formulas
+(tests/golden/dynamics_ref_vectors.npz, tests/test_dynamics_reference_*.py).
+It does not pin lsp-dsp-lib's array primitives or their SIMD variants, the
+Sidechain's detectors, the Lanczos tables or the IIR streaming arithmetic.
 """
 from .binding import *  # noqa: F401,F403
 from . import spectral  # noqa: F401,E402

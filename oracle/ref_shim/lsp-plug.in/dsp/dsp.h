@@ -1,0 +1,162 @@
+// STAND-IN for lsp-dsp-lib's <lsp-plug.in/dsp/dsp.h>, which the reference tree does not carry.  Only what Compressor,
+// Expander, Gate and DynamicProcessor take from it: dsp::copy, the knee structs, and the eight array gain primitives.
+//
+// The primitives are plain loops of the formula that each class states in full in its own scalar overload
+// (Compressor::reduction(float) / curve(float), Expander::amplification(float) / curve(float), Gate::amplification(float, bool)
+// / curve(float, bool)).  They are NOT lsp-dsp-lib's code and pin none of its SIMD variants; the vector generator asserts, on
+// every level and envelope sample it records, that each loop returns the bits of the class's scalar overload, so what is
+// recorded as the reference's gain is what the reference's own text computes.  No follower, settings or hysteresis
+// arithmetic lives here.
+#ifndef ORACLE_REF_SHIM_DSP_DSP_H_
+#define ORACLE_REF_SHIM_DSP_DSP_H_
+
+#include <cmath>
+#include <cstring>
+#include <lsp-plug.in/common/types.h>
+
+namespace lsp
+{
+    namespace dsp
+    {
+        struct compressor_knee_t    { float start, end, gain, herm[3], tilt[2]; };
+        struct compressor_x2_t      { compressor_knee_t k[2]; };
+        struct expander_knee_t      { float start, end, threshold, herm[3], tilt[2]; };
+        struct gate_knee_t          { float start, end, gain_start, gain_end, herm[4]; };
+
+        inline void copy(float *dst, const float *src, size_t count)
+        {
+            if (dst != src)
+                memmove(dst, src, count * sizeof(float));
+        }
+
+        // ---- compressor: two knees, their gains multiplied ------------------------------------------------------------
+        inline float shim_compressor_gain(const compressor_x2_t *c, float x)
+        {
+            if ((x <= c->k[0].start) && (x <= c->k[1].start))
+                return c->k[0].gain * c->k[1].gain;
+            float lx = logf(x), g[2];
+            for (size_t j = 0; j < 2; ++j)
+            {
+                const compressor_knee_t *k = &c->k[j];
+                g[j] = (x <= k->start) ? k->gain :
+                       (x >= k->end) ? expf(lx * k->tilt[0] + k->tilt[1]) :
+                       expf((k->herm[0] * lx + k->herm[1]) * lx + k->herm[2]);
+            }
+            return g[0] * g[1];
+        }
+
+        inline void compressor_x2_gain(float *dst, const float *src, const compressor_x2_t *c, size_t count)
+        {
+            for (size_t i = 0; i < count; ++i)
+                dst[i] = shim_compressor_gain(c, fabsf(src[i]));
+        }
+
+        inline void compressor_x2_curve(float *dst, const float *src, const compressor_x2_t *c, size_t count)
+        {
+            for (size_t i = 0; i < count; ++i)
+            {
+                float x = fabsf(src[i]);
+                // the scalar overload's two returns: (gain0 * gain1) * x below both knees, (g1 * g2) * x elsewhere
+                dst[i] = shim_compressor_gain(c, x) * x;
+            }
+        }
+
+        // ---- gate: one knee, a cubic in ln x ----------------------------------------------------------------------------
+        inline float shim_gate_gain(const gate_knee_t *c, float x)
+        {
+            if (x <= c->start)
+                return c->gain_start;
+            if (x >= c->end)
+                return c->gain_end;
+            float lx = logf(x);
+            return expf(((c->herm[0] * lx + c->herm[1]) * lx + c->herm[2]) * lx + c->herm[3]);
+        }
+
+        inline void gate_x1_gain(float *dst, const float *src, const gate_knee_t *c, size_t count)
+        {
+            for (size_t i = 0; i < count; ++i)
+                dst[i] = shim_gate_gain(c, fabsf(src[i]));
+        }
+
+        inline void gate_x1_curve(float *dst, const float *src, const gate_knee_t *c, size_t count)
+        {
+            for (size_t i = 0; i < count; ++i)
+            {
+                float x = fabsf(src[i]);
+                dst[i] = x * shim_gate_gain(c, x);
+            }
+        }
+
+        // ---- expander, upward: the level limited to the threshold ------------------------------------------------------
+        inline float shim_uexpander_gain(const expander_knee_t *c, float *x)
+        {
+            if (*x > c->threshold)
+                *x = c->threshold;
+            if (*x > c->start)
+            {
+                float lx = logf(*x);
+                return (*x >= c->end) ? expf(c->tilt[0] * lx + c->tilt[1]) :
+                                        expf((c->herm[0] * lx + c->herm[1]) * lx + c->herm[2]);
+            }
+            return 1.0f;
+        }
+
+        inline void uexpander_x1_gain(float *dst, const float *src, const expander_knee_t *c, size_t count)
+        {
+            for (size_t i = 0; i < count; ++i)
+            {
+                float x = fabsf(src[i]);
+                dst[i] = shim_uexpander_gain(c, &x);
+            }
+        }
+
+        inline void uexpander_x1_curve(float *dst, const float *src, const expander_knee_t *c, size_t count)
+        {
+            for (size_t i = 0; i < count; ++i)
+            {
+                float x = fabsf(src[i]);
+                float g = shim_uexpander_gain(c, &x);
+                dst[i] = (x > c->start) ? x * g : x;
+            }
+        }
+
+        // ---- expander, downward: nothing below the threshold ------------------------------------------------------------
+        inline void dexpander_x1_gain(float *dst, const float *src, const expander_knee_t *c, size_t count)
+        {
+            for (size_t i = 0; i < count; ++i)
+            {
+                float x = fabsf(src[i]);
+                if (x < c->threshold)
+                    dst[i] = 0.0f;
+                else if (x < c->end)
+                {
+                    float lx = logf(x);
+                    dst[i] = (x <= c->start) ? expf(c->tilt[0] * lx + c->tilt[1]) :
+                                               expf((c->herm[0] * lx + c->herm[1]) * lx + c->herm[2]);
+                }
+                else
+                    dst[i] = 1.0f;
+            }
+        }
+
+        inline void dexpander_x1_curve(float *dst, const float *src, const expander_knee_t *c, size_t count)
+        {
+            for (size_t i = 0; i < count; ++i)
+            {
+                float x = fabsf(src[i]);
+                if (x < c->threshold)
+                    dst[i] = 0.0f;
+                else if (x < c->end)
+                {
+                    float lx = logf(x);
+                    dst[i] = (x <= c->start) ? x * expf(c->tilt[0] * lx + c->tilt[1]) :
+                                               x * expf((c->herm[0] * lx + c->herm[1]) * lx + c->herm[2]);
+                }
+                else
+                    dst[i] = x;
+            }
+        }
+    }
+}
+
+#endif

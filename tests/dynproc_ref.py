@@ -136,13 +136,17 @@ def limited(e, lo):
     return np.clip(np.abs(np.ascontiguousarray(e, f32)), f32(lo), FLOAT_SAT_P_INF).astype(f32)
 
 
-def _curve(e, params, dtype, lo, model):
+def _curve(e, params, dtype, lo, model, shift=0):
     """(gain, bound in u, which) of the level e [C, n] in `dtype` arithmetic.  which: int8 [C, n, 4], per spline 0 below
-    knee_start (model: at or below thresh), 1 inside the knee, 2 from knee_stop on (model: above thresh), -1 no such spline."""
+    knee_start (model: at or below thresh), 1 inside the knee, 2 from knee_stop on (model: above thresh), -1 no such spline.
+    shift: the branches are chosen on lx moved by that many float32 spacings (the arithmetic stays on lx): the branch a logf
+    takes that is `shift` ulp from the correctly rounded one, see gain_bound_either()."""
     x32 = limited(e, lo)
     C, n = x32.shape
     lx32 = np.log(x32.astype(np.float64)).astype(f32)          # logf, correctly rounded: the float32 value both sides use
     lx = lx32.astype(dtype)
+    for _ in range(abs(shift)):                                 # from here on lx32 only chooses branches
+        lx32 = np.nextafter(lx32, f32(np.inf if shift > 0 else -np.inf))
     gain, D = np.zeros((C, n), dtype), np.zeros((C, n))
     which = np.full((C, n, DOTS), -1, np.int8)
     count = np.array([len(p["splines"]) for p in params])
@@ -189,6 +193,21 @@ def gain32(e, params, lo=GAIN_AMP_MIN, model=False):
 def gain_bound(e, params, lo=GAIN_AMP_MIN, model=False):
     """Allowed |gain - gain64| / gain64 in units of u = 2^-24, per sample (0 for a channel without splines: the gain is 1)."""
     return _curve(e, params, np.float64, lo, model)[1]
+
+
+def gain_bound_either(e, params, lo=GAIN_AMP_MIN, model=False):
+    """gain_bound() for an implementation whose logf is not the correctly rounded one.  The splines choose their branch on
+    lx = logf(x); LIBM allows logf 2 ulp, so at a level whose logarithm lies within 2 ulp of a knee end or a threshold either
+    branch is a correct evaluation.  The two meet there in value and slope, but their bounds differ (the knee's monomial
+    form cancels, the line's does not): allowed is, over the branch choices of lx - 2 ulp .. lx + 2 ulp, the largest of that
+    choice's own bound plus the distance of its float64 value from gain64()'s, in u."""
+    g0, b0, _ = _curve(e, params, np.float64, lo, model)
+    out = b0
+    with np.errstate(all="ignore"):
+        for shift in (-2, -1, 1, 2):
+            g, b, _ = _curve(e, params, np.float64, lo, model, shift)
+            out = np.maximum(out, b + np.where(g == g0, 0.0, np.abs(g - g0) / g0 / U))
+    return out
 
 
 def within(got, g64, bound):
