@@ -1138,6 +1138,91 @@ int mi_dynproc_bank_curve(mi_dynproc_bank_t *bank, float *out, const float *in, 
 int mi_dynproc_bank_model(mi_dynproc_bank_t *bank, float *out, const float *in, size_t dots, size_t out_stride,
                           size_t in_stride, void *stream);
 
+/* ---- limiter bank (look-ahead peak search and multiplicative gain patches) ----------------------------------------------- */
+/*
+ * mi_limiter_bank: `channels` x lsp::dspu::Limiter (dynamics/Limiter.h:55-381, src/main/dynamics/Limiter.cpp), every channel
+ * with settings and mode of its own; the maximum look-ahead is the bank's.  process() is the reference's (:695-784): the call is
+ * cut into chunks of at most 8192 samples counted from its first sample; per chunk the gain window (ML = nMaxLookahead behind,
+ * the chunk, 3 ML ahead) takes ones at its end, the ALR follower if enabled, and then patches: the first index of the maximum
+ * of gain |sc| is found, and while it exceeds the threshold the gains around it are multiplied by 1 - k shape(t), the knee
+ * lowered by 0.9886 after every 32 patches.  The gain, nHead, the ALR envelope and the number of patches are the bits of that
+ * loop in float32 (every product, sum and quotient rounded on its own) with shape(t) from the host's table
+ * (mi_limiter_compute_patch) and dsp::max_index / dsp::abs_mul3 of the absent lsp-dsp-lib taken as "first index of the
+ * maximum" and a |b| (DESIGN.md sections 3.15 and 4).  TWO DIFFERENCES: the patch loop of a chunk of n samples ends after 2 n
+ * patches at the latest and then sets the channel's sticky overrun flag (the reference does not return on NaN); and a patch
+ * that reaches outside the window, which happens only with a look-ahead under 8 samples, is cut at the window's ends, where the
+ * reference multiplies floats it never reads again (or, with ML < 8, floats outside its allocation).  The gain window, nHead,
+ * the ALR envelope, the audio history of process_apply and the counters live on the device: calls can be captured and
+ * replayed.  Inputs are finite.  Unlike Limiter::process, the results depend on how the stream is cut into calls exactly as the
+ * reference's do.  Rows of the sample buffers: [channels][stride].
+ */
+typedef struct mi_limiter_bank mi_limiter_bank_t;
+#define MI_LIMITER_MAX_LOOKAHEAD 4064   /* the largest nMaxLookahead in samples: window, |sc| and gain |sc| of a chunk fill the LDS */
+#define MI_LIMITER_MODES 12             /* limiter_mode_t: LM_HERM_, LM_EXP_, LM_LINE_ x THIN, WIDE, TAIL, DUCK */
+/* the setters' values: times in ms; threshold is fReqThreshold; alr_knee as set_alr_knee stored it */
+typedef struct
+{
+    uint32_t sample_rate, mode;
+    float threshold, lookahead, attack, release, knee, alr_attack, alr_release, alr_knee;
+} mi_limiter_settings_t;
+/* what update_settings() computes: nLookahead; nAttack, nPlane, nRelease, nMiddle, vAttack, vRelease of sSat / sExp / sLine
+ * (entries the mode does not write are 0); fThreshold; sALR.fKS, fKE, fGain, vHermite, fTauAttack, fTauRelease */
+typedef struct
+{
+    uint32_t lookahead, mode;
+    int32_t attack, plane, release, middle;
+    float v_attack[4], v_release[4];
+    float threshold, ks, ke, gain, hermite[3], tau_attack, tau_release;
+} mi_limiter_params_t;
+/* update_settings(), :396-548, with init_sat / init_exp / init_line (:278-394) in host float32; interpolation::hermite_cubic
+ * and ::exponent with their double stretches (interpolation.cpp:112-131, :224-230).  As in the reference init_exp compares
+ * the mode with the LM_HERM_ values, so the four LM_EXP_ modes share the WIDE widths.  No device needed. */
+int mi_limiter_compute_params(const mi_limiter_settings_t *settings, mi_limiter_params_t *params);
+/* shape[t], t in [0, params->release): what apply_*_patch (:609-673) multiplies amp with, in float32, every operation rounded
+ * on its own, expf the host's; exactly 1 on the plane.  capacity: floats at shape; MI_EINVAL if params->release exceeds it. */
+int mi_limiter_compute_patch(const mi_limiter_params_t *params, float *shape, size_t capacity);
+/* construct() and init(max_sample_rate, max_lookahead_ms), :47-109, of every channel: gains 1, nHead 0, an update pending.
+ * MI_EINVAL if millis_to_samples(max_sample_rate, max_lookahead_ms) exceeds MI_LIMITER_MAX_LOOKAHEAD. */
+int mi_limiter_bank_create(mi_limiter_bank_t **bank, uint32_t channels, uint32_t max_sample_rate, float max_lookahead_ms);
+int mi_limiter_bank_destroy(mi_limiter_bank_t *bank);
+/* The setters of one channel (:111-229): early return on unchanged values; set_lookahead limits to the maximum;
+ * set_threshold without `immediate` leaves fThreshold for update_settings() to lower (which scales ML gains);
+ * set_alr_knee stores 1 / knee for a knee above 1; set_alr(0) zeroes the envelope before the next launch */
+int mi_limiter_bank_set_sample_rate(mi_limiter_bank_t *bank, uint32_t channel, uint32_t sample_rate);
+int mi_limiter_bank_set_mode(mi_limiter_bank_t *bank, uint32_t channel, uint32_t mode);
+int mi_limiter_bank_set_threshold(mi_limiter_bank_t *bank, uint32_t channel, float threshold, int immediate);
+int mi_limiter_bank_set_attack(mi_limiter_bank_t *bank, uint32_t channel, float attack);
+int mi_limiter_bank_set_release(mi_limiter_bank_t *bank, uint32_t channel, float release);
+int mi_limiter_bank_set_lookahead(mi_limiter_bank_t *bank, uint32_t channel, float lookahead);
+int mi_limiter_bank_set_knee(mi_limiter_bank_t *bank, uint32_t channel, float knee);
+int mi_limiter_bank_set_alr(mi_limiter_bank_t *bank, uint32_t channel, int enable);
+int mi_limiter_bank_set_alr_attack(mi_limiter_bank_t *bank, uint32_t channel, float attack);
+int mi_limiter_bank_set_alr_release(mi_limiter_bank_t *bank, uint32_t channel, float release);
+int mi_limiter_bank_set_alr_knee(mi_limiter_bank_t *bank, uint32_t channel, float knee);
+/* update_settings(), :396-548, of every channel with changes, its work on the gain window included; not during a capture */
+int mi_limiter_bank_update_settings(mi_limiter_bank_t *bank, void *stream);
+/* every channel as after create(): gains 1, nHead 0, envelope 0, audio history 0, counters and overrun flag 0 */
+int mi_limiter_bank_clear(mi_limiter_bank_t *bank, void *stream);
+int mi_limiter_bank_get_params(const mi_limiter_bank_t *bank, uint32_t channel, mi_limiter_params_t *params);
+/* the channel's shape table as the device has it (HOST memory, *count entries; capacity: floats at shape; waits for the
+ * stream; not during a capture) */
+int mi_limiter_bank_get_patch(mi_limiter_bank_t *bank, uint32_t channel, float *shape, size_t capacity, uint32_t *count,
+                              void *stream);
+/* nLookahead of the channel after pending settings */
+int mi_limiter_bank_get_latency(mi_limiter_bank_t *bank, uint32_t channel, uint32_t *latency);
+/* nHead, sALR.fEnvelope, the patches and the chunks of the last call, the sticky overrun flag (HOST memory, each may be NULL;
+ * waits for the stream; not during a capture) */
+int mi_limiter_bank_get_state(mi_limiter_bank_t *bank, uint32_t channel, uint32_t *head, float *envelope, uint32_t *patches,
+                              uint32_t *chunks, uint32_t *overrun, void *stream);
+/* process(gain, sc, samples), :695-784; gain may be the sc rows (same stride) */
+int mi_limiter_bank_process(mi_limiter_bank_t *bank, float *gain, const float *sc, size_t count, size_t gain_stride,
+                            size_t sc_stride, void *stream);
+/* dst[i] = audio_stream[i - nLookahead] * gain[i] in the same launch: the Delay and the multiply a caller puts behind
+ * process().  The last ML samples of every channel's audio are kept between calls (zero at the start); a changed look-ahead
+ * moves the read offset at the next call.  dst may be audio or sc (same stride). */
+int mi_limiter_bank_process_apply(mi_limiter_bank_t *bank, float *dst, const float *audio, const float *sc, size_t count,
+                                  size_t dst_stride, size_t audio_stride, size_t sc_stride, void *stream);
+
 /* ---- sidechain bank (source selection, pre-amplification and the peak / RMS / low-pass / uniform detectors) ------------- */
 /*
  * mi_sidechain_bank: `channels` x lsp::dspu::Sidechain (util/Sidechain.h:59-205, src/main/util/Sidechain.cpp), every channel

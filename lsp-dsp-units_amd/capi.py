@@ -114,6 +114,21 @@ class DynprocSettings(ctypes.Structure):
                 ("attack_time", c_float * 5), ("release_time", c_float * 5)]
 
 
+class LimiterSettings(ctypes.Structure):
+    """mi_limiter_settings_t: the values of Limiter's setters."""
+    _fields_ = [("sample_rate", c_uint32), ("mode", c_uint32)] + \
+               [(n, c_float) for n in ("threshold", "lookahead", "attack", "release", "knee", "alr_attack", "alr_release", "alr_knee")]
+
+
+class LimiterParams(ctypes.Structure):
+    """mi_limiter_params_t: what Limiter::update_settings computes."""
+    _fields_ = [("lookahead", c_uint32), ("mode", c_uint32)] + \
+               [(n, ctypes.c_int32) for n in ("attack", "plane", "release", "middle")] + \
+               [("v_attack", c_float * 4), ("v_release", c_float * 4)] + \
+               [(n, c_float) for n in ("threshold", "ks", "ke", "gain")] + [("hermite", c_float * 3)] + \
+               [("tau_attack", c_float), ("tau_release", c_float)]
+
+
 class SidechainParams(ctypes.Structure):
     """mi_sidechain_params_t: what Sidechain::update_settings and set_sample_rate compute, and the settings beside them."""
     _fields_ = [("reactivity", c_uint32), ("tau", c_float), ("interval", c_float), ("capacity", c_uint32), ("mode", c_uint32),
@@ -366,6 +381,30 @@ PROTOTYPES = {
     "mi_dynproc_bank_process_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_dynproc_bank_curve": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_dynproc_bank_model": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_limiter_compute_params": (c_int, [POINTER(LimiterSettings), POINTER(LimiterParams)]),
+    "mi_limiter_compute_patch": (c_int, [POINTER(LimiterParams), c_void_p, c_size_t]),
+    "mi_limiter_bank_create": (c_int, [POINTER(c_void_p), c_uint32, c_uint32, c_float]),
+    "mi_limiter_bank_destroy": (c_int, [c_void_p]),
+    "mi_limiter_bank_set_sample_rate": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_limiter_bank_set_mode": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_limiter_bank_set_threshold": (c_int, [c_void_p, c_uint32, c_float, c_int]),
+    "mi_limiter_bank_set_attack": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_limiter_bank_set_release": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_limiter_bank_set_lookahead": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_limiter_bank_set_knee": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_limiter_bank_set_alr": (c_int, [c_void_p, c_uint32, c_int]),
+    "mi_limiter_bank_set_alr_attack": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_limiter_bank_set_alr_release": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_limiter_bank_set_alr_knee": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_limiter_bank_update_settings": (c_int, [c_void_p, c_void_p]),
+    "mi_limiter_bank_clear": (c_int, [c_void_p, c_void_p]),
+    "mi_limiter_bank_get_params": (c_int, [c_void_p, c_uint32, POINTER(LimiterParams)]),
+    "mi_limiter_bank_get_patch": (c_int, [c_void_p, c_uint32, c_void_p, c_size_t, POINTER(c_uint32), c_void_p]),
+    "mi_limiter_bank_get_latency": (c_int, [c_void_p, c_uint32, POINTER(c_uint32)]),
+    "mi_limiter_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(c_uint32), POINTER(c_float), POINTER(c_uint32), POINTER(c_uint32),
+                                          POINTER(c_uint32), c_void_p]),
+    "mi_limiter_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_limiter_bank_process_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_sidechain_compute_params": (c_int, [c_uint32, c_float, c_float, POINTER(SidechainParams)]),
     "mi_sidechain_bank_create": (c_int, [POINTER(c_void_p), c_uint32, c_uint32, c_float]),
     "mi_sidechain_bank_destroy": (c_int, [c_void_p]),

@@ -830,6 +830,10 @@ int mi_dynfilter_bank_create(mi_dynfilter_bank_t **bank, uint32_t channels, uint
     const size_t bytes = size_t(filters) * channels * CHAINS_MAX * 2 * sizeof(float);
     hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_state), bytes);
     if (e == hipSuccess) e = hipMemset(b->d_state, 0, bytes);
+    // hipMemset on device memory may return before the fill has run: it is queued on the null stream, behind whatever is
+    // there.  A first process() on a stream that does not wait for the null stream would otherwise race with it (the fill
+    // landing between two later calls zeroes the filter memory they carry): the creation ends when the fill has.
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess)
     {
         mi_dynfilter_bank_destroy(b);

@@ -1098,6 +1098,156 @@ class GateBank(_DynamicsBank):
                                      _stream(stream)))
 
 
+def _limiter_dict(p):
+    d = dict((n, getattr(p, n)) for n in ("lookahead", "mode", "attack", "plane", "release", "middle"))
+    d.update((n, np.float32(getattr(p, n))) for n in ("threshold", "ks", "ke", "gain", "tau_attack", "tau_release"))
+    d.update((n, np.array(getattr(p, n)[:], np.float32)) for n in ("v_attack", "v_release", "hermite"))
+    return d
+
+
+def _limiter_params(d):
+    from .capi import LimiterParams
+    p = LimiterParams()
+    for n in ("lookahead", "mode", "attack", "plane", "release", "middle", "threshold", "ks", "ke", "gain", "tau_attack", "tau_release"):
+        setattr(p, n, d[n].item() if hasattr(d[n], "item") else d[n])
+    for n in ("v_attack", "v_release", "hermite"):
+        getattr(p, n)[:] = [float(v) for v in d[n]]
+    return p
+
+
+class LimiterBank:
+    """`channels` x lsp::dspu::Limiter (mi_limiter_bank_*): look-ahead peak search and multiplicative gain patches, every
+    channel with settings and mode of its own; the maximum sample rate and look-ahead (ms) are the bank's."""
+    MODES = ("HERM_THIN", "HERM_WIDE", "HERM_TAIL", "HERM_DUCK", "EXP_THIN", "EXP_WIDE", "EXP_TAIL", "EXP_DUCK",
+             "LINE_THIN", "LINE_WIDE", "LINE_TAIL", "LINE_DUCK")
+    MAX_LOOKAHEAD = 4064
+    SETTINGS = {"sample_rate": 0, "mode": 0, "threshold": 1.0, "lookahead": 0.0, "attack": 0.0, "release": 0.0, "knee": 0.50118,
+                "alr_attack": 10.0, "alr_release": 50.0, "alr_knee": 0.56234}
+
+    def __init__(self, channels, max_sample_rate, max_lookahead):
+        h = c_void_p()
+        check(lib.mi_limiter_bank_create(byref(h), channels, max_sample_rate, max_lookahead))
+        self.handle, self.channels = h, channels
+
+    @classmethod
+    def compute_params(cls, **settings):
+        """update_settings() of one limiter on the host (mi_limiter_compute_params): no device needed.  Keywords as SETTINGS
+        (construct()'s values where not given); alr_knee is the stored value."""
+        from .capi import LimiterParams, LimiterSettings
+        v = dict(cls.SETTINGS, **settings)
+        s = LimiterSettings(*[v[n] for n, _ in LimiterSettings._fields_])
+        p = LimiterParams()
+        check(lib.mi_limiter_compute_params(byref(s), byref(p)))
+        return _limiter_dict(p)
+
+    @staticmethod
+    def compute_patch(params):
+        """The patch of compute_params()'s result as a table of params["release"] float32 (mi_limiter_compute_patch)."""
+        out = np.zeros(max(params["release"], 0), np.float32)
+        check(lib.mi_limiter_compute_patch(byref(_limiter_params(params)), out.ctypes.data_as(c_void_p), out.size))
+        return out
+
+    def set_sample_rate(self, channel, sr):
+        check(lib.mi_limiter_bank_set_sample_rate(self.handle, channel, sr))
+
+    def set_mode(self, channel, mode):
+        check(lib.mi_limiter_bank_set_mode(self.handle, channel, mode))
+
+    def set_threshold(self, channel, threshold, immediate=False):
+        check(lib.mi_limiter_bank_set_threshold(self.handle, channel, threshold, 1 if immediate else 0))
+
+    def set_attack(self, channel, attack):
+        check(lib.mi_limiter_bank_set_attack(self.handle, channel, attack))
+
+    def set_release(self, channel, release):
+        check(lib.mi_limiter_bank_set_release(self.handle, channel, release))
+
+    def set_lookahead(self, channel, lookahead):
+        check(lib.mi_limiter_bank_set_lookahead(self.handle, channel, lookahead))
+
+    def set_knee(self, channel, knee):
+        check(lib.mi_limiter_bank_set_knee(self.handle, channel, knee))
+
+    def set_alr(self, channel, enable):
+        check(lib.mi_limiter_bank_set_alr(self.handle, channel, 1 if enable else 0))
+
+    def set_alr_attack(self, channel, attack):
+        check(lib.mi_limiter_bank_set_alr_attack(self.handle, channel, attack))
+
+    def set_alr_release(self, channel, release):
+        check(lib.mi_limiter_bank_set_alr_release(self.handle, channel, release))
+
+    def set_alr_knee(self, channel, knee):
+        check(lib.mi_limiter_bank_set_alr_knee(self.handle, channel, knee))
+
+    def configure(self, channel, sample_rate, mode, threshold, lookahead, attack, release, knee=None, alr=None, alr_attack=None,
+                  alr_release=None, alr_knee=None, immediate=True):
+        """The setters of one channel; what is None keeps its value."""
+        self.set_sample_rate(channel, sample_rate)
+        self.set_mode(channel, mode)
+        self.set_threshold(channel, threshold, immediate)
+        self.set_lookahead(channel, lookahead)
+        self.set_attack(channel, attack)
+        self.set_release(channel, release)
+        for value, setter in ((knee, self.set_knee), (alr_attack, self.set_alr_attack), (alr_release, self.set_alr_release),
+                              (alr_knee, self.set_alr_knee), (alr, self.set_alr)):
+            if value is not None:
+                setter(channel, value)
+
+    def update_settings(self, stream=None):
+        check(lib.mi_limiter_bank_update_settings(self.handle, _stream(stream)))
+
+    def clear(self, stream=None):
+        check(lib.mi_limiter_bank_clear(self.handle, _stream(stream)))
+
+    def get_params(self, channel):
+        from .capi import LimiterParams
+        p = LimiterParams()
+        check(lib.mi_limiter_bank_get_params(self.handle, channel, byref(p)))
+        return _limiter_dict(p)
+
+    def get_patch(self, channel, stream=None):
+        """The channel's shape table as the device has it, float32."""
+        out = np.zeros(3 * self.MAX_LOOKAHEAD + 17, np.float32)
+        n = c_uint32()
+        check(lib.mi_limiter_bank_get_patch(self.handle, channel, out.ctypes.data_as(c_void_p), out.size, byref(n), _stream(stream)))
+        return out[:n.value].copy()
+
+    def get_latency(self, channel):
+        n = c_uint32()
+        check(lib.mi_limiter_bank_get_latency(self.handle, channel, byref(n)))
+        return n.value
+
+    def get_state(self, channel, stream=None):
+        """(nHead, sALR.fEnvelope as numpy float32, patches and chunks of the last call, the sticky overrun flag)."""
+        h, e, p, c, o = c_uint32(), c_float(), c_uint32(), c_uint32(), c_uint32()
+        check(lib.mi_limiter_bank_get_state(self.handle, channel, byref(h), byref(e), byref(p), byref(c), byref(o), _stream(stream)))
+        return h.value, np.float32(e.value), p.value, c.value, o.value
+
+    def process(self, gain, sc, count, gain_stride=None, sc_stride=None, stream=None):
+        """process(gain, sc, samples); gain may be sc (in place)."""
+        check(lib.mi_limiter_bank_process(self.handle, _ptr(gain), _ptr(sc), count, count if gain_stride is None else gain_stride,
+                                          count if sc_stride is None else sc_stride, _stream(stream)))
+
+    def process_apply(self, out, audio, sc, count, out_stride=None, audio_stride=None, sc_stride=None, stream=None):
+        """out[i] = audio_stream[i - latency] * gain[i] in one launch; out may be audio or sc."""
+        check(lib.mi_limiter_bank_process_apply(self.handle, _ptr(out), _ptr(audio), _ptr(sc), count,
+                                                count if out_stride is None else out_stride,
+                                                count if audio_stride is None else audio_stride,
+                                                count if sc_stride is None else sc_stride, _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            lib.mi_limiter_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _dynproc_dict(p):
     """Entries [0, count) of the three tables, float32."""
     return {"hold": p.hold,
