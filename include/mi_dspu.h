@@ -1223,6 +1223,121 @@ int mi_limiter_bank_process(mi_limiter_bank_t *bank, float *gain, const float *s
 int mi_limiter_bank_process_apply(mi_limiter_bank_t *bank, float *dst, const float *audio, const float *sc, size_t count,
                                   size_t dst_stride, size_t audio_stride, size_t sc_stride, void *stream);
 
+/* ---- autogain bank (loudness gain riding: two levels in, one VCA gain out) ------------------------------------------------ */
+/*
+ * mi_autogain_bank: `channels` x lsp::dspu::AutoGain (dynamics/AutoGain.h:42-303, src/main/dynamics/AutoGain.cpp), every channel
+ * with settings of its own: what takes the loudness meter's per-sample output.  process() is the reference's (:223-296): a
+ * serial recurrence over (fCurrGain, fOutGain, the two surge flags) with up to five divisions per sample and no transcendental,
+ * so the gain and the state are the reference's bit for bit in float32 (every product, sum and quotient rounded on its own,
+ * division correctly rounded, subnormals kept).  The state lives on the device; the bank has no positions, so its process calls
+ * can be captured into a graph and replayed.  lexp > 0 and every input is finite: NaN is out of scope, and a gain that has
+ * underflowed to zero makes 0 / 0 here as it does in the reference.  Rows of the sample buffers: [channels][stride].
+ */
+typedef struct mi_autogain_bank mi_autogain_bank_t;
+/* AutoGain::flags_t without F_UPDATE: two switches and the two surge flags of the state */
+enum mi_autogain_flags { MI_AG_QUICK_AMP = 2, MI_AG_MAX_GAIN = 4, MI_AG_SURGE_UP = 8, MI_AG_SURGE_DOWN = 16 };
+/* AutoGain::compressor_t: x below x1, t above x2, between them ((a v + b) v + c v) + d of v = x - x1, as
+ * eval_curve (:197-206) writes it */
+typedef struct { float x1, x2, t, a, b, c, d; } mi_autogain_curve_t;
+/* the setters' values: speeds in dB/s, silence, deviation and max_gain as gains, flags of QUICK_AMP | MAX_GAIN */
+typedef struct
+{
+    uint32_t sample_rate, flags;
+    float short_grow, short_fall, long_grow, long_fall, silence, deviation, max_gain;
+} mi_autogain_settings_t;
+/* what update() computes (sShort.fKGrow, fKFall, sLong.fKGrow, fKFall, sShortComp, sOutComp) and, as set, fSilence,
+ * fDeviation, fMaxGain and the two switches */
+typedef struct
+{
+    float short_kgrow, short_kfall, long_kgrow, long_kfall;
+    mi_autogain_curve_t short_comp, out_comp;
+    float silence, deviation, max_gain;
+    uint32_t flags;
+} mi_autogain_params_t;
+/* update(), :155-173, with calc_compressor (:180-195) in host float32 (expf, sqrtf; ksr and c.a through double as the
+ * reference's expressions go).  No device needed. */
+int mi_autogain_compute_params(const mi_autogain_settings_t *settings, mi_autogain_params_t *params);
+/* construct(), :43-66: silence -72 dB, deviation +6 dB, max gain +12 dB, both gains 1, no switch, an update pending */
+int mi_autogain_bank_create(mi_autogain_bank_t **bank, uint32_t channels);
+int mi_autogain_bank_destroy(mi_autogain_bank_t *bank);
+/* The setters of one channel (:90-153, :175-178, AutoGain.h:166-215).  The speeds (limited to >= 0), the deviation (to >= 1)
+ * and the sample rate return early on an unchanged value and otherwise leave an update pending.  set_silence_threshold (limited
+ * to >= 0), set_max_gain (to >= 0), set_max_gain_control (the reference's set_max_gain(value, enable)), enable_max_gain and
+ * enable_quick_amplifier raise no update, as in the reference: their values go into the parameter table as they are and reach
+ * the device with the next update_settings() or process entry. */
+int mi_autogain_bank_set_sample_rate(mi_autogain_bank_t *bank, uint32_t channel, uint32_t sample_rate);
+int mi_autogain_bank_set_silence_threshold(mi_autogain_bank_t *bank, uint32_t channel, float threshold);
+int mi_autogain_bank_set_deviation(mi_autogain_bank_t *bank, uint32_t channel, float deviation);
+int mi_autogain_bank_set_short_grow(mi_autogain_bank_t *bank, uint32_t channel, float value);
+int mi_autogain_bank_set_short_fall(mi_autogain_bank_t *bank, uint32_t channel, float value);
+int mi_autogain_bank_set_short_speed(mi_autogain_bank_t *bank, uint32_t channel, float grow, float fall);
+int mi_autogain_bank_set_long_grow(mi_autogain_bank_t *bank, uint32_t channel, float value);
+int mi_autogain_bank_set_long_fall(mi_autogain_bank_t *bank, uint32_t channel, float value);
+int mi_autogain_bank_set_long_speed(mi_autogain_bank_t *bank, uint32_t channel, float grow, float fall);
+int mi_autogain_bank_set_max_gain(mi_autogain_bank_t *bank, uint32_t channel, float value);
+int mi_autogain_bank_set_max_gain_control(mi_autogain_bank_t *bank, uint32_t channel, float value, int enable);
+int mi_autogain_bank_enable_max_gain(mi_autogain_bank_t *bank, uint32_t channel, int enable);
+int mi_autogain_bank_enable_quick_amplifier(mi_autogain_bank_t *bank, uint32_t channel, int enable);
+/* update() of every channel with an update pending; the changed stretch of the parameter table goes to the device (and the
+ * call waits for it).  The process entries run it first.  On a stream being captured a pending upload is refused (MI_ESTATE) */
+int mi_autogain_bank_update_settings(mi_autogain_bank_t *bank, void *stream);
+/* The channel's parameter table entry (HOST memory); fCurrGain, fOutGain and nFlags without F_UPDATE (the switches as set,
+ * the surge flags of the state) as the work enqueued on `stream` leaves them (HOST memory, each may be NULL; waits for the
+ * stream; not during a capture) */
+int mi_autogain_bank_get_params(const mi_autogain_bank_t *bank, uint32_t channel, mi_autogain_params_t *params);
+int mi_autogain_bank_get_state(mi_autogain_bank_t *bank, uint32_t channel, float *curr_gain, float *out_gain, uint32_t *flags,
+                               void *stream);
+/* process(vca, llong, lshort, lexp, count), :278-286.  vca may be any of the three input rows (same stride). */
+int mi_autogain_bank_process(mi_autogain_bank_t *bank, float *vca, const float *llong, const float *lshort, const float *lexp,
+                             size_t count, size_t vca_stride, size_t long_stride, size_t short_stride, size_t exp_stride,
+                             void *stream);
+/* process(vca, llong, lshort, float lexp, count), :288-296: the expected level of channel ch is levels[ch], read from DEVICE
+ * memory by the launch, so that a captured call replays with new levels */
+int mi_autogain_bank_process_level(mi_autogain_bank_t *bank, float *vca, const float *llong, const float *lshort,
+                                   const float *levels, size_t count, size_t vca_stride, size_t long_stride, size_t short_stride,
+                                   void *stream);
+/* dst = audio * vca in the same launch: process() followed by one float32 multiply, bit for bit.  dst may be audio or any of
+ * the three level rows (same stride). */
+int mi_autogain_bank_process_apply(mi_autogain_bank_t *bank, float *dst, const float *audio, const float *llong,
+                                   const float *lshort, const float *lexp, size_t count, size_t dst_stride, size_t audio_stride,
+                                   size_t long_stride, size_t short_stride, size_t exp_stride, void *stream);
+
+/*
+ * mi_simple_autogain_bank: `channels` x lsp::dspu::SimpleAutoGain (dynamics/SimpleAutoGain.h:41-212,
+ * src/main/dynamics/SimpleAutoGain.cpp): one measured level in, the gain grows by fKGrow below the threshold, falls by fKFall
+ * above it, stays where the two are equal, and is limited with lsp_limit(g, min, max) after every sample.  Bit for bit in
+ * float32, subnormal gains kept.  fCurrGain lives on the device.  set_max_gain, set_min_gain and set_gain change fCurrGain at
+ * once in the reference (lsp_min, lsp_max, lsp_limit); here they are recorded IN ORDER and applied by the next process launch
+ * ahead of its first sample (get_state applies them to what it read); with min > max lsp_limit is no clamp, so nothing is
+ * merged.  Sending them is an upload: refused on a stream being captured (MI_ESTATE).  Inputs are finite.
+ */
+typedef struct mi_simple_autogain_bank mi_simple_autogain_bank_t;
+typedef struct { uint32_t sample_rate; float grow, fall, threshold, min_gain, max_gain; } mi_simple_autogain_settings_t;
+/* fKGrow, fKFall as update() computes them; fThreshold, fMinGain, fMaxGain as set */
+typedef struct { float kgrow, kfall, threshold, min_gain, max_gain; } mi_simple_autogain_params_t;
+/* update(), :142-153, in host float32.  No device needed. */
+int mi_simple_autogain_compute_params(const mi_simple_autogain_settings_t *settings, mi_simple_autogain_params_t *params);
+/* construct(), :43-56: gain 1, min gain 1e-6, max gain 1, everything else 0, an update pending */
+int mi_simple_autogain_bank_create(mi_simple_autogain_bank_t **bank, uint32_t channels);
+int mi_simple_autogain_bank_destroy(mi_simple_autogain_bank_t *bank);
+/* The setters of one channel (:68-140): sample rate, grow, fall and speed leave an update pending unless unchanged; the gain
+ * limits return early on unchanged values and otherwise act on fCurrGain as said above; set_threshold just sets */
+int mi_simple_autogain_bank_set_sample_rate(mi_simple_autogain_bank_t *bank, uint32_t channel, uint32_t sample_rate);
+int mi_simple_autogain_bank_set_grow(mi_simple_autogain_bank_t *bank, uint32_t channel, float value);
+int mi_simple_autogain_bank_set_fall(mi_simple_autogain_bank_t *bank, uint32_t channel, float value);
+int mi_simple_autogain_bank_set_speed(mi_simple_autogain_bank_t *bank, uint32_t channel, float grow, float fall);
+int mi_simple_autogain_bank_set_max_gain(mi_simple_autogain_bank_t *bank, uint32_t channel, float value);
+int mi_simple_autogain_bank_set_min_gain(mi_simple_autogain_bank_t *bank, uint32_t channel, float value);
+int mi_simple_autogain_bank_set_gain(mi_simple_autogain_bank_t *bank, uint32_t channel, float min, float max);
+int mi_simple_autogain_bank_set_threshold(mi_simple_autogain_bank_t *bank, uint32_t channel, float threshold);
+/* as mi_autogain_bank_update_settings / _get_params; fCurrGain of the channel with the recorded limit changes applied */
+int mi_simple_autogain_bank_update_settings(mi_simple_autogain_bank_t *bank, void *stream);
+int mi_simple_autogain_bank_get_params(const mi_simple_autogain_bank_t *bank, uint32_t channel, mi_simple_autogain_params_t *params);
+int mi_simple_autogain_bank_get_state(mi_simple_autogain_bank_t *bank, uint32_t channel, float *curr_gain, void *stream);
+/* process(dst, src, count), :155-175; dst may be src (same stride) */
+int mi_simple_autogain_bank_process(mi_simple_autogain_bank_t *bank, float *dst, const float *src, size_t count,
+                                    size_t dst_stride, size_t src_stride, void *stream);
+
 /* ---- sidechain bank (source selection, pre-amplification and the peak / RMS / low-pass / uniform detectors) ------------- */
 /*
  * mi_sidechain_bank: `channels` x lsp::dspu::Sidechain (util/Sidechain.h:59-205, src/main/util/Sidechain.cpp), every channel

@@ -129,6 +129,34 @@ class LimiterParams(ctypes.Structure):
                [("tau_attack", c_float), ("tau_release", c_float)]
 
 
+class AutoGainCurve(ctypes.Structure):
+    """mi_autogain_curve_t == AutoGain::compressor_t layout."""
+    _fields_ = [(n, c_float) for n in ("x1", "x2", "t", "a", "b", "c", "d")]
+
+
+class AutoGainSettings(ctypes.Structure):
+    """mi_autogain_settings_t: the values of AutoGain's setters."""
+    _fields_ = [("sample_rate", c_uint32), ("flags", c_uint32)] + \
+               [(n, c_float) for n in ("short_grow", "short_fall", "long_grow", "long_fall", "silence", "deviation", "max_gain")]
+
+
+class AutoGainParams(ctypes.Structure):
+    """mi_autogain_params_t: what AutoGain::update computes, and the values that need no update."""
+    _fields_ = [(n, c_float) for n in ("short_kgrow", "short_kfall", "long_kgrow", "long_kfall")] + \
+               [("short_comp", AutoGainCurve), ("out_comp", AutoGainCurve)] + \
+               [(n, c_float) for n in ("silence", "deviation", "max_gain")] + [("flags", c_uint32)]
+
+
+class SimpleAutoGainSettings(ctypes.Structure):
+    """mi_simple_autogain_settings_t: the values of SimpleAutoGain's setters."""
+    _fields_ = [("sample_rate", c_uint32)] + [(n, c_float) for n in ("grow", "fall", "threshold", "min_gain", "max_gain")]
+
+
+class SimpleAutoGainParams(ctypes.Structure):
+    """mi_simple_autogain_params_t: fKGrow, fKFall and the values that need no update."""
+    _fields_ = [(n, c_float) for n in ("kgrow", "kfall", "threshold", "min_gain", "max_gain")]
+
+
 class SidechainParams(ctypes.Structure):
     """mi_sidechain_params_t: what Sidechain::update_settings and set_sample_rate compute, and the settings beside them."""
     _fields_ = [("reactivity", c_uint32), ("tau", c_float), ("interval", c_float), ("capacity", c_uint32), ("mode", c_uint32),
@@ -405,6 +433,46 @@ PROTOTYPES = {
                                           POINTER(c_uint32), c_void_p]),
     "mi_limiter_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_limiter_bank_process_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_autogain_compute_params": (c_int, [POINTER(AutoGainSettings), POINTER(AutoGainParams)]),
+    "mi_autogain_bank_create": (c_int, [POINTER(c_void_p), c_uint32]),
+    "mi_autogain_bank_destroy": (c_int, [c_void_p]),
+    "mi_autogain_bank_set_sample_rate": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_autogain_bank_set_silence_threshold": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_autogain_bank_set_deviation": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_autogain_bank_set_short_grow": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_autogain_bank_set_short_fall": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_autogain_bank_set_short_speed": (c_int, [c_void_p, c_uint32, c_float, c_float]),
+    "mi_autogain_bank_set_long_grow": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_autogain_bank_set_long_fall": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_autogain_bank_set_long_speed": (c_int, [c_void_p, c_uint32, c_float, c_float]),
+    "mi_autogain_bank_set_max_gain": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_autogain_bank_set_max_gain_control": (c_int, [c_void_p, c_uint32, c_float, c_int]),
+    "mi_autogain_bank_enable_max_gain": (c_int, [c_void_p, c_uint32, c_int]),
+    "mi_autogain_bank_enable_quick_amplifier": (c_int, [c_void_p, c_uint32, c_int]),
+    "mi_autogain_bank_update_settings": (c_int, [c_void_p, c_void_p]),
+    "mi_autogain_bank_get_params": (c_int, [c_void_p, c_uint32, POINTER(AutoGainParams)]),
+    "mi_autogain_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(c_float), POINTER(c_float), POINTER(c_uint32), c_void_p]),
+    "mi_autogain_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t,
+                                         c_size_t, c_void_p]),
+    "mi_autogain_bank_process_level": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t,
+                                               c_size_t, c_void_p]),
+    "mi_autogain_bank_process_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t,
+                                               c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_simple_autogain_compute_params": (c_int, [POINTER(SimpleAutoGainSettings), POINTER(SimpleAutoGainParams)]),
+    "mi_simple_autogain_bank_create": (c_int, [POINTER(c_void_p), c_uint32]),
+    "mi_simple_autogain_bank_destroy": (c_int, [c_void_p]),
+    "mi_simple_autogain_bank_set_sample_rate": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_simple_autogain_bank_set_grow": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_simple_autogain_bank_set_fall": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_simple_autogain_bank_set_speed": (c_int, [c_void_p, c_uint32, c_float, c_float]),
+    "mi_simple_autogain_bank_set_max_gain": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_simple_autogain_bank_set_min_gain": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_simple_autogain_bank_set_gain": (c_int, [c_void_p, c_uint32, c_float, c_float]),
+    "mi_simple_autogain_bank_set_threshold": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_simple_autogain_bank_update_settings": (c_int, [c_void_p, c_void_p]),
+    "mi_simple_autogain_bank_get_params": (c_int, [c_void_p, c_uint32, POINTER(SimpleAutoGainParams)]),
+    "mi_simple_autogain_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(c_float), c_void_p]),
+    "mi_simple_autogain_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_sidechain_compute_params": (c_int, [c_uint32, c_float, c_float, POINTER(SidechainParams)]),
     "mi_sidechain_bank_create": (c_int, [POINTER(c_void_p), c_uint32, c_uint32, c_float]),
     "mi_sidechain_bank_destroy": (c_int, [c_void_p]),

@@ -1353,6 +1353,213 @@ class DynamicProcessorBank(_DynamicsBank):
                                         dots if in_stride is None else in_stride, _stream(stream)))
 
 
+def _autogain_dict(p):
+    curve = lambda c: dict((n, np.float32(getattr(c, n))) for n in ("x1", "x2", "t", "a", "b", "c", "d"))
+    d = dict((n, np.float32(getattr(p, n))) for n in ("short_kgrow", "short_kfall", "long_kgrow", "long_kfall", "silence",
+                                                      "deviation", "max_gain"))
+    d.update(short_comp=curve(p.short_comp), out_comp=curve(p.out_comp), flags=p.flags)
+    return d
+
+
+def _n(count, stride):
+    return count if stride is None else stride
+
+
+class AutoGainBank:
+    """`channels` x lsp::dspu::AutoGain (mi_autogain_bank_*): a long-period and a short-period loudness and the expected
+    level in, one VCA gain per sample out; every channel with settings of its own."""
+    F_QUICK_AMP, F_MAX_GAIN, F_SURGE_UP, F_SURGE_DOWN = 2, 4, 8, 16
+
+    def __init__(self, channels):
+        h = c_void_p()
+        check(lib.mi_autogain_bank_create(byref(h), channels))
+        self.handle, self.channels = h, channels
+
+    @staticmethod
+    def compute_params(sample_rate=0, flags=0, short_grow=0.0, short_fall=0.0, long_grow=0.0, long_fall=0.0, silence=2.5119e-4,
+                       deviation=1.99526, max_gain=3.98107):
+        """update() of one unit on the host (mi_autogain_compute_params): no device needed."""
+        from .capi import AutoGainParams, AutoGainSettings
+        s = AutoGainSettings(sample_rate, flags, short_grow, short_fall, long_grow, long_fall, silence, deviation, max_gain)
+        p = AutoGainParams()
+        check(lib.mi_autogain_compute_params(byref(s), byref(p)))
+        return _autogain_dict(p)
+
+    def set_sample_rate(self, channel, sr):
+        check(lib.mi_autogain_bank_set_sample_rate(self.handle, channel, sr))
+
+    def set_silence_threshold(self, channel, threshold):
+        check(lib.mi_autogain_bank_set_silence_threshold(self.handle, channel, threshold))
+
+    def set_deviation(self, channel, deviation):
+        check(lib.mi_autogain_bank_set_deviation(self.handle, channel, deviation))
+
+    def set_short_grow(self, channel, value):
+        check(lib.mi_autogain_bank_set_short_grow(self.handle, channel, value))
+
+    def set_short_fall(self, channel, value):
+        check(lib.mi_autogain_bank_set_short_fall(self.handle, channel, value))
+
+    def set_short_speed(self, channel, grow, fall):
+        check(lib.mi_autogain_bank_set_short_speed(self.handle, channel, grow, fall))
+
+    def set_long_grow(self, channel, value):
+        check(lib.mi_autogain_bank_set_long_grow(self.handle, channel, value))
+
+    def set_long_fall(self, channel, value):
+        check(lib.mi_autogain_bank_set_long_fall(self.handle, channel, value))
+
+    def set_long_speed(self, channel, grow, fall):
+        check(lib.mi_autogain_bank_set_long_speed(self.handle, channel, grow, fall))
+
+    def set_max_gain(self, channel, value, enable=None):
+        """set_max_gain(value) or, with enable, set_max_gain(value, enable)."""
+        if enable is None:
+            check(lib.mi_autogain_bank_set_max_gain(self.handle, channel, value))
+        else:
+            check(lib.mi_autogain_bank_set_max_gain_control(self.handle, channel, value, int(bool(enable))))
+
+    def enable_max_gain(self, channel, enable):
+        check(lib.mi_autogain_bank_enable_max_gain(self.handle, channel, int(bool(enable))))
+
+    def enable_quick_amplifier(self, channel, enable):
+        check(lib.mi_autogain_bank_enable_quick_amplifier(self.handle, channel, int(bool(enable))))
+
+    def configure(self, channel, sample_rate, short_grow, short_fall, long_grow, long_fall, silence, deviation, max_gain,
+                  quick_amp=False, limit=False):
+        """Every setter of one channel."""
+        self.set_sample_rate(channel, sample_rate)
+        self.set_short_speed(channel, short_grow, short_fall)
+        self.set_long_speed(channel, long_grow, long_fall)
+        self.set_silence_threshold(channel, silence)
+        self.set_deviation(channel, deviation)
+        self.set_max_gain(channel, max_gain, limit)
+        self.enable_quick_amplifier(channel, quick_amp)
+
+    def update_settings(self, stream=None):
+        check(lib.mi_autogain_bank_update_settings(self.handle, _stream(stream)))
+
+    def get_params(self, channel):
+        from .capi import AutoGainParams
+        p = AutoGainParams()
+        check(lib.mi_autogain_bank_get_params(self.handle, channel, byref(p)))
+        return _autogain_dict(p)
+
+    def get_state(self, channel, stream=None):
+        """(fCurrGain, fOutGain, nFlags without F_UPDATE) of the channel; the gains as numpy float32."""
+        g, o, f = c_float(), c_float(), c_uint32()
+        check(lib.mi_autogain_bank_get_state(self.handle, channel, byref(g), byref(o), byref(f), _stream(stream)))
+        return np.float32(g.value), np.float32(o.value), f.value
+
+    def process(self, vca, llong, lshort, lexp, count, vca_stride=None, long_stride=None, short_stride=None, exp_stride=None,
+                stream=None):
+        """process(vca, llong, lshort, lexp, count); vca may be any of the inputs (in place)."""
+        check(lib.mi_autogain_bank_process(self.handle, _ptr(vca), _ptr(llong), _ptr(lshort), _ptr(lexp), count, _n(count, vca_stride),
+                                           _n(count, long_stride), _n(count, short_stride), _n(count, exp_stride), _stream(stream)))
+
+    def process_level(self, vca, llong, lshort, levels, count, vca_stride=None, long_stride=None, short_stride=None, stream=None):
+        """process(vca, llong, lshort, float lexp, count) with levels[channels] in device memory."""
+        check(lib.mi_autogain_bank_process_level(self.handle, _ptr(vca), _ptr(llong), _ptr(lshort), _ptr(levels), count,
+                                                 _n(count, vca_stride), _n(count, long_stride), _n(count, short_stride),
+                                                 _stream(stream)))
+
+    def process_apply(self, out, audio, llong, lshort, lexp, count, out_stride=None, audio_stride=None, long_stride=None,
+                      short_stride=None, exp_stride=None, stream=None):
+        """out = audio * vca in one launch; out may be audio or any of the level rows."""
+        check(lib.mi_autogain_bank_process_apply(self.handle, _ptr(out), _ptr(audio), _ptr(llong), _ptr(lshort), _ptr(lexp), count,
+                                                 _n(count, out_stride), _n(count, audio_stride), _n(count, long_stride),
+                                                 _n(count, short_stride), _n(count, exp_stride), _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            lib.mi_autogain_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SimpleAutoGainBank:
+    """`channels` x lsp::dspu::SimpleAutoGain (mi_simple_autogain_bank_*): the gain grows below a threshold, falls above it
+    and stays within [min, max]; every channel with settings of its own."""
+
+    def __init__(self, channels):
+        h = c_void_p()
+        check(lib.mi_simple_autogain_bank_create(byref(h), channels))
+        self.handle, self.channels = h, channels
+
+    @staticmethod
+    def _dict(p):
+        return dict((n, np.float32(getattr(p, n))) for n in ("kgrow", "kfall", "threshold", "min_gain", "max_gain"))
+
+    @staticmethod
+    def compute_params(sample_rate=0, grow=0.0, fall=0.0, threshold=0.0, min_gain=0.000001, max_gain=1.0):
+        """update() of one unit on the host (mi_simple_autogain_compute_params): no device needed."""
+        from .capi import SimpleAutoGainParams, SimpleAutoGainSettings
+        s = SimpleAutoGainSettings(sample_rate, grow, fall, threshold, min_gain, max_gain)
+        p = SimpleAutoGainParams()
+        check(lib.mi_simple_autogain_compute_params(byref(s), byref(p)))
+        return SimpleAutoGainBank._dict(p)
+
+    def set_sample_rate(self, channel, sr):
+        check(lib.mi_simple_autogain_bank_set_sample_rate(self.handle, channel, sr))
+
+    def set_grow(self, channel, value):
+        check(lib.mi_simple_autogain_bank_set_grow(self.handle, channel, value))
+
+    def set_fall(self, channel, value):
+        check(lib.mi_simple_autogain_bank_set_fall(self.handle, channel, value))
+
+    def set_speed(self, channel, grow, fall):
+        check(lib.mi_simple_autogain_bank_set_speed(self.handle, channel, grow, fall))
+
+    def set_max_gain(self, channel, value):
+        check(lib.mi_simple_autogain_bank_set_max_gain(self.handle, channel, value))
+
+    def set_min_gain(self, channel, value):
+        check(lib.mi_simple_autogain_bank_set_min_gain(self.handle, channel, value))
+
+    def set_gain(self, channel, lo, hi):
+        check(lib.mi_simple_autogain_bank_set_gain(self.handle, channel, lo, hi))
+
+    def set_threshold(self, channel, threshold):
+        check(lib.mi_simple_autogain_bank_set_threshold(self.handle, channel, threshold))
+
+    def update_settings(self, stream=None):
+        check(lib.mi_simple_autogain_bank_update_settings(self.handle, _stream(stream)))
+
+    def get_params(self, channel):
+        from .capi import SimpleAutoGainParams
+        p = SimpleAutoGainParams()
+        check(lib.mi_simple_autogain_bank_get_params(self.handle, channel, byref(p)))
+        return self._dict(p)
+
+    def get_state(self, channel, stream=None):
+        """fCurrGain of the channel as numpy float32."""
+        g = c_float()
+        check(lib.mi_simple_autogain_bank_get_state(self.handle, channel, byref(g), _stream(stream)))
+        return np.float32(g.value)
+
+    def process(self, out, inp, count, out_stride=None, in_stride=None, stream=None):
+        """process(dst, src, count); out may be inp (in place)."""
+        check(lib.mi_simple_autogain_bank_process(self.handle, _ptr(out), _ptr(inp), count, _n(count, out_stride),
+                                                  _n(count, in_stride), _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            lib.mi_simple_autogain_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _sidechain_dict(p):
     return {"reactivity": p.reactivity, "tau": np.float32(p.tau), "interval": np.float32(p.interval), "capacity": p.capacity,
             "mode": p.mode, "source": p.source, "flags": p.flags, "gain": np.float32(p.gain)}
