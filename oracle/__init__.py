@@ -18,8 +18,12 @@ and DynamicProcessor (Makefile -> _ref/dyn_ref, with the stand-in headers of
 ref_shim/ and the driver dyn_driver.cpp; _ref/ is never committed).  That pins
 their followers, hold, hysteresis, update_settings and scalar gain formulas
 (tests/golden/dynamics_ref_vectors.npz, tests/test_dynamics_reference_*.py).
-It does not pin lsp-dsp-lib's array primitives or their SIMD variants, the
-Sidechain's detectors, the Lanczos tables or the IIR streaming arithmetic.
+Three more likewise, Limiter, AutoGain and SimpleAutoGain (Makefile -> _ref/gain_ref and its
+sanitizer twin _ref/gain_ref_san, driver gain_driver.cpp; tests/golden/
+limiter_ref_vectors.npz and autogain_ref_vectors.npz, tests/test_gain_reference_*.py).
+It does not pin lsp-dsp-lib's array primitives or their SIMD variants (dsp::max_index
+and dsp::abs_mul3 of the Limiter among them), the Sidechain's detectors, the Lanczos
+tables or the IIR streaming arithmetic.
 """
 from .binding import *  # noqa: F401,F403
 from . import spectral  # noqa: F401,E402

@@ -1,5 +1,6 @@
 // STAND-IN for lsp-dsp-lib's <lsp-plug.in/dsp/dsp.h>, which the reference tree does not carry.  Only what Compressor,
-// Expander, Gate and DynamicProcessor take from it: dsp::copy, the knee structs, and the eight array gain primitives.
+// Expander, Gate, DynamicProcessor and Limiter take from it: dsp::copy, the knee structs, the eight array gain primitives, and
+// Limiter.cpp's buffer primitives (at the end of this file; AutoGain and SimpleAutoGain take nothing).
 //
 // The primitives are plain loops of the formula that each class states in full in its own scalar overload
 // (Compressor::reduction(float) / curve(float), Expander::amplification(float) / curve(float), Gate::amplification(float, bool)
@@ -155,6 +156,54 @@ namespace lsp
                 else
                     dst[i] = x;
             }
+        }
+
+        // ---- Limiter.cpp's buffer primitives, each written from its call sites ---------------------------------------------
+        // :775 move(vGainBuf, &vGainBuf[nHead], 4 ML): the ranges overlap where nHead < 4 ML
+        inline void move(float *dst, const float *src, size_t count)
+        {
+            memmove(dst, src, count * sizeof(float));
+        }
+
+        // :103, :404, :707 (the comments say "fill gain buffer"; construct() starts from a gain of one) and :104
+        inline void fill_one(float *dst, size_t count)
+        {
+            for (size_t i = 0; i < count; ++i)
+                dst[i] = 1.0f;
+        }
+
+        inline void fill_zero(float *dst, size_t count)
+        {
+            for (size_t i = 0; i < count; ++i)
+                dst[i] = 0.0f;
+        }
+
+        // :415 mul_k2(gbuf, gnorm, nMaxLookahead): "lower gain since threshold has been lowered"
+        inline void mul_k2(float *dst, float k, size_t count)
+        {
+            for (size_t i = 0; i < count; ++i)
+                dst[i] *= k;
+        }
+
+        // UNPINNED, a stand-in by this project's reading.  :708, :712, :763 abs_mul3(vTmpBuf, gbuf, sc, to_do): "apply gain
+        // to sidechain", the result compared with the threshold as a level: a[i] * |b[i]|.  The reference tree does not carry
+        // lsp-dsp-lib, so neither the operand that loses its sign nor the order of the product is pinned by anything here.
+        inline void abs_mul3(float *dst, const float *a, const float *b, size_t count)
+        {
+            for (size_t i = 0; i < count; ++i)
+                dst[i] = a[i] * fabsf(b[i]);
+        }
+
+        // UNPINNED, a stand-in by this project's reading.  :721 max_index(vTmpBuf, to_do): "find peak": the FIRST index of
+        // the maximum.  Which of two equal maxima lsp-dsp-lib returns (and what its SIMD variants return) is not pinned by
+        // anything here; the vectors hold a case with two exactly equal peaks so that whoever pins it later sees it move.
+        inline size_t max_index(const float *src, size_t count)
+        {
+            size_t idx = 0;
+            for (size_t i = 1; i < count; ++i)
+                if (src[i] > src[idx])
+                    idx = i;
+            return idx;
         }
     }
 }

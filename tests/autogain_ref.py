@@ -1,7 +1,8 @@
 """float32 restatements of lsp::dspu::AutoGain and lsp::dspu::SimpleAutoGain (src/main/dynamics/AutoGain.cpp,
 SimpleAutoGain.cpp of lsp-dsp-units) in numpy: vectorised over channels, one Python step per sample, every product, sum and
 quotient rounded to float32 on its own.  Both count the branches they take, per channel, so that a test can say what its
-input reached.  Line numbers are the reference's."""
+input reached.  Line numbers are the reference's.  tests/test_gain_reference_host.py holds both, fed the reference's own recorded
+parameters, to what the reference's compiled classes computed (tests/golden/autogain_ref_vectors.npz), bit for bit."""
 import itertools
 import math
 

@@ -14,6 +14,10 @@ Limiter         process() (:695-784) and what update_settings() does to the gain
                 is compared bit for bit is the loop, not libm.  dsp::max_index is "first index of the maximum"
                 (numpy argmax), dsp::abs_mul3(dst, a, b) is a |b|: lsp-dsp-lib is absent, DESIGN section 4 says so.
                 The patch loop carries the bank's bound of 2 n patches per chunk and counts the patches.
+
+tests/test_gain_reference_host.py holds Limiter and Unit, fed the reference's own recorded parameters, to what the reference's
+compiled class computed (tests/golden/limiter_ref_vectors.npz): gain, nHead and the ALR envelope bit for bit.  The two primitives
+above stay this file's reading.
 """
 import numpy as np
 
