@@ -2,10 +2,13 @@
 // of process() (:404-430) -- the Compressor's three-variable recurrence with tau looked up per sample from the running envelope
 // (solve_reaction, :195-202) -- and the array reduction() (:562-584): the sum of up to four splines of ln |e|, then expf.
 //
-// dynproc_kernel runs on the tile walk of tile_chain_device.h exactly as compressor_kernel does: prepare loads the input
-// tile, the chain is the follower in place in LDS (dynproc_follow_tile, a function of its own so that its instructions can be
-// looked at, tests/test_dynproc_host.py), emit computes the gain from the envelope and stores.  The parameters are computed in
-// host/dynproc.cpp (mi_dynproc_compute_params).
+// dynproc_kernel runs on the tile walk of tile_chain_device.h as follow_kernel of dynamics_device.h does: prepare loads the
+// input tile, the chain is the follower in place in LDS (dynproc_follow_tile, a function of its own so that its instructions
+// can be looked at, tests/test_dynproc_host.py), emit computes the gain from the envelope and stores.  It is a kernel of its
+// own because emit reads the row's table anew for every tile through a wave-uniform pointer and the follower takes two
+// tables, not two taus, which nobody else in the walk would use; the flags, the follower's state, the end of its step and the
+// bank around the kernel (dynamics_bank_core.h) are the shared ones.  The parameters are computed in host/dynproc.cpp
+// (mi_dynproc_compute_params).
 //
 // Both tables of a channel are PADDED to their full length where they are loaded: a reaction level of +inf is never reached
 // by a finite envelope, so the look-up is four compares and four selects on every lane; a spline with knee_start = +inf and
@@ -13,26 +16,17 @@
 //
 // Inputs are finite: NaN is out of scope.  Subnormal envelopes are kept (the float32 denormal mode is on).
 #include "dynproc_bank.h"
-#include "tile_chain_device.h"
+#include "dynamics_bank_core.h"
 
 #include <cmath>
-#include <cstring>
-#include <new>
-#include <vector>
 
 #pragma clang fp contract(off)      // every product and every sum below rounds on its own
 
 namespace
 {
-    using namespace mi_tile_chain;
+    using namespace mi_dynamics;
 
-    constexpr int CURVE_BLOCK = 256;
     constexpr int DOTS = MI_DYNPROC_DOTS, RANGES = MI_DYNPROC_RANGES;
-
-    enum { VEC_IN = 1, VEC_GAIN = 2, VEC_ENV = 4, VEC_AUDIO = 8 };
-
-    struct follow_state { float e, peak; uint32_t hold; };
-    struct device_state { float e, peak; uint32_t hold, pad; };     // [channels] between calls
 
     // vAttack or vRelease in a lane's registers: t0 is the default, t1 .. t4 hold from l1 .. l4 on; +inf where unused.  Named
     // scalars, not arrays: of `r = (x >= lvl[i]) ? tau[i + 1] : r` over arrays the compiler makes a selected INDEX and a load
@@ -70,11 +64,7 @@ namespace
         const bool neg = d < 0.0f;
         const float tau = neg ? tr : ta;
         const float en = e + d * tau;
-        const bool held = neg && hold > 0;
-        const bool rearm = !neg && en >= peak;
-        e = held ? e : en;
-        peak = ((neg && !held) || rearm) ? en : peak;
-        hold = held ? hold - 1 : rearm ? nhold : hold;
+        MI_FOLLOW_SETTLE(e, peak, hold, neg, en, nhold);
     }
 
     // ... over samples [0, n) of one row in LDS, in place: row[i] becomes the envelope.  The two tables come as eighteen
@@ -281,81 +271,47 @@ namespace
         out[size_t(ch) * out_stride + i] = spline_gain<MODEL>(sp, x) * x;
     }
 
-    // DynamicProcessor::construct, :43-74
-    mi_dynproc_settings_t fresh_settings()
+} // namespace
+
+struct mi_dynproc_bank : mi_dynamics::bank<mi_dynproc_settings_t, mi_dynproc_params_t, device_state>
+{
+    static constexpr const char *NAME = "mi_dynproc_bank";
+
+    static mi_dynproc_settings_t fresh_settings()                               // DynamicProcessor::construct, :43-74
     {
         mi_dynproc_settings_t s = {};
         s.in_ratio = 1.0f;
         s.out_ratio = 1.0f;
         return s;
     }
-} // namespace
-
-struct mi_dynproc_bank
-{
-    uint32_t                                channels = 0;
-    std::vector<mi_dynproc_settings_t>      cfg;            // the setters' values
-    std::vector<uint8_t>                    update;         // bUpdate of every channel
-    std::vector<mi_dynproc_params_t>        params;         // what update_settings computed
-    mi::dirty_range                         up;             // where params differs from the device table
-    mi_dynproc_params_t                    *d_params = nullptr;     // [channels]
-    device_state                           *d_state = nullptr;      // [channels]
+    static mi_dynproc_params_t fresh_params()       // what the kernel may read before the first update: nothing but defaults
+    {
+        mi_dynproc_params_t p = {};
+        p.attacks = p.releases = 1;
+        return p;
+    }
+    static void compute(const mi_dynproc_settings_t &s, mi_dynproc_params_t &p) { mi_dynproc_compute_params(&s, &p); }
+    template <class... Args> static void launch(dim3 grid, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, Args... args)
+    {
+        MI_LAUNCH(dynproc_kernel, grid, dim3(BLOCK), 0, st, ev0, ev1, args...);
+    }
 };
 
 namespace
 {
-    // update_settings of every channel whose bUpdate is set; the changed stretch of the table goes to the device
-    int dyn_update(mi_dynproc_bank *b, hipStream_t st)
-    {
-        for (uint32_t ch = 0; ch < b->channels; ++ch)
-        {
-            if (!b->update[ch])
-                continue;
-            mi_dynproc_compute_params(&b->cfg[ch], &b->params[ch]);
-            b->update[ch] = 0;
-            b->up.touch(ch);
-        }
-        return mi::upload_dirty("mi_dynproc_bank", b->d_params, b->params.data(), b->up, st);
-    }
-
-    int dyn_launch(mi_dynproc_bank *b, float *gain, float *env, const float *in, const float *audio, size_t count,
-                   size_t gain_stride, size_t env_stride, size_t in_stride, size_t audio_stride, hipStream_t st)
-    {
-        const uint32_t vec = (mi::aligned16(in, in_stride, b->channels) ? VEC_IN : 0) | (mi::aligned16(gain, gain_stride, b->channels) ? VEC_GAIN : 0) |
-                             (mi::aligned16(env, env_stride, b->channels) ? VEC_ENV : 0) | (mi::aligned16(audio, audio_stride, b->channels) ? VEC_AUDIO : 0);
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        mi::take_profile_events(&ev0, &ev1);
-        MI_LAUNCH(dynproc_kernel, dim3((b->channels + GROUP - 1) / GROUP), dim3(BLOCK), 0, st, ev0, ev1, gain, env, in, audio,
-                  gain_stride, env_stride, in_stride, audio_stride, uint32_t(count), b->channels, b->d_params, b->d_state, vec);
-        MI_HIP_CHECK(hipGetLastError());
-        return MI_OK;
-    }
-
     int dyn_curve(mi_dynproc_bank *b, const char *entry, bool model, float *out, const float *in, size_t dots, size_t out_stride,
                   size_t in_stride, void *stream)
     {
-        MI_REQUIRE(b != nullptr, MI_ESTATE, "%s: NULL bank", entry);
-        hipStream_t st = mi::as_stream(stream);
-        const int r = dyn_update(b, st);
-        if (r != MI_OK || dots == 0)
-            return r;
-        MI_REQUIRE(out != nullptr && in != nullptr, MI_EINVAL, "%s: NULL buffer", entry);
-        MI_REQUIRE(dots < (size_t(1) << 31), MI_EINVAL, "%s: %zu dots are too many", entry, dots);
-        MI_REQUIRE(b->channels <= 65535u, MI_EINVAL, "%s: more than 65535 channels", entry);
-        MI_REQUIRE(b->channels == 1 || (out_stride >= dots && in_stride >= dots), MI_EINVAL,
-                   "%s: strides (%zu, %zu) shorter than %zu dots", entry, out_stride, in_stride, dots);
-        MI_REQUIRE(out != in || out_stride == in_stride, MI_EINVAL, "%s: in place with different strides", entry);
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        mi::take_profile_events(&ev0, &ev1);
-        const dim3 grid(uint32_t((dots + CURVE_BLOCK - 1) / CURVE_BLOCK), b->channels);
-        if (model)
-            MI_LAUNCH(dynproc_curve_kernel<true>, grid, dim3(CURVE_BLOCK), 0, st, ev0, ev1, out, in, out_stride, in_stride,
-                      uint32_t(dots), b->d_params);
-        else
-            MI_LAUNCH(dynproc_curve_kernel<false>, grid, dim3(CURVE_BLOCK), 0, st, ev0, ev1, out, in, out_stride, in_stride,
-                      uint32_t(dots), b->d_params);
-        MI_HIP_CHECK(hipGetLastError());
-        return MI_OK;
+        return mi_dynamics::curve(b, entry, out, in, dots, out_stride, in_stride, stream,
+                                  [&](dim3 grid, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1)
+        {
+            if (model)
+                MI_LAUNCH(dynproc_curve_kernel<true>, grid, dim3(CURVE_BLOCK), 0, st, ev0, ev1, out, in, out_stride, in_stride,
+                          uint32_t(dots), b->d_params);
+            else
+                MI_LAUNCH(dynproc_curve_kernel<false>, grid, dim3(CURVE_BLOCK), 0, st, ev0, ev1, out, in, out_stride, in_stride,
+                          uint32_t(dots), b->d_params);
+        });
     }
 } // namespace
 
@@ -363,21 +319,17 @@ namespace mi
 {
     int dynproc_bank_set_params(mi_dynproc_bank_t *b, uint32_t channel, const mi_dynproc_params_t *p)
     {
-        MI_REQUIRE(b != nullptr && p != nullptr && channel < b->channels, MI_EINVAL, "dynproc_bank_set_params: bad argument");
+        const int r = mi_dynamics::set_params_checks(b, "dynproc_bank_set_params", channel, p);
+        if (r != MI_OK)
+            return r;
         MI_REQUIRE(p->splines <= uint32_t(DOTS) && p->attacks >= 1 && p->attacks <= uint32_t(RANGES) && p->releases >= 1 &&
                    p->releases <= uint32_t(RANGES), MI_EINVAL, "dynproc_bank_set_params: counts out of range");
-        if (b->update[channel] == 0 && memcmp(&b->params[channel], p, sizeof(*p)) == 0)
-            return MI_OK;
-        b->params[channel] = *p;
-        b->update[channel] = 0;
-        b->up.touch(channel);
-        return MI_OK;
+        return mi_dynamics::set_params_store(b, channel, p);
     }
 
     int dynproc_bank_set_state(mi_dynproc_bank_t *b, uint32_t channel, float envelope, float peak, uint32_t hold, hipStream_t st)
     {
-        MI_REQUIRE(b != nullptr && channel < b->channels, MI_EINVAL, "dynproc_bank_set_state: bad argument");
-        return mi::write_state(b->d_state + channel, device_state{ envelope, peak, hold, 0 }, st);
+        return mi_dynamics::set_state(b, "dynproc_bank_set_state", channel, device_state{ envelope, peak, hold, 0 }, true, st);
     }
 }
 
@@ -385,38 +337,12 @@ extern "C" {
 
 int mi_dynproc_bank_create(mi_dynproc_bank_t **bank, uint32_t channels)                 // DynamicProcessor.cpp:43-74
 {
-    MI_REQUIRE(bank != nullptr, MI_EINVAL, "mi_dynproc_bank_create: NULL result pointer");
-    *bank = nullptr;
-    MI_REQUIRE(channels > 0 && channels <= (1u << 20), MI_EINVAL, "mi_dynproc_bank_create: channels must be 1 .. 1048576");
-    MI_REQUIRE(mi_dspu_device_count() > 0, MI_ENODEV, "no HIP device available (there is no CPU fallback)");
-    mi_dynproc_bank *b = new (std::nothrow) mi_dynproc_bank();
-    MI_REQUIRE(b != nullptr, MI_ENOMEM, "mi_dynproc_bank_create: out of host memory");
-    b->channels = channels;
-    b->cfg.assign(channels, fresh_settings());
-    b->update.assign(channels, 1);
-    mi_dynproc_params_t fresh = {};
-    fresh.attacks = fresh.releases = 1;             // what the kernel may read before the first update: nothing but defaults
-    b->params.assign(channels, fresh);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_params), size_t(channels) * sizeof(mi_dynproc_params_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_state), size_t(channels) * sizeof(device_state));
-    if (e == hipSuccess) e = hipMemcpy(b->d_params, b->params.data(), size_t(channels) * sizeof(mi_dynproc_params_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(b->d_state, 0, size_t(channels) * sizeof(device_state));
-    if (e != hipSuccess)
-    {
-        mi_dynproc_bank_destroy(b);
-        return mi::fail(MI_EHIP, "mi_dynproc_bank_create: %s", hipGetErrorString(e));
-    }
-    *bank = b;
-    return MI_OK;
+    return mi_dynamics::create(bank, "mi_dynproc_bank_create", channels);
 }
 
 int mi_dynproc_bank_destroy(mi_dynproc_bank_t *b)
 {
-    if (b == nullptr)
-        return MI_OK;
-    (void)hipFree(b->d_params); (void)hipFree(b->d_state);
-    delete b;
-    return MI_OK;
+    return mi_dynamics::destroy(b);
 }
 
 int mi_dynproc_bank_set_sample_rate(mi_dynproc_bank_t *b, uint32_t channel, uint32_t sample_rate)         // :80-86
@@ -526,73 +452,36 @@ int mi_dynproc_bank_set_hold(mi_dynproc_bank_t *b, uint32_t channel, float hold)
 
 int mi_dynproc_bank_update_settings(mi_dynproc_bank_t *b, void *stream)                                    // :339-395
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_dynproc_bank_update_settings: NULL bank");
-    return dyn_update(b, mi::as_stream(stream));
+    return mi_dynamics::update_settings(b, "mi_dynproc_bank_update_settings", stream);
 }
 
 int mi_dynproc_bank_clear(mi_dynproc_bank_t *b, void *stream)
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_dynproc_bank_clear: NULL bank");
-    MI_HIP_CHECK(hipMemsetAsync(b->d_state, 0, size_t(b->channels) * sizeof(device_state), mi::as_stream(stream)));
-    return MI_OK;
+    return mi_dynamics::clear(b, "mi_dynproc_bank_clear", stream);
 }
 
 int mi_dynproc_bank_get_params(const mi_dynproc_bank_t *b, uint32_t channel, mi_dynproc_params_t *params)
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_dynproc_bank_get_params: NULL bank");
-    MI_REQUIRE(channel < b->channels && params != nullptr, MI_EINVAL, "mi_dynproc_bank_get_params: bad argument");
-    *params = b->params[channel];
-    return MI_OK;
+    return mi_dynamics::get_params(b, "mi_dynproc_bank_get_params", channel, params);
 }
 
 int mi_dynproc_bank_get_state(mi_dynproc_bank_t *b, uint32_t channel, float *envelope, float *peak, uint32_t *hold,
                               void *stream)
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_dynproc_bank_get_state: NULL bank");
-    MI_REQUIRE(channel < b->channels, MI_EINVAL, "mi_dynproc_bank_get_state: channel %u out of range", channel);
-    device_state s;
-    const int r = mi::read_state(&s, b->d_state + channel, mi::as_stream(stream));
-    if (r != MI_OK)
-        return r;
-    if (envelope != nullptr) *envelope = s.e;
-    if (peak != nullptr) *peak = s.peak;
-    if (hold != nullptr) *hold = s.hold;
-    return MI_OK;
+    return mi_dynamics::get_follow_state(b, "mi_dynproc_bank_get_state", channel, envelope, peak, hold, stream);
 }
 
 int mi_dynproc_bank_process(mi_dynproc_bank_t *b, float *gain, float *env, const float *in, size_t count,
                             size_t gain_stride, size_t env_stride, size_t in_stride, void *stream)        // :397-442
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_dynproc_bank_process: NULL bank");
-    hipStream_t st = mi::as_stream(stream);
-    const int r = dyn_update(b, st);
-    if (r != MI_OK || count == 0)
-        return r;
-    MI_REQUIRE(gain != nullptr && in != nullptr, MI_EINVAL, "mi_dynproc_bank_process: NULL buffer");
-    MI_REQUIRE(count < (size_t(1) << 31), MI_EINVAL, "mi_dynproc_bank_process: count %zu too large", count);
-    MI_REQUIRE(b->channels == 1 || (gain_stride >= count && in_stride >= count && (env == nullptr || env_stride >= count)), MI_EINVAL,
-               "mi_dynproc_bank_process: strides (%zu, %zu, %zu) shorter than count %zu", gain_stride, env_stride, in_stride, count);
-    MI_REQUIRE(gain != env, MI_EINVAL, "mi_dynproc_bank_process: gain and env are the same buffer");
-    MI_REQUIRE((gain != in || gain_stride == in_stride) && (env != in || env_stride == in_stride), MI_EINVAL,
-               "mi_dynproc_bank_process: in place with different strides");
-    return dyn_launch(b, gain, env, in, nullptr, count, gain_stride, env_stride, in_stride, 0, st);
+    return mi_dynamics::process(b, "mi_dynproc_bank_process", gain, env, in, count, gain_stride, env_stride, in_stride, stream);
 }
 
 int mi_dynproc_bank_process_apply(mi_dynproc_bank_t *b, float *dst, const float *audio, const float *sc, size_t count,
                                   size_t dst_stride, size_t audio_stride, size_t sc_stride, void *stream)
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_dynproc_bank_process_apply: NULL bank");
-    hipStream_t st = mi::as_stream(stream);
-    const int r = dyn_update(b, st);
-    if (r != MI_OK || count == 0)
-        return r;
-    MI_REQUIRE(dst != nullptr && audio != nullptr && sc != nullptr, MI_EINVAL, "mi_dynproc_bank_process_apply: NULL buffer");
-    MI_REQUIRE(count < (size_t(1) << 31), MI_EINVAL, "mi_dynproc_bank_process_apply: count %zu too large", count);
-    MI_REQUIRE(b->channels == 1 || (dst_stride >= count && audio_stride >= count && sc_stride >= count), MI_EINVAL,
-               "mi_dynproc_bank_process_apply: strides (%zu, %zu, %zu) shorter than count %zu", dst_stride, audio_stride, sc_stride, count);
-    MI_REQUIRE((dst != audio || dst_stride == audio_stride) && (dst != sc || dst_stride == sc_stride), MI_EINVAL,
-               "mi_dynproc_bank_process_apply: in place with different strides");
-    return dyn_launch(b, dst, nullptr, sc, audio, count, dst_stride, 0, sc_stride, audio_stride, st);
+    return mi_dynamics::process_apply(b, "mi_dynproc_bank_process_apply", dst, audio, sc, count, dst_stride, audio_stride, sc_stride,
+                                      stream);
 }
 
 int mi_dynproc_bank_curve(mi_dynproc_bank_t *b, float *out, const float *in, size_t dots, size_t out_stride,

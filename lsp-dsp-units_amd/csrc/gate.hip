@@ -10,7 +10,10 @@
 // function of its own so that its instructions can be looked at) writes the envelope over the input in LDS and the curve
 // index of every sample into bit words beside the tile, one bit per sample, eight words per row and buffer; emit, after the
 // walk's barrier, takes its four bits and evaluates the knee each selects.  The input sample stays in a register for the
-// second step, so the arithmetic is the reference's out-of-place call whichever buffers alias.
+// second step, so the arithmetic is the reference's out-of-place call whichever buffers alias.  The bit words are the Gate's
+// alone, so the kernel is its own and not follow_kernel of dynamics_device.h (the two knees held in one struct for it also
+// put pick() through a selected address: 80 bytes of scratch per lane); the flags, the end of the follower's step and the
+// bank around the kernel (dynamics_bank_core.h) are the shared ones.
 //
 // THE SAMPLE LOOP IS BOUNDED BY count ALONE: a sample is stepped again at most once, then the walk advances.  With
 // sCurves[1].sKnee.start <= sCurves[0].sKnee.end and taus in [0, 1] the reference never does more; with
@@ -18,28 +21,22 @@
 //
 // Inputs are finite: NaN is out of scope.  Subnormal envelopes are kept (the float32 denormal mode is on).
 #include "gate_bank.h"
-#include "tile_chain_device.h"
+#include "dynamics_bank_core.h"
 
 #include <lsp-plug.in/dsp-units/units.h>
 
 #include <cmath>
-#include <cstring>
-#include <new>
-#include <vector>
 
 #pragma clang fp contract(off)      // every product and every sum below rounds on its own, host and device
 
 namespace
 {
-    using namespace mi_tile_chain;
+    using namespace mi_dynamics;
     using lsp::dspu::millis_to_samples;
 
-    constexpr int CURVE_BLOCK = 256;
     constexpr int WORDS = TILE / 32;                                // bit words of a row: one bit per sample
 
     typedef __attribute__((address_space(3))) uint32_t lds_u32;
-
-    enum { VEC_IN = 1, VEC_GAIN = 2, VEC_ENV = 4, VEC_AUDIO = 8 };
 
     struct gate_state { float e, peak; uint32_t hold, curve; };     // in registers, and [channels] between calls
 
@@ -49,11 +46,7 @@ namespace
         const float d = s - e;
         const bool neg = d < 0.0f;
         const float en = e + (neg ? tr : ta) * d;
-        const bool held = neg && hold > 0;
-        const bool rearm = !neg && en >= peak;
-        e = held ? e : en;
-        peak = ((neg && !held) || rearm) ? en : peak;
-        hold = held ? hold - 1 : rearm ? nhold : hold;
+        MI_FOLLOW_SETTLE(e, peak, hold, neg, en, nhold);
     }
 
     // ... over samples [0, n) of one row in LDS, in place: row[i] becomes the envelope, bit i of bits[] the curve of sample i
@@ -248,73 +241,36 @@ namespace
         }
     }
 
-    // Gate::construct, Gate.cpp:41-74
-    mi_gate_settings_t fresh_settings()
+} // namespace
+
+struct mi_gate_bank : mi_dynamics::bank<mi_gate_settings_t, mi_gate_params_t, gate_state>
+{
+    static constexpr const char *NAME = "mi_gate_bank";
+
+    static mi_gate_settings_t fresh_settings()                                  // Gate::construct, Gate.cpp:41-74
     {
         mi_gate_settings_t s = {};
         s.zone[0] = s.zone[1] = 1.0f;
         return s;
     }
-} // namespace
-
-struct mi_gate_bank
-{
-    uint32_t                            channels = 0;
-    std::vector<mi_gate_settings_t>     cfg;            // the setters' values
-    std::vector<uint8_t>                update;         // bUpdate of every channel
-    std::vector<mi_gate_params_t>       params;         // what update_settings computed
-    mi::dirty_range                     up;             // where params differs from the device table
-    mi_gate_params_t                   *d_params = nullptr;     // [channels]
-    gate_state                         *d_state = nullptr;      // [channels]
+    static mi_gate_params_t fresh_params() { return mi_gate_params_t{}; }
+    static void compute(const mi_gate_settings_t &s, mi_gate_params_t &p) { compute_params(s, p); }
+    template <class... Args> static void launch(dim3 grid, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, Args... args)
+    {
+        MI_LAUNCH(gate_kernel, grid, dim3(BLOCK), 0, st, ev0, ev1, args...);
+    }
 };
-
-namespace
-{
-    // update_settings of every channel whose bUpdate is set; the changed stretch of the table goes to the device
-    int gate_update(mi_gate_bank *b, hipStream_t st)
-    {
-        for (uint32_t ch = 0; ch < b->channels; ++ch)
-        {
-            if (!b->update[ch])
-                continue;
-            compute_params(b->cfg[ch], b->params[ch]);
-            b->update[ch] = 0;
-            b->up.touch(ch);
-        }
-        return mi::upload_dirty("mi_gate_bank", b->d_params, b->params.data(), b->up, st);
-    }
-
-    int gate_launch(mi_gate_bank *b, float *gain, float *env, const float *in, const float *audio, size_t count,
-                    size_t gain_stride, size_t env_stride, size_t in_stride, size_t audio_stride, hipStream_t st)
-    {
-        const uint32_t vec = (mi::aligned16(in, in_stride, b->channels) ? VEC_IN : 0) | (mi::aligned16(gain, gain_stride, b->channels) ? VEC_GAIN : 0) |
-                             (mi::aligned16(env, env_stride, b->channels) ? VEC_ENV : 0) | (mi::aligned16(audio, audio_stride, b->channels) ? VEC_AUDIO : 0);
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        mi::take_profile_events(&ev0, &ev1);
-        MI_LAUNCH(gate_kernel, dim3((b->channels + GROUP - 1) / GROUP), dim3(BLOCK), 0, st, ev0, ev1, gain, env, in, audio,
-                  gain_stride, env_stride, in_stride, audio_stride, uint32_t(count), b->channels, b->d_params, b->d_state, vec);
-        MI_HIP_CHECK(hipGetLastError());
-        return MI_OK;
-    }
-} // namespace
 
 namespace mi
 {
     int gate_bank_set_params(mi_gate_bank_t *b, uint32_t channel, const mi_gate_params_t *p)
     {
-        MI_REQUIRE(b != nullptr && p != nullptr && channel < b->channels, MI_EINVAL, "gate_bank_set_params: bad argument");
-        if (b->update[channel] == 0 && memcmp(&b->params[channel], p, sizeof(*p)) == 0)
-            return MI_OK;
-        b->params[channel] = *p;
-        b->update[channel] = 0;
-        b->up.touch(channel);
-        return MI_OK;
+        return mi_dynamics::set_params(b, "gate_bank_set_params", channel, p);
     }
 
     int gate_bank_set_state(mi_gate_bank_t *b, uint32_t channel, float envelope, float peak, uint32_t hold, uint32_t curve, hipStream_t st)
     {
-        MI_REQUIRE(b != nullptr && channel < b->channels && curve <= 1, MI_EINVAL, "gate_bank_set_state: bad argument");
-        return mi::write_state(b->d_state + channel, gate_state{ envelope, peak, hold, curve }, st);
+        return mi_dynamics::set_state(b, "gate_bank_set_state", channel, gate_state{ envelope, peak, hold, curve }, curve <= 1, st);
     }
 }
 
@@ -323,43 +279,19 @@ extern "C" {
 int mi_gate_compute_params(const mi_gate_settings_t *settings, mi_gate_params_t *params)
 {
     MI_REQUIRE(settings != nullptr && params != nullptr, MI_EINVAL, "mi_gate_compute_params: NULL argument");
-    *params = mi_gate_params_t{};
+    *params = mi_gate_bank::fresh_params();
     compute_params(*settings, *params);
     return MI_OK;
 }
 
 int mi_gate_bank_create(mi_gate_bank_t **bank, uint32_t channels)                       // Gate.cpp:41-74
 {
-    MI_REQUIRE(bank != nullptr, MI_EINVAL, "mi_gate_bank_create: NULL result pointer");
-    *bank = nullptr;
-    MI_REQUIRE(channels > 0 && channels <= (1u << 20), MI_EINVAL, "mi_gate_bank_create: channels must be 1 .. 1048576");
-    MI_REQUIRE(mi_dspu_device_count() > 0, MI_ENODEV, "no HIP device available (there is no CPU fallback)");
-    mi_gate_bank *b = new (std::nothrow) mi_gate_bank();
-    MI_REQUIRE(b != nullptr, MI_ENOMEM, "mi_gate_bank_create: out of host memory");
-    b->channels = channels;
-    b->cfg.assign(channels, fresh_settings());
-    b->update.assign(channels, 1);
-    b->params.assign(channels, mi_gate_params_t{});
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_params), size_t(channels) * sizeof(mi_gate_params_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_state), size_t(channels) * sizeof(gate_state));
-    if (e == hipSuccess) e = hipMemcpy(b->d_params, b->params.data(), size_t(channels) * sizeof(mi_gate_params_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(b->d_state, 0, size_t(channels) * sizeof(gate_state));
-    if (e != hipSuccess)
-    {
-        mi_gate_bank_destroy(b);
-        return mi::fail(MI_EHIP, "mi_gate_bank_create: %s", hipGetErrorString(e));
-    }
-    *bank = b;
-    return MI_OK;
+    return mi_dynamics::create(bank, "mi_gate_bank_create", channels);
 }
 
 int mi_gate_bank_destroy(mi_gate_bank_t *b)
 {
-    if (b == nullptr)
-        return MI_OK;
-    (void)hipFree(b->d_params); (void)hipFree(b->d_state);
-    delete b;
-    return MI_OK;
+    return mi_dynamics::destroy(b);
 }
 
 int mi_gate_bank_set_sample_rate(mi_gate_bank_t *b, uint32_t channel, uint32_t sample_rate)               // :138-144
@@ -425,32 +357,24 @@ int mi_gate_bank_set_hold(mi_gate_bank_t *b, uint32_t channel, float hold)      
 
 int mi_gate_bank_update_settings(mi_gate_bank_t *b, void *stream)                                          // :180-205
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_gate_bank_update_settings: NULL bank");
-    return gate_update(b, mi::as_stream(stream));
+    return mi_dynamics::update_settings(b, "mi_gate_bank_update_settings", stream);
 }
 
 int mi_gate_bank_clear(mi_gate_bank_t *b, void *stream)
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_gate_bank_clear: NULL bank");
-    MI_HIP_CHECK(hipMemsetAsync(b->d_state, 0, size_t(b->channels) * sizeof(gate_state), mi::as_stream(stream)));
-    return MI_OK;
+    return mi_dynamics::clear(b, "mi_gate_bank_clear", stream);
 }
 
 int mi_gate_bank_get_params(const mi_gate_bank_t *b, uint32_t channel, mi_gate_params_t *params)
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_gate_bank_get_params: NULL bank");
-    MI_REQUIRE(channel < b->channels && params != nullptr, MI_EINVAL, "mi_gate_bank_get_params: bad argument");
-    *params = b->params[channel];
-    return MI_OK;
+    return mi_dynamics::get_params(b, "mi_gate_bank_get_params", channel, params);
 }
 
 int mi_gate_bank_get_state(mi_gate_bank_t *b, uint32_t channel, float *envelope, float *peak, uint32_t *hold, uint32_t *curve,
                            void *stream)
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_gate_bank_get_state: NULL bank");
-    MI_REQUIRE(channel < b->channels, MI_EINVAL, "mi_gate_bank_get_state: channel %u out of range", channel);
     gate_state s;
-    const int r = mi::read_state(&s, b->d_state + channel, mi::as_stream(stream));
+    const int r = mi_dynamics::get_state(b, "mi_gate_bank_get_state", channel, &s, stream);
     if (r != MI_OK)
         return r;
     if (envelope != nullptr) *envelope = s.e;
@@ -463,58 +387,24 @@ int mi_gate_bank_get_state(mi_gate_bank_t *b, uint32_t channel, float *envelope,
 int mi_gate_bank_process(mi_gate_bank_t *b, float *gain, float *env, const float *in, size_t count,
                          size_t gain_stride, size_t env_stride, size_t in_stride, void *stream)           // :267-367
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_gate_bank_process: NULL bank");
-    hipStream_t st = mi::as_stream(stream);
-    const int r = gate_update(b, st);
-    if (r != MI_OK || count == 0)
-        return r;
-    MI_REQUIRE(gain != nullptr && in != nullptr, MI_EINVAL, "mi_gate_bank_process: NULL buffer");
-    MI_REQUIRE(count < (size_t(1) << 31), MI_EINVAL, "mi_gate_bank_process: count %zu too large", count);
-    MI_REQUIRE(b->channels == 1 || (gain_stride >= count && in_stride >= count && (env == nullptr || env_stride >= count)), MI_EINVAL,
-               "mi_gate_bank_process: strides (%zu, %zu, %zu) shorter than count %zu", gain_stride, env_stride, in_stride, count);
-    MI_REQUIRE(gain != env, MI_EINVAL, "mi_gate_bank_process: gain and env are the same buffer");
-    MI_REQUIRE((gain != in || gain_stride == in_stride) && (env != in || env_stride == in_stride), MI_EINVAL,
-               "mi_gate_bank_process: in place with different strides");
-    return gate_launch(b, gain, env, in, nullptr, count, gain_stride, env_stride, in_stride, 0, st);
+    return mi_dynamics::process(b, "mi_gate_bank_process", gain, env, in, count, gain_stride, env_stride, in_stride, stream);
 }
 
 int mi_gate_bank_process_apply(mi_gate_bank_t *b, float *dst, const float *audio, const float *sc, size_t count,
                                size_t dst_stride, size_t audio_stride, size_t sc_stride, void *stream)
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_gate_bank_process_apply: NULL bank");
-    hipStream_t st = mi::as_stream(stream);
-    const int r = gate_update(b, st);
-    if (r != MI_OK || count == 0)
-        return r;
-    MI_REQUIRE(dst != nullptr && audio != nullptr && sc != nullptr, MI_EINVAL, "mi_gate_bank_process_apply: NULL buffer");
-    MI_REQUIRE(count < (size_t(1) << 31), MI_EINVAL, "mi_gate_bank_process_apply: count %zu too large", count);
-    MI_REQUIRE(b->channels == 1 || (dst_stride >= count && audio_stride >= count && sc_stride >= count), MI_EINVAL,
-               "mi_gate_bank_process_apply: strides (%zu, %zu, %zu) shorter than count %zu", dst_stride, audio_stride, sc_stride, count);
-    MI_REQUIRE((dst != audio || dst_stride == audio_stride) && (dst != sc || dst_stride == sc_stride), MI_EINVAL,
-               "mi_gate_bank_process_apply: in place with different strides");
-    return gate_launch(b, dst, nullptr, sc, audio, count, dst_stride, 0, sc_stride, audio_stride, st);
+    return mi_dynamics::process_apply(b, "mi_gate_bank_process_apply", dst, audio, sc, count, dst_stride, audio_stride, sc_stride, stream);
 }
 
 int mi_gate_bank_curve(mi_gate_bank_t *b, float *out, const float *in, size_t dots, int hyst, size_t out_stride, size_t in_stride,
                        void *stream)                                                                       // :207-226
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_gate_bank_curve: NULL bank");
-    hipStream_t st = mi::as_stream(stream);
-    const int r = gate_update(b, st);
-    if (r != MI_OK || dots == 0)
-        return r;
-    MI_REQUIRE(out != nullptr && in != nullptr, MI_EINVAL, "mi_gate_bank_curve: NULL buffer");
-    MI_REQUIRE(dots < (size_t(1) << 31), MI_EINVAL, "mi_gate_bank_curve: %zu dots are too many", dots);
-    MI_REQUIRE(b->channels <= 65535u, MI_EINVAL, "mi_gate_bank_curve: more than 65535 channels");
-    MI_REQUIRE(b->channels == 1 || (out_stride >= dots && in_stride >= dots), MI_EINVAL,
-               "mi_gate_bank_curve: strides (%zu, %zu) shorter than %zu dots", out_stride, in_stride, dots);
-    MI_REQUIRE(out != in || out_stride == in_stride, MI_EINVAL, "mi_gate_bank_curve: in place with different strides");
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    mi::take_profile_events(&ev0, &ev1);
-    MI_LAUNCH(gate_curve_kernel, dim3(uint32_t((dots + CURVE_BLOCK - 1) / CURVE_BLOCK), b->channels), dim3(CURVE_BLOCK), 0, st,
-              ev0, ev1, out, in, out_stride, in_stride, uint32_t(dots), b->d_params, uint32_t(hyst != 0 ? 1 : 0));
-    MI_HIP_CHECK(hipGetLastError());
-    return MI_OK;
+    return mi_dynamics::curve(b, "mi_gate_bank_curve", out, in, dots, out_stride, in_stride, stream,
+                              [&](dim3 grid, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1)
+    {
+        MI_LAUNCH(gate_curve_kernel, grid, dim3(CURVE_BLOCK), 0, st, ev0, ev1, out, in, out_stride, in_stride, uint32_t(dots),
+                  b->d_params, uint32_t(hyst != 0 ? 1 : 0));
+    });
 }
 
 } // extern "C"

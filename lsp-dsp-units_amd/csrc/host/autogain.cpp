@@ -10,12 +10,11 @@
 
 #include <cmath>
 #include <cstring>
-#include <mutex>
 #include <new>
-#include <unordered_map>
 #include <vector>
 
 #include "autogain_bank.h"
+#include "beside.h"
 
 #pragma clang fp contract(off)      // update() rounds every product and every sum on its own
 
@@ -707,86 +706,20 @@ namespace dspu
 {
 namespace
 {
-    // a bank of one channel and a staging buffer beside an object, keyed by its address
-    template <class Bank> struct beside
+    // the state as the device holds it, beside the object (beside.h)
+    struct autogain_held { float gain = 1.0f, out = 1.0f; uint32_t surge = 0; };
+    struct simple_held { float gain = 1.0f; };
+    typedef mi_host::registry<mi_autogain_bank_t, autogain_held, mi_autogain_bank_create, mi_autogain_bank_destroy> autogains;
+    typedef mi_host::registry<mi_simple_autogain_bank_t, simple_held, mi_simple_autogain_bank_create, mi_simple_autogain_bank_destroy> simples;
+
+    int send_autogain_state(mi_autogain_bank_t *bank, const autogain_held &s)
     {
-        Bank   *bank = nullptr;
-        float  *d_buf = nullptr;            // [rows][cap]
-        size_t  cap = 0, rows = 0;
-        float   gain = 1.0f, out = 1.0f;    // the state as the device holds it: a fresh bank's, then what process() read back
-        uint32_t surge = 0;
-
-        bool reserve(size_t n, size_t nrows)
-        {
-            if (n <= cap && nrows <= rows)
-                return true;
-            mi_dspu_free(d_buf);
-            d_buf = nullptr;
-            cap = rows = 0;
-            if (mi_dspu_malloc(reinterpret_cast<void **>(&d_buf), nrows * n * sizeof(float)) != MI_OK)
-                return false;
-            cap = n, rows = nrows;
-            return true;
-        }
-    };
-
-    int make_bank(mi_autogain_bank_t **b)           { return mi_autogain_bank_create(b, 1); }
-    int make_bank(mi_simple_autogain_bank_t **b)    { return mi_simple_autogain_bank_create(b, 1); }
-    void free_bank(mi_autogain_bank_t *b)           { mi_autogain_bank_destroy(b); }
-    void free_bank(mi_simple_autogain_bank_t *b)    { mi_simple_autogain_bank_destroy(b); }
-
-    template <class Bank> struct registry
-    {
-        std::mutex lock;
-        std::unordered_map<const void *, beside<Bank> *> table;
-
-        beside<Bank> *of(const void *self)
-        {
-            std::lock_guard<std::mutex> guard(lock);
-            auto it = table.find(self);
-            if (it != table.end())
-                return it->second;
-            beside<Bank> *p = new (std::nothrow) beside<Bank>();
-            if (p == nullptr)
-                return nullptr;
-            if (make_bank(&p->bank) != MI_OK)
-            {
-                delete p;
-                return nullptr;
-            }
-            table[self] = p;
-            return p;
-        }
-
-        void drop(const void *self)
-        {
-            beside<Bank> *p = nullptr;
-            {
-                std::lock_guard<std::mutex> guard(lock);
-                auto it = table.find(self);
-                if (it == table.end())
-                    return;
-                p = it->second;
-                table.erase(it);
-            }
-            free_bank(p->bank);
-            mi_dspu_free(p->d_buf);
-            delete p;
-        }
-    };
-
-    registry<mi_autogain_bank_t> &autogains()
-    {
-        static registry<mi_autogain_bank_t> r;
-        return r;
+        return mi::autogain_bank_set_state(bank, 0, s.gain, s.out, s.surge, nullptr);
     }
-    registry<mi_simple_autogain_bank_t> &simples()
+    int send_simple_state(mi_simple_autogain_bank_t *bank, const simple_held &s)
     {
-        static registry<mi_simple_autogain_bank_t> r;
-        return r;
+        return mi::simple_autogain_bank_set_state(bank, 0, s.gain, nullptr);
     }
-
-    inline bool same_bits(float a, float b) { return memcmp(&a, &b, sizeof(a)) == 0; }
 }
 
 AutoGain::AutoGain()  { construct(); }
@@ -794,7 +727,7 @@ AutoGain::~AutoGain() { destroy(); }
 
 void AutoGain::construct()                                      // AutoGain.cpp:43-66
 {
-    autogains().drop(this);                                     // whatever lived at this address before
+    autogains::drop(this);                                      // whatever lived at this address before
     nSampleRate = 0;
     sShort.fGrow = sShort.fFall = sShort.fKGrow = sShort.fKFall = 0.0f;
     sLong.fGrow = sLong.fFall = sLong.fKGrow = sLong.fKFall = 0.0f;
@@ -810,7 +743,7 @@ void AutoGain::construct()                                      // AutoGain.cpp:
 
 void AutoGain::destroy()                                        // :68-70
 {
-    autogains().drop(this);
+    autogains::drop(this);
 }
 
 void AutoGain::init_compressor(compressor_t &c)                 // :72-81
@@ -914,7 +847,7 @@ void AutoGain::update()                                         // :155-173
 void AutoGain::run(float *vca, const float *llong, const float *lshort, const float *lexp, float level, size_t count)
 {
     update();
-    beside<mi_autogain_bank_t> *p = autogains().of(this);
+    autogains::entry *p = autogains::of(this);
     if (p == nullptr || count == 0 || !p->reserve(count, 3))
         return;
     mi_autogain_params_t q;
@@ -926,12 +859,8 @@ void AutoGain::run(float *vca, const float *llong, const float *lshort, const fl
     if (mi::autogain_bank_set_params(p->bank, 0, &q) != MI_OK)
         return;
     const uint32_t surge = uint32_t(nFlags) & (MI_AG_SURGE_UP | MI_AG_SURGE_DOWN);
-    if (!same_bits(fCurrGain, p->gain) || !same_bits(fOutGain, p->out) || surge != p->surge)
-    {
-        if (mi::autogain_bank_set_state(p->bank, 0, fCurrGain, fOutGain, surge, nullptr) != MI_OK)
-            return;
-        p->gain = fCurrGain, p->out = fOutGain, p->surge = surge;
-    }
+    if (!p->hand_over_state({ fCurrGain, fOutGain, surge }, send_autogain_state))
+        return;
     float *d_long = p->d_buf, *d_short = d_long + p->cap, *d_exp = d_short + p->cap;
     const size_t bytes = count * sizeof(float);
     if (mi_dspu_copy_h2d(d_long, llong, bytes, nullptr) != MI_OK || mi_dspu_copy_h2d(d_short, lshort, bytes, nullptr) != MI_OK)
@@ -948,11 +877,11 @@ void AutoGain::run(float *vca, const float *llong, const float *lshort, const fl
     if (mi_dspu_copy_d2h(vca, d_long, bytes, nullptr) != MI_OK)
         return;
     uint32_t flags = 0;
-    if (mi_autogain_bank_get_state(p->bank, 0, &p->gain, &p->out, &flags, nullptr) != MI_OK)
+    if (mi_autogain_bank_get_state(p->bank, 0, &p->held.gain, &p->held.out, &flags, nullptr) != MI_OK)
         return;
-    p->surge = flags & (MI_AG_SURGE_UP | MI_AG_SURGE_DOWN);
-    fCurrGain = p->gain, fOutGain = p->out;
-    nFlags = (nFlags & ~size_t(F_SURGE_UP | F_SURGE_DOWN)) | p->surge;
+    p->held.surge = flags & (MI_AG_SURGE_UP | MI_AG_SURGE_DOWN);
+    fCurrGain = p->held.gain, fOutGain = p->held.out;
+    nFlags = (nFlags & ~size_t(F_SURGE_UP | F_SURGE_DOWN)) | p->held.surge;
 }
 
 void AutoGain::process(float *vca, const float *llong, const float *lshort, const float *lexp, size_t count)   // :278-286
@@ -1007,7 +936,7 @@ SimpleAutoGain::~SimpleAutoGain() { destroy(); }
 
 void SimpleAutoGain::construct()                                // SimpleAutoGain.cpp:43-56
 {
-    simples().drop(this);
+    simples::drop(this);
     nSampleRate = 0;
     nFlags = F_UPDATE;
     fKGrow = 0.0f;
@@ -1022,7 +951,7 @@ void SimpleAutoGain::construct()                                // SimpleAutoGai
 
 void SimpleAutoGain::destroy()                                  // :58-60
 {
-    simples().drop(this);
+    simples::drop(this);
 }
 
 status_t SimpleAutoGain::init()                                 // :62-66
@@ -1110,24 +1039,20 @@ void SimpleAutoGain::update()                                   // :142-153
 void SimpleAutoGain::process(float *dst, const float *src, size_t count)        // :155-175
 {
     update();
-    beside<mi_simple_autogain_bank_t> *p = simples().of(this);
+    simples::entry *p = simples::of(this);
     if (p == nullptr || count == 0 || !p->reserve(count, 1))
         return;
     const mi_simple_autogain_params_t q = { fKGrow, fKFall, fThreshold, fMinGain, fMaxGain };
     if (mi::simple_autogain_bank_set_params(p->bank, 0, &q) != MI_OK)
         return;
-    if (!same_bits(fCurrGain, p->gain))
-    {
-        if (mi::simple_autogain_bank_set_state(p->bank, 0, fCurrGain, nullptr) != MI_OK)
-            return;
-        p->gain = fCurrGain;
-    }
+    if (!p->hand_over_state({ fCurrGain }, send_simple_state))
+        return;
     if (mi_dspu_copy_h2d(p->d_buf, src, count * sizeof(float), nullptr) != MI_OK ||
         mi_simple_autogain_bank_process(p->bank, p->d_buf, p->d_buf, count, count, count, nullptr) != MI_OK ||
         mi_dspu_copy_d2h(dst, p->d_buf, count * sizeof(float), nullptr) != MI_OK ||
-        mi_simple_autogain_bank_get_state(p->bank, 0, &p->gain, nullptr) != MI_OK)
+        mi_simple_autogain_bank_get_state(p->bank, 0, &p->held.gain, nullptr) != MI_OK)
         return;
-    fCurrGain = p->gain;
+    fCurrGain = p->held.gain;
 }
 
 float SimpleAutoGain::process(float src)                        // :177-194: one sample on the device

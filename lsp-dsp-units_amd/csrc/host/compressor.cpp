@@ -1,18 +1,14 @@
 // lsp::dspu::Compressor (src/main/dynamics/Compressor.cpp) on a mi_compressor_bank of one channel.  The class has no member
-// to hang the bank on (its 132 bytes are the reference's), so the bank and its staging buffers live in a table keyed by the
-// object's address: made at the first call that needs the device, dropped in destroy() and in construct().  Before every
-// device call the bank is handed the object's own fTau*, fReleaseThresh, nHold and sComp; process() also sends fEnvelope,
-// fPeak and nHoldCounter when they are not what it read back after the previous call (a subclass may write the protected
-// fields), and reads them back afterwards.  An object whose storage is released without destroy() or its destructor leaves
-// its entry behind until a Compressor is constructed at that address again.
+// to hang the bank on (its 132 bytes are the reference's), so the bank and its staging buffers live beside the object
+// (beside.h).  Before every device call the bank is handed the object's own fTau*, fReleaseThresh, nHold and sComp;
+// process() also sends fEnvelope, fPeak and nHoldCounter when they are not what it read back after the previous call (a
+// subclass may write the protected fields), and reads them back afterwards.
 #include <lsp-plug.in/dsp-units/dynamics/Compressor.h>
 
 #include <cmath>
 #include <cstring>
-#include <mutex>
-#include <new>
-#include <unordered_map>
 
+#include "beside.h"
 #include "compressor_bank.h"
 
 namespace lsp
@@ -21,70 +17,7 @@ namespace dspu
 {
 namespace
 {
-    struct compressor_impl
-    {
-        mi_compressor_bank_t *bank = nullptr;
-        float  *d_buf = nullptr;            // [2][cap]: the staged input (gain in place on it), the envelope
-        size_t  cap = 0;
-        float   e = 0.0f, peak = 0.0f;      // the follower's state as the device holds it: a fresh bank's, then what
-        uint32_t hold = 0;                  // process() read back
-
-        bool reserve(size_t n)
-        {
-            if (n <= cap)
-                return true;
-            mi_dspu_free(d_buf);
-            d_buf = nullptr;
-            cap = 0;
-            if (mi_dspu_malloc(reinterpret_cast<void **>(&d_buf), 2 * n * sizeof(float)) != MI_OK)
-                return false;
-            cap = n;
-            return true;
-        }
-    };
-
-    std::mutex g_lock;
-    std::unordered_map<const void *, compressor_impl *> &table()
-    {
-        static std::unordered_map<const void *, compressor_impl *> t;
-        return t;
-    }
-
-    compressor_impl *impl_of(const void *self, bool make)
-    {
-        std::lock_guard<std::mutex> guard(g_lock);
-        auto it = table().find(self);
-        if (it != table().end())
-            return it->second;
-        if (!make)
-            return nullptr;
-        compressor_impl *p = new (std::nothrow) compressor_impl();
-        if (p == nullptr)
-            return nullptr;
-        if (mi_compressor_bank_create(&p->bank, 1) != MI_OK)
-        {
-            delete p;
-            return nullptr;
-        }
-        table()[self] = p;
-        return p;
-    }
-
-    void drop(const void *self)
-    {
-        compressor_impl *p = nullptr;
-        {
-            std::lock_guard<std::mutex> guard(g_lock);
-            auto it = table().find(self);
-            if (it == table().end())
-                return;
-            p = it->second;
-            table().erase(it);
-        }
-        mi_compressor_bank_destroy(p->bank);
-        mi_dspu_free(p->d_buf);
-        delete p;
-    }
+    typedef mi_host::registry<mi_compressor_bank_t, mi_host::follow_held, mi_compressor_bank_create, mi_compressor_bank_destroy> besides;
 
     inline float knee_gain(float x, float lx, const dsp::compressor_knee_t &k)     // Compressor.cpp:302-307
     {
@@ -107,7 +40,7 @@ Compressor::~Compressor() { destroy(); }
 
 void Compressor::construct()                                    // Compressor.cpp:46-83
 {
-    drop(this);                                                 // whatever lived at this address before
+    besides::drop(this);                                        // whatever lived at this address before
     fAttackThresh = 0.0f;
     fReleaseThresh = 0.0f;
     fBoostThresh = float(2.5119e-4);                            // GAIN_AMP_M_72_DB
@@ -138,7 +71,7 @@ void Compressor::construct()                                    // Compressor.cp
 
 void Compressor::destroy()                                      // :85-87
 {
-    drop(this);
+    besides::drop(this);
 }
 
 void Compressor::update_settings()                              // :89-220
@@ -169,7 +102,7 @@ void Compressor::update_settings()                              // :89-220
 namespace
 {
     // the object's computed fields as the bank's channel 0
-    bool hand_over(compressor_impl *p, float ta, float tr, float rt, uint32_t hold, const dsp::compressor_x2_t &c)
+    bool hand_over(besides::entry *p, float ta, float tr, float rt, uint32_t hold, const dsp::compressor_x2_t &c)
     {
         mi_compressor_params_t q;
         q.tau_attack = ta;
@@ -180,25 +113,19 @@ namespace
         return mi::compressor_bank_set_params(p->bank, 0, &q) == MI_OK;
     }
 
-    // the object's follower state as the bank's, where the fields are not what the device holds
-    bool hand_over_state(compressor_impl *p, float e, float peak, uint32_t hold)
+    int send_state(mi_compressor_bank_t *bank, const mi_host::follow_held &s)
     {
-        if (memcmp(&e, &p->e, sizeof(e)) == 0 && memcmp(&peak, &p->peak, sizeof(peak)) == 0 && hold == p->hold)
-            return true;
-        if (mi::compressor_bank_set_state(p->bank, 0, e, peak, hold, nullptr) != MI_OK)
-            return false;
-        p->e = e, p->peak = peak, p->hold = hold;
-        return true;
+        return mi::compressor_bank_set_state(bank, 0, s.e, s.peak, s.hold, nullptr);
     }
 }
 
 void Compressor::process(float *out, float *env, const float *in, size_t samples)      // :222-267
 {
     update_settings();
-    compressor_impl *p = impl_of(this, true);
-    if (p == nullptr || samples == 0 || !p->reserve(samples) ||
+    besides::entry *p = besides::of(this);
+    if (p == nullptr || samples == 0 || !p->reserve(samples, 2) ||
         !hand_over(p, fTauAttack, fTauRelease, fReleaseThresh, nHold, sComp) ||
-        !hand_over_state(p, fEnvelope, fPeak, uint32_t(nHoldCounter)))
+        !p->hand_over_state({ fEnvelope, fPeak, uint32_t(nHoldCounter) }, send_state))
         return;
     float *d_in = p->d_buf, *d_env = p->d_buf + p->cap;
     if (mi_dspu_copy_h2d(d_in, in, samples * sizeof(float), nullptr) != MI_OK ||
@@ -207,9 +134,9 @@ void Compressor::process(float *out, float *env, const float *in, size_t samples
         return;
     if (env != nullptr && mi_dspu_copy_d2h(env, d_env, samples * sizeof(float), nullptr) != MI_OK)
         return;
-    if (mi_compressor_bank_get_state(p->bank, 0, &p->e, &p->peak, &p->hold, nullptr) != MI_OK)
+    if (mi_compressor_bank_get_state(p->bank, 0, &p->held.e, &p->held.peak, &p->held.hold, nullptr) != MI_OK)
         return;
-    fEnvelope = p->e, fPeak = p->peak, nHoldCounter = p->hold;
+    fEnvelope = p->held.e, fPeak = p->held.peak, nHoldCounter = p->held.hold;
 }
 
 float Compressor::process(float *env, float in)                 // :269-311: one sample on the device
@@ -223,8 +150,8 @@ float Compressor::process(float *env, float in)                 // :269-311: one
 
 void Compressor::curve(float *out, const float *in, size_t dots)                        // :313-316
 {
-    compressor_impl *p = impl_of(this, true);
-    if (p == nullptr || dots == 0 || !p->reserve(dots) ||
+    besides::entry *p = besides::of(this);
+    if (p == nullptr || dots == 0 || !p->reserve(dots, 2) ||
         !hand_over(p, fTauAttack, fTauRelease, fReleaseThresh, nHold, sComp))
         return;
     if (mi_dspu_copy_h2d(p->d_buf, in, dots * sizeof(float), nullptr) == MI_OK &&

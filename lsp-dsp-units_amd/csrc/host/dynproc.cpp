@@ -1,19 +1,16 @@
 // lsp::dspu::DynamicProcessor (src/main/dynamics/DynamicProcessor.cpp): update_settings() in host float32
 // (mi_dynproc_compute_params, what mi_dynproc_bank runs for its dirty channels), and the class on a mi_dynproc_bank of one
-// channel, in the manner of host/expander.cpp: the class has no member to hang the bank on (its 400 bytes are the
-// reference's), so the bank and its staging buffers live in a table keyed by the object's address: made at the first call
-// that needs the device, dropped in destroy() and in construct().  Before every device call the bank is handed the object's
-// own fCount, nHold, vAttack, vRelease and vSplines; process() also sends fEnvelope, fPeak and nHoldCounter when they are not
-// what it read back after the previous call (the scalar process() steps them on the host), and reads them back afterwards.
+// channel.  The class has no member to hang the bank on (its 400 bytes are the reference's), so the bank and its staging
+// buffers live beside the object (beside.h).  Before every device call the bank is handed the object's own fCount, nHold,
+// vAttack, vRelease and vSplines; process() also sends fEnvelope, fPeak and nHoldCounter when they are not what it read back
+// after the previous call (the scalar process() steps them on the host), and reads them back afterwards.
 #include <lsp-plug.in/dsp-units/dynamics/DynamicProcessor.h>
 #include <lsp-plug.in/dsp-units/units.h>
 
 #include <cmath>
 #include <cstring>
-#include <mutex>
-#include <new>
-#include <unordered_map>
 
+#include "beside.h"
 #include "dynproc_bank.h"
 
 #pragma clang fp contract(off)      // every product and every sum below rounds on its own, as the reference's build has it
@@ -152,73 +149,10 @@ namespace dspu
 {
 namespace
 {
-    struct dynproc_impl
-    {
-        mi_dynproc_bank_t *bank = nullptr;
-        float  *d_buf = nullptr;            // [2][cap]: the staged input (gain in place on it), the envelope
-        size_t  cap = 0;
-        float   e = 0.0f, peak = 0.0f;      // the follower's state as the device holds it
-        uint32_t hold = 0;
-
-        bool reserve(size_t n)
-        {
-            if (n <= cap)
-                return true;
-            mi_dspu_free(d_buf);
-            d_buf = nullptr;
-            cap = 0;
-            if (mi_dspu_malloc(reinterpret_cast<void **>(&d_buf), 2 * n * sizeof(float)) != MI_OK)
-                return false;
-            cap = n;
-            return true;
-        }
-    };
-
-    std::mutex g_lock;
-    std::unordered_map<const void *, dynproc_impl *> &table()
-    {
-        static std::unordered_map<const void *, dynproc_impl *> t;
-        return t;
-    }
-
-    dynproc_impl *impl_of(const void *self, bool make)
-    {
-        std::lock_guard<std::mutex> guard(g_lock);
-        auto it = table().find(self);
-        if (it != table().end())
-            return it->second;
-        if (!make)
-            return nullptr;
-        dynproc_impl *p = new (std::nothrow) dynproc_impl();
-        if (p == nullptr)
-            return nullptr;
-        if (mi_dynproc_bank_create(&p->bank, 1) != MI_OK)
-        {
-            delete p;
-            return nullptr;
-        }
-        table()[self] = p;
-        return p;
-    }
-
-    void drop(const void *self)
-    {
-        dynproc_impl *p = nullptr;
-        {
-            std::lock_guard<std::mutex> guard(g_lock);
-            auto it = table().find(self);
-            if (it == table().end())
-                return;
-            p = it->second;
-            table().erase(it);
-        }
-        mi_dynproc_bank_destroy(p->bank);
-        mi_dspu_free(p->d_buf);
-        delete p;
-    }
+    typedef mi_host::registry<mi_dynproc_bank_t, mi_host::follow_held, mi_dynproc_bank_create, mi_dynproc_bank_destroy> besides;
 
     // the object's computed fields as the bank's channel 0 (the three tables have the C-ABI's layouts)
-    bool hand_over(dynproc_impl *p, uint32_t splines, uint32_t attacks, uint32_t releases, uint32_t hold, const void *attack,
+    bool hand_over(besides::entry *p, uint32_t splines, uint32_t attacks, uint32_t releases, uint32_t hold, const void *attack,
                    const void *release, const void *spline)
     {
         mi_dynproc_params_t q = mi_dynproc_params_t();
@@ -229,15 +163,9 @@ namespace
         return mi::dynproc_bank_set_params(p->bank, 0, &q) == MI_OK;
     }
 
-    // the object's follower state as the bank's, where the fields are not what the device holds
-    bool hand_over_state(dynproc_impl *p, float e, float peak, uint32_t hold)
+    int send_state(mi_dynproc_bank_t *bank, const mi_host::follow_held &s)
     {
-        if (memcmp(&e, &p->e, sizeof(e)) == 0 && memcmp(&peak, &p->peak, sizeof(peak)) == 0 && hold == p->hold)
-            return true;
-        if (mi::dynproc_bank_set_state(p->bank, 0, e, peak, hold, nullptr) != MI_OK)
-            return false;
-        p->e = e, p->peak = peak, p->hold = hold;
-        return true;
+        return mi::dynproc_bank_set_state(bank, 0, s.e, s.peak, s.hold, nullptr);
     }
 
     inline float limited(float x, float lo)
@@ -260,7 +188,7 @@ DynamicProcessor::~DynamicProcessor() { destroy(); }
 
 void DynamicProcessor::construct()                              // DynamicProcessor.cpp:43-74
 {
-    drop(this);                                                 // whatever lived at this address before
+    besides::drop(this);                                        // whatever lived at this address before
     fInRatio = 1.0f;
     fOutRatio = 1.0f;
     fEnvelope = 0.0f;
@@ -293,7 +221,7 @@ void DynamicProcessor::construct()                              // DynamicProces
 
 void DynamicProcessor::destroy()                                // :76-78
 {
-    drop(this);
+    besides::drop(this);
 }
 
 // update_settings(), :339-395: computes whenever it is called, the caller asks modified() first.  ONE DIFFERENCE: the
@@ -349,10 +277,10 @@ float DynamicProcessor::solve_reaction(const reaction_t *s, float x, size_t coun
 
 void DynamicProcessor::process(float *out, float *env, const float *in, size_t samples)         // :397-442
 {
-    dynproc_impl *p = impl_of(this, true);
-    if (p == nullptr || samples == 0 || !p->reserve(samples) ||
+    besides::entry *p = besides::of(this);
+    if (p == nullptr || samples == 0 || !p->reserve(samples, 2) ||
         !hand_over(p, fCount[CT_SPLINES], fCount[CT_ATTACK], fCount[CT_RELEASE], nHold, vAttack, vRelease, vSplines) ||
-        !hand_over_state(p, fEnvelope, fPeak, nHoldCounter))
+        !p->hand_over_state({ fEnvelope, fPeak, nHoldCounter }, send_state))
         return;
     float *d_in = p->d_buf, *d_env = p->d_buf + p->cap;
     if (mi_dspu_copy_h2d(d_in, in, samples * sizeof(float), nullptr) != MI_OK ||
@@ -361,9 +289,9 @@ void DynamicProcessor::process(float *out, float *env, const float *in, size_t s
         return;
     if (env != nullptr && mi_dspu_copy_d2h(env, d_env, samples * sizeof(float), nullptr) != MI_OK)
         return;
-    if (mi_dynproc_bank_get_state(p->bank, 0, &p->e, &p->peak, &p->hold, nullptr) != MI_OK)
+    if (mi_dynproc_bank_get_state(p->bank, 0, &p->held.e, &p->held.peak, &p->held.hold, nullptr) != MI_OK)
         return;
-    fEnvelope = p->e, fPeak = p->peak, nHoldCounter = p->hold;
+    fEnvelope = p->held.e, fPeak = p->held.peak, nHoldCounter = p->held.hold;
 }
 
 float DynamicProcessor::process(float *env, float s)            // :444-472: on the host; the gain has the scalar limit
@@ -395,8 +323,8 @@ float DynamicProcessor::process(float *env, float s)            // :444-472: on 
 
 void DynamicProcessor::curve(float *out, const float *in, size_t dots)                  // :474-496
 {
-    dynproc_impl *p = impl_of(this, true);
-    if (p == nullptr || dots == 0 || !p->reserve(dots) ||
+    besides::entry *p = besides::of(this);
+    if (p == nullptr || dots == 0 || !p->reserve(dots, 2) ||
         !hand_over(p, fCount[CT_SPLINES], fCount[CT_ATTACK], fCount[CT_RELEASE], nHold, vAttack, vRelease, vSplines))
         return;
     if (mi_dspu_copy_h2d(p->d_buf, in, dots * sizeof(float), nullptr) == MI_OK &&
@@ -417,8 +345,8 @@ float DynamicProcessor::curve(float in)                         // :498-516
 
 void DynamicProcessor::model(float *out, const float *in, size_t dots)                  // :518-540
 {
-    dynproc_impl *p = impl_of(this, true);
-    if (p == nullptr || dots == 0 || !p->reserve(dots) ||
+    besides::entry *p = besides::of(this);
+    if (p == nullptr || dots == 0 || !p->reserve(dots, 2) ||
         !hand_over(p, fCount[CT_SPLINES], fCount[CT_ATTACK], fCount[CT_RELEASE], nHold, vAttack, vRelease, vSplines))
         return;
     if (mi_dspu_copy_h2d(p->d_buf, in, dots * sizeof(float), nullptr) == MI_OK &&

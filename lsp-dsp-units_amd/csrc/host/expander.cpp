@@ -1,17 +1,14 @@
-// lsp::dspu::Expander (src/main/dynamics/Expander.cpp) on a mi_expander_bank of one channel, in the manner of
-// host/compressor.cpp: the class has no member to hang the bank on (its 92 bytes are the reference's), so the bank and its
-// staging buffers live in a table keyed by the object's address: made at the first call that needs the device, dropped in
-// destroy() and in construct().  Before every device call the bank is handed the object's own fTau*, fReleaseThresh, nHold,
-// sExp and bUpward; process() also sends fEnvelope, fPeak and nHoldCounter when they are not what it read back after the
-// previous call, and reads them back afterwards.
+// lsp::dspu::Expander (src/main/dynamics/Expander.cpp) on a mi_expander_bank of one channel.  The class has no
+// member to hang the bank on (its 92 bytes are the reference's), so the bank and its staging buffers live beside the object
+// (beside.h).  Before every device call the bank is handed the object's own fTau*, fReleaseThresh, nHold, sExp and bUpward;
+// process() also sends fEnvelope, fPeak and nHoldCounter when they are not what it read back after the previous call, and
+// reads them back afterwards.
 #include <lsp-plug.in/dsp-units/dynamics/Expander.h>
 
 #include <cmath>
 #include <cstring>
-#include <mutex>
-#include <new>
-#include <unordered_map>
 
+#include "beside.h"
 #include "expander_bank.h"
 
 namespace lsp
@@ -20,73 +17,10 @@ namespace dspu
 {
 namespace
 {
-    struct expander_impl
-    {
-        mi_expander_bank_t *bank = nullptr;
-        float  *d_buf = nullptr;            // [2][cap]: the staged input (gain in place on it), the envelope
-        size_t  cap = 0;
-        float   e = 0.0f, peak = 0.0f;      // the follower's state as the device holds it
-        uint32_t hold = 0;
-
-        bool reserve(size_t n)
-        {
-            if (n <= cap)
-                return true;
-            mi_dspu_free(d_buf);
-            d_buf = nullptr;
-            cap = 0;
-            if (mi_dspu_malloc(reinterpret_cast<void **>(&d_buf), 2 * n * sizeof(float)) != MI_OK)
-                return false;
-            cap = n;
-            return true;
-        }
-    };
-
-    std::mutex g_lock;
-    std::unordered_map<const void *, expander_impl *> &table()
-    {
-        static std::unordered_map<const void *, expander_impl *> t;
-        return t;
-    }
-
-    expander_impl *impl_of(const void *self, bool make)
-    {
-        std::lock_guard<std::mutex> guard(g_lock);
-        auto it = table().find(self);
-        if (it != table().end())
-            return it->second;
-        if (!make)
-            return nullptr;
-        expander_impl *p = new (std::nothrow) expander_impl();
-        if (p == nullptr)
-            return nullptr;
-        if (mi_expander_bank_create(&p->bank, 1) != MI_OK)
-        {
-            delete p;
-            return nullptr;
-        }
-        table()[self] = p;
-        return p;
-    }
-
-    void drop(const void *self)
-    {
-        expander_impl *p = nullptr;
-        {
-            std::lock_guard<std::mutex> guard(g_lock);
-            auto it = table().find(self);
-            if (it == table().end())
-                return;
-            p = it->second;
-            table().erase(it);
-        }
-        mi_expander_bank_destroy(p->bank);
-        mi_dspu_free(p->d_buf);
-        delete p;
-    }
+    typedef mi_host::registry<mi_expander_bank_t, mi_host::follow_held, mi_expander_bank_create, mi_expander_bank_destroy> besides;
 
     // the object's computed fields as the bank's channel 0
-    bool hand_over(expander_impl *p, float ta, float tr, float rt, uint32_t hold, const dsp::expander_knee_t &k, bool upward)
+    bool hand_over(besides::entry *p, float ta, float tr, float rt, uint32_t hold, const dsp::expander_knee_t &k, bool upward)
     {
         mi_expander_params_t q;
         q.tau_attack = ta;
@@ -99,15 +33,9 @@ namespace
         return mi::expander_bank_set_params(p->bank, 0, &q) == MI_OK;
     }
 
-    // the object's follower state as the bank's, where the fields are not what the device holds
-    bool hand_over_state(expander_impl *p, float e, float peak, uint32_t hold)
+    int send_state(mi_expander_bank_t *bank, const mi_host::follow_held &s)
     {
-        if (memcmp(&e, &p->e, sizeof(e)) == 0 && memcmp(&peak, &p->peak, sizeof(peak)) == 0 && hold == p->hold)
-            return true;
-        if (mi::expander_bank_set_state(p->bank, 0, e, peak, hold, nullptr) != MI_OK)
-            return false;
-        p->e = e, p->peak = peak, p->hold = hold;
-        return true;
+        return mi::expander_bank_set_state(bank, 0, s.e, s.peak, s.hold, nullptr);
     }
 }
 
@@ -116,7 +44,7 @@ Expander::~Expander() { destroy(); }
 
 void Expander::construct()                                      // Expander.cpp:70-101
 {
-    drop(this);                                                 // whatever lived at this address before
+    besides::drop(this);                                        // whatever lived at this address before
     fAttackThresh = 0.0f;
     fReleaseThresh = 0.0f;
     fAttack = 0.0f;
@@ -142,7 +70,7 @@ void Expander::construct()                                      // Expander.cpp:
 
 void Expander::destroy()                                        // :103-105
 {
-    drop(this);
+    besides::drop(this);
 }
 
 void Expander::update_settings()                                // :200-245
@@ -172,10 +100,10 @@ void Expander::update_settings()                                // :200-245
 void Expander::process(float *out, float *env, const float *in, size_t samples)        // :247-292
 {
     update_settings();
-    expander_impl *p = impl_of(this, true);
-    if (p == nullptr || samples == 0 || !p->reserve(samples) ||
+    besides::entry *p = besides::of(this);
+    if (p == nullptr || samples == 0 || !p->reserve(samples, 2) ||
         !hand_over(p, fTauAttack, fTauRelease, fReleaseThresh, nHold, sExp, bUpward) ||
-        !hand_over_state(p, fEnvelope, fPeak, uint32_t(nHoldCounter)))
+        !p->hand_over_state({ fEnvelope, fPeak, uint32_t(nHoldCounter) }, send_state))
         return;
     float *d_in = p->d_buf, *d_env = p->d_buf + p->cap;
     if (mi_dspu_copy_h2d(d_in, in, samples * sizeof(float), nullptr) != MI_OK ||
@@ -184,9 +112,9 @@ void Expander::process(float *out, float *env, const float *in, size_t samples) 
         return;
     if (env != nullptr && mi_dspu_copy_d2h(env, d_env, samples * sizeof(float), nullptr) != MI_OK)
         return;
-    if (mi_expander_bank_get_state(p->bank, 0, &p->e, &p->peak, &p->hold, nullptr) != MI_OK)
+    if (mi_expander_bank_get_state(p->bank, 0, &p->held.e, &p->held.peak, &p->held.hold, nullptr) != MI_OK)
         return;
-    fEnvelope = p->e, fPeak = p->peak, nHoldCounter = p->hold;
+    fEnvelope = p->held.e, fPeak = p->held.peak, nHoldCounter = p->held.hold;
 }
 
 float Expander::process(float *env, float s)                    // :294-323: one sample on the device
@@ -200,8 +128,8 @@ float Expander::process(float *env, float s)                    // :294-323: one
 
 void Expander::curve(float *out, const float *in, size_t dots)                          // :325-331
 {
-    expander_impl *p = impl_of(this, true);
-    if (p == nullptr || dots == 0 || !p->reserve(dots) ||
+    besides::entry *p = besides::of(this);
+    if (p == nullptr || dots == 0 || !p->reserve(dots, 2) ||
         !hand_over(p, fTauAttack, fTauRelease, fReleaseThresh, nHold, sExp, bUpward))
         return;
     if (mi_dspu_copy_h2d(p->d_buf, in, dots * sizeof(float), nullptr) == MI_OK &&

@@ -1,17 +1,14 @@
-// lsp::dspu::Gate (src/main/dynamics/Gate.cpp) on a mi_gate_bank of one channel, in the manner of host/compressor.cpp: the
-// class has no member to hang the bank on (its 128 bytes are the reference's), so the bank and its staging buffers live in a
-// table keyed by the object's address: made at the first call that needs the device, dropped in destroy() and in
-// construct().  Before every device call the bank is handed the object's own fTau*, nHold and the two sKnee; process() also
-// sends fEnvelope, fPeak, nHoldCounter and nCurve when they are not what it read back after the previous call (the scalar
-// process() and a subclass write them), and reads them back afterwards.
+// lsp::dspu::Gate (src/main/dynamics/Gate.cpp) on a mi_gate_bank of one channel.  The class has no member to hang the
+// bank on (its 128 bytes are the reference's), so the bank and its staging buffers live beside the object (beside.h).  Before
+// every device call the bank is handed the object's own fTau*, nHold and the two sKnee; process() also sends fEnvelope, fPeak,
+// nHoldCounter and nCurve when they are not what it read back after the previous call (the scalar process() and a subclass
+// write them), and reads them back afterwards.
 #include <lsp-plug.in/dsp-units/dynamics/Gate.h>
 
 #include <cmath>
 #include <cstring>
-#include <mutex>
-#include <new>
-#include <unordered_map>
 
+#include "beside.h"
 #include "gate_bank.h"
 
 namespace lsp
@@ -20,73 +17,11 @@ namespace dspu
 {
 namespace
 {
-    struct gate_impl
-    {
-        mi_gate_bank_t *bank = nullptr;
-        float  *d_buf = nullptr;            // [2][cap]: the staged input (gain in place on it), the envelope
-        size_t  cap = 0;
-        float   e = 0.0f, peak = 0.0f;      // the state as the device holds it
-        uint32_t hold = 0, curve = 0;
-
-        bool reserve(size_t n)
-        {
-            if (n <= cap)
-                return true;
-            mi_dspu_free(d_buf);
-            d_buf = nullptr;
-            cap = 0;
-            if (mi_dspu_malloc(reinterpret_cast<void **>(&d_buf), 2 * n * sizeof(float)) != MI_OK)
-                return false;
-            cap = n;
-            return true;
-        }
-    };
-
-    std::mutex g_lock;
-    std::unordered_map<const void *, gate_impl *> &table()
-    {
-        static std::unordered_map<const void *, gate_impl *> t;
-        return t;
-    }
-
-    gate_impl *impl_of(const void *self, bool make)
-    {
-        std::lock_guard<std::mutex> guard(g_lock);
-        auto it = table().find(self);
-        if (it != table().end())
-            return it->second;
-        if (!make)
-            return nullptr;
-        gate_impl *p = new (std::nothrow) gate_impl();
-        if (p == nullptr)
-            return nullptr;
-        if (mi_gate_bank_create(&p->bank, 1) != MI_OK)
-        {
-            delete p;
-            return nullptr;
-        }
-        table()[self] = p;
-        return p;
-    }
-
-    void drop(const void *self)
-    {
-        gate_impl *p = nullptr;
-        {
-            std::lock_guard<std::mutex> guard(g_lock);
-            auto it = table().find(self);
-            if (it == table().end())
-                return;
-            p = it->second;
-            table().erase(it);
-        }
-        mi_gate_bank_destroy(p->bank);
-        mi_dspu_free(p->d_buf);
-        delete p;
-    }
+    struct gate_held { float e = 0.0f, peak = 0.0f; uint32_t hold = 0, curve = 0; };    // the state as the device holds it
+    typedef mi_host::registry<mi_gate_bank_t, gate_held, mi_gate_bank_create, mi_gate_bank_destroy> besides;
 
     // the object's computed fields as the bank's channel 0
-    bool hand_over(gate_impl *p, float ta, float tr, uint32_t hold, const dsp::gate_knee_t &k0, const dsp::gate_knee_t &k1)
+    bool hand_over(besides::entry *p, float ta, float tr, uint32_t hold, const dsp::gate_knee_t &k0, const dsp::gate_knee_t &k1)
     {
         mi_gate_params_t q;
         q.tau_attack = ta;
@@ -99,15 +34,9 @@ namespace
         return mi::gate_bank_set_params(p->bank, 0, &q) == MI_OK;
     }
 
-    // the object's state as the bank's, where the fields are not what the device holds
-    bool hand_over_state(gate_impl *p, float e, float peak, uint32_t hold, uint32_t curve)
+    int send_state(mi_gate_bank_t *bank, const gate_held &s)
     {
-        if (memcmp(&e, &p->e, sizeof(e)) == 0 && memcmp(&peak, &p->peak, sizeof(peak)) == 0 && hold == p->hold && curve == p->curve)
-            return true;
-        if (mi::gate_bank_set_state(p->bank, 0, e, peak, hold, curve, nullptr) != MI_OK)
-            return false;
-        p->e = e, p->peak = peak, p->hold = hold, p->curve = curve;
-        return true;
+        return mi::gate_bank_set_state(bank, 0, s.e, s.peak, s.hold, s.curve, nullptr);
     }
 
     inline float knee_gain(float x, const dsp::gate_knee_t *c)  // Gate.cpp:236-247, x = |input|
@@ -126,7 +55,7 @@ Gate::~Gate() { destroy(); }
 
 void Gate::construct()                                          // Gate.cpp:41-74
 {
-    drop(this);                                                 // whatever lived at this address before
+    besides::drop(this);                                        // whatever lived at this address before
     for (size_t i = 0; i < 2; ++i)
     {
         curve_t *c = &sCurves[i];
@@ -155,7 +84,7 @@ void Gate::construct()                                          // Gate.cpp:41-7
 
 void Gate::destroy()                                            // :76-78
 {
-    drop(this);
+    besides::drop(this);
 }
 
 void Gate::update_settings()                                    // :180-205: computes whether or not bUpdate is set
@@ -183,10 +112,10 @@ void Gate::update_settings()                                    // :180-205: com
 
 void Gate::process(float *out, float *env, const float *in, size_t samples)            // :267-367: no update_settings()
 {
-    gate_impl *p = impl_of(this, true);
-    if (p == nullptr || samples == 0 || !p->reserve(samples) ||
+    besides::entry *p = besides::of(this);
+    if (p == nullptr || samples == 0 || !p->reserve(samples, 2) ||
         !hand_over(p, fTauAttack, fTauRelease, nHold, sCurves[0].sKnee, sCurves[1].sKnee) ||
-        !hand_over_state(p, fEnvelope, fPeak, uint32_t(nHoldCounter), (nCurve != 0) ? 1 : 0))
+        !p->hand_over_state({ fEnvelope, fPeak, uint32_t(nHoldCounter), (nCurve != 0) ? 1u : 0u }, send_state))
         return;
     float *d_in = p->d_buf, *d_env = p->d_buf + p->cap;
     if (mi_dspu_copy_h2d(d_in, in, samples * sizeof(float), nullptr) != MI_OK ||
@@ -195,9 +124,9 @@ void Gate::process(float *out, float *env, const float *in, size_t samples)     
         return;
     if (env != nullptr && mi_dspu_copy_d2h(env, d_env, samples * sizeof(float), nullptr) != MI_OK)
         return;
-    if (mi_gate_bank_get_state(p->bank, 0, &p->e, &p->peak, &p->hold, &p->curve, nullptr) != MI_OK)
+    if (mi_gate_bank_get_state(p->bank, 0, &p->held.e, &p->held.peak, &p->held.hold, &p->held.curve, nullptr) != MI_OK)
         return;
-    fEnvelope = p->e, fPeak = p->peak, nHoldCounter = p->hold, nCurve = uint8_t(p->curve);
+    fEnvelope = p->held.e, fPeak = p->held.peak, nHoldCounter = p->held.hold, nCurve = uint8_t(p->held.curve);
 }
 
 float Gate::process(float *env, float s)                        // :369-407: one step, the curve chosen by the old curve's knee
@@ -236,8 +165,8 @@ float Gate::process(float *env, float s)                        // :369-407: one
 
 void Gate::curve(float *out, const float *in, size_t dots, bool hyst) const            // :207-210
 {
-    gate_impl *p = impl_of(this, true);
-    if (p == nullptr || dots == 0 || !p->reserve(dots) ||
+    besides::entry *p = besides::of(this);
+    if (p == nullptr || dots == 0 || !p->reserve(dots, 2) ||
         !hand_over(p, fTauAttack, fTauRelease, nHold, sCurves[0].sKnee, sCurves[1].sKnee))
         return;
     if (mi_dspu_copy_h2d(p->d_buf, in, dots * sizeof(float), nullptr) == MI_OK &&

@@ -4,7 +4,7 @@
 // exponent of its own, so one kernel serves the twelve modes and expf is this file's for every one of them (a device expf that
 // differs in the last bit would move a peak decision, and everything after it).
 //
-// Below them lsp::dspu::Limiter on a mi_limiter_bank of one channel, in the manner of host/gate.cpp: the class has no member
+// Below them lsp::dspu::Limiter on a mi_limiter_bank of one channel, in the manner of host/beside.h: the class has no member
 // to hang the bank on (its 216 bytes are the reference's), so the bank and its staging buffer live in a table keyed by the
 // object's address: made in init(), dropped in destroy() and in construct().  Every setter goes to the bank as well, so the
 // bank's own update_settings() sees what the object's sees; nHead and sALR.fEnvelope are read back after every process().

@@ -1,5 +1,5 @@
-// The tile walk of compressor.hip and sidechain.hip, device side: a serial per-channel chain over rows with element-wise work
-// beside it.  The two kernels differ in what they prepare, chain and emit.
+// The tile walk of the envelope dynamics (dynamics_device.h, gate.hip, dynproc.hip) and sidechain.hip, device side: a serial
+// per-channel chain over rows with element-wise work beside it.  The kernels differ in what they prepare, chain and emit.
 //
 // A workgroup of BLOCK threads owns GROUP channels and walks their rows in tiles of TILE samples through LDS, two buffers
 // (tile[2][GROUP][ROW], declared by the kernel):
@@ -14,7 +14,7 @@
 // out in place: the roles, the extents, the stores and the chain's batch loop (the two __noinline__ chains keep every
 // instruction).  The walk is a MACRO, as in lanczos_device.h: as a template over three callables it moved
 // compressor_kernel from 81 to 80 VGPRs (taken by value) or grew it by 200 bytes (by reference); the same tokens in place
-// give the same kernel.  The LOADS of a lane's four samples stay written out in the two kernels: one load_quad for them,
+// give the same kernel.  The LOADS of a lane's four samples stay written out in the kernels: one load_quad for them,
 // tried as a function and as a macro, moved the register counts at every site but one (compressor_kernel 81 -> 77 VGPRs,
 // or 58 -> 60 SGPRs with only the audio load replaced; sidechain_kernel 83 -> 79; five waves per SIMD -> six).
 #pragma once

@@ -812,118 +812,8 @@ class OversamplerBank:
             pass
 
 
-def _params_dict(p):
-    return {"tau_attack": p.tau_attack, "tau_release": p.tau_release, "release_threshold": p.release_threshold, "hold": p.hold,
-            "k": [{"start": k.start, "end": k.end, "gain": k.gain, "herm": np.array(k.herm[:], np.float32),
-                   "tilt": np.array(k.tilt[:], np.float32)} for k in p.k]}
-
-
-class CompressorBank:
-    """`channels` x lsp::dspu::Compressor (mi_compressor_bank_*): envelope follower and two-knee gain curve, every channel
-    with settings of its own."""
-    CM_DOWNWARD, CM_UPWARD, CM_BOOSTING = range(3)
-
-    def __init__(self, channels):
-        h = c_void_p()
-        check(lib.mi_compressor_bank_create(byref(h), channels))
-        self.handle, self.channels = h, channels
-
-    @staticmethod
-    def compute_params(sample_rate=0, mode=0, attack_threshold=0.0, release_threshold=0.0, boost_threshold=2.5119e-4, attack=0.0,
-                       release=0.0, hold=0.0, knee=0.0, ratio=1.0):
-        """update_settings() of one compressor on the host (mi_compressor_compute_params): no device needed."""
-        from .capi import CompressorParams, CompressorSettings
-        s = CompressorSettings(sample_rate, mode, attack_threshold, release_threshold, boost_threshold, attack, release, hold, knee, ratio)
-        p = CompressorParams()
-        check(lib.mi_compressor_compute_params(byref(s), byref(p)))
-        return _params_dict(p)
-
-    def set_sample_rate(self, channel, sr):
-        check(lib.mi_compressor_bank_set_sample_rate(self.handle, channel, sr))
-
-    def set_mode(self, channel, mode):
-        check(lib.mi_compressor_bank_set_mode(self.handle, channel, mode))
-
-    def set_threshold(self, channel, attack, release):
-        check(lib.mi_compressor_bank_set_threshold(self.handle, channel, attack, release))
-
-    def set_boost_threshold(self, channel, boost):
-        check(lib.mi_compressor_bank_set_boost_threshold(self.handle, channel, boost))
-
-    def set_timings(self, channel, attack, release):
-        check(lib.mi_compressor_bank_set_timings(self.handle, channel, attack, release))
-
-    def set_hold(self, channel, hold):
-        check(lib.mi_compressor_bank_set_hold(self.handle, channel, hold))
-
-    def set_knee(self, channel, knee):
-        check(lib.mi_compressor_bank_set_knee(self.handle, channel, knee))
-
-    def set_ratio(self, channel, ratio):
-        check(lib.mi_compressor_bank_set_ratio(self.handle, channel, ratio))
-
-    def configure(self, channel, sample_rate, mode, attack_threshold, release_threshold, boost_threshold, attack, release, hold,
-                  knee, ratio):
-        """Every setter of one channel."""
-        self.set_sample_rate(channel, sample_rate)
-        self.set_mode(channel, mode)
-        self.set_threshold(channel, attack_threshold, release_threshold)
-        self.set_boost_threshold(channel, boost_threshold)
-        self.set_timings(channel, attack, release)
-        self.set_hold(channel, hold)
-        self.set_knee(channel, knee)
-        self.set_ratio(channel, ratio)
-
-    def update_settings(self, stream=None):
-        check(lib.mi_compressor_bank_update_settings(self.handle, _stream(stream)))
-
-    def clear(self, stream=None):
-        check(lib.mi_compressor_bank_clear(self.handle, _stream(stream)))
-
-    def get_params(self, channel):
-        from .capi import CompressorParams
-        p = CompressorParams()
-        check(lib.mi_compressor_bank_get_params(self.handle, channel, byref(p)))
-        return _params_dict(p)
-
-    def get_state(self, channel, stream=None):
-        """(fEnvelope, fPeak, nHoldCounter) of the channel; the envelope and the peak as numpy float32."""
-        e, p, h = c_float(), c_float(), c_uint32()
-        check(lib.mi_compressor_bank_get_state(self.handle, channel, byref(e), byref(p), byref(h), _stream(stream)))
-        return np.float32(e.value), np.float32(p.value), h.value
-
-    def process(self, gain, env, inp, count, gain_stride=None, env_stride=None, in_stride=None, stream=None):
-        """process(out, env, in, samples); env may be None, gain or env may be inp (in place)."""
-        check(lib.mi_compressor_bank_process(self.handle, _ptr(gain), None if env is None else _ptr(env), _ptr(inp), count,
-                                             count if gain_stride is None else gain_stride, count if env_stride is None else env_stride,
-                                             count if in_stride is None else in_stride, _stream(stream)))
-
-    def process_apply(self, out, audio, sc, count, out_stride=None, audio_stride=None, sc_stride=None, stream=None):
-        """out = audio * gain(sc) in one launch; out may be audio or sc."""
-        check(lib.mi_compressor_bank_process_apply(self.handle, _ptr(out), _ptr(audio), _ptr(sc), count,
-                                                   count if out_stride is None else out_stride,
-                                                   count if audio_stride is None else audio_stride,
-                                                   count if sc_stride is None else sc_stride, _stream(stream)))
-
-    def curve(self, out, inp, dots, out_stride=None, in_stride=None, stream=None):
-        """curve(out, in, dots) of every channel: out = gain(|in|) |in|."""
-        check(lib.mi_compressor_bank_curve(self.handle, _ptr(out), _ptr(inp), dots, dots if out_stride is None else out_stride,
-                                           dots if in_stride is None else in_stride, _stream(stream)))
-
-    def close(self):
-        if self.handle:
-            lib.mi_compressor_bank_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
 class _DynamicsBank:
-    """What ExpanderBank and GateBank share with each other: the calls of mi_<unit>_bank_* that have one signature."""
+    """What the four envelope dynamics banks share: the calls of mi_<unit>_bank_* that have one signature."""
     UNIT = None
 
     def __init__(self, channels):
@@ -973,6 +863,73 @@ class _DynamicsBank:
             self.close()
         except Exception:
             pass
+
+
+def _params_dict(p):
+    return {"tau_attack": p.tau_attack, "tau_release": p.tau_release, "release_threshold": p.release_threshold, "hold": p.hold,
+            "k": [{"start": k.start, "end": k.end, "gain": k.gain, "herm": np.array(k.herm[:], np.float32),
+                   "tilt": np.array(k.tilt[:], np.float32)} for k in p.k]}
+
+
+class CompressorBank(_DynamicsBank):
+    """`channels` x lsp::dspu::Compressor (mi_compressor_bank_*): envelope follower and two-knee gain curve, every channel
+    with settings of its own."""
+    UNIT = "compressor"
+    CM_DOWNWARD, CM_UPWARD, CM_BOOSTING = range(3)
+
+    @staticmethod
+    def compute_params(sample_rate=0, mode=0, attack_threshold=0.0, release_threshold=0.0, boost_threshold=2.5119e-4, attack=0.0,
+                       release=0.0, hold=0.0, knee=0.0, ratio=1.0):
+        """update_settings() of one compressor on the host (mi_compressor_compute_params): no device needed."""
+        from .capi import CompressorParams, CompressorSettings
+        s = CompressorSettings(sample_rate, mode, attack_threshold, release_threshold, boost_threshold, attack, release, hold, knee, ratio)
+        p = CompressorParams()
+        check(lib.mi_compressor_compute_params(byref(s), byref(p)))
+        return _params_dict(p)
+
+    def set_mode(self, channel, mode):
+        check(lib.mi_compressor_bank_set_mode(self.handle, channel, mode))
+
+    def set_threshold(self, channel, attack, release):
+        check(lib.mi_compressor_bank_set_threshold(self.handle, channel, attack, release))
+
+    def set_boost_threshold(self, channel, boost):
+        check(lib.mi_compressor_bank_set_boost_threshold(self.handle, channel, boost))
+
+    def set_knee(self, channel, knee):
+        check(lib.mi_compressor_bank_set_knee(self.handle, channel, knee))
+
+    def set_ratio(self, channel, ratio):
+        check(lib.mi_compressor_bank_set_ratio(self.handle, channel, ratio))
+
+    def configure(self, channel, sample_rate, mode, attack_threshold, release_threshold, boost_threshold, attack, release, hold,
+                  knee, ratio):
+        """Every setter of one channel."""
+        self.set_sample_rate(channel, sample_rate)
+        self.set_mode(channel, mode)
+        self.set_threshold(channel, attack_threshold, release_threshold)
+        self.set_boost_threshold(channel, boost_threshold)
+        self.set_timings(channel, attack, release)
+        self.set_hold(channel, hold)
+        self.set_knee(channel, knee)
+        self.set_ratio(channel, ratio)
+
+    def get_params(self, channel):
+        from .capi import CompressorParams
+        p = CompressorParams()
+        check(lib.mi_compressor_bank_get_params(self.handle, channel, byref(p)))
+        return _params_dict(p)
+
+    def get_state(self, channel, stream=None):
+        """(fEnvelope, fPeak, nHoldCounter) of the channel; the envelope and the peak as numpy float32."""
+        e, p, h = c_float(), c_float(), c_uint32()
+        check(lib.mi_compressor_bank_get_state(self.handle, channel, byref(e), byref(p), byref(h), _stream(stream)))
+        return np.float32(e.value), np.float32(p.value), h.value
+
+    def curve(self, out, inp, dots, out_stride=None, in_stride=None, stream=None):
+        """curve(out, in, dots) of every channel: out = gain(|in|) |in|."""
+        check(lib.mi_compressor_bank_curve(self.handle, _ptr(out), _ptr(inp), dots, dots if out_stride is None else out_stride,
+                                           dots if in_stride is None else in_stride, _stream(stream)))
 
 
 def _expander_dict(p):

@@ -120,6 +120,23 @@ def test_dynfilter_kernels_keep_the_cascades_in_registers(tmp_path):
 
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
+@pytest.mark.parametrize("source,kernel,vgprs", [("compressor.hip", "follow_kernel", 81), ("expander.hip", "follow_kernel", 72),
+                                                  ("gate.hip", "gate_kernel", 93), ("dynproc.hip", "dynproc_kernel", 82)])
+def test_dynamics_kernels_keep_their_registers_and_have_no_scratch(tmp_path, source, kernel, vgprs):
+    """The four envelope dynamics kernels share code (dynamics_device.h: compressor_kernel and expander_kernel are follow_kernel
+    over the bank's description; gate_kernel and dynproc_kernel use its pieces), and a shared piece written a little
+    differently has cost them before: the Gate's two knees in one struct took gate_kernel from 93 VGPRs and no scratch to
+    80 bytes of scratch per lane.  Each kernel keeps no private segment and no more vector registers than it had with its text
+    written out in its own file (5 waves per SIMD for three of them, 7 for the Expander's)."""
+    text = "\n".join(_isa(os.path.join(CSRC, source), tmp_path))
+    blocks = [b for b in text[text.index("amdhsa.kernels:"):].split("  - .agpr_count:")[1:]
+              if kernel in re.search(r"\.name: *(\S+)", b).group(1)]
+    assert len(blocks) == 1, [re.search(r"\.name: *(\S+)", b).group(1) for b in blocks]
+    assert int(re.search(r"\.private_segment_fixed_size: *(\d+)", blocks[0]).group(1)) == 0
+    assert int(re.search(r"\.vgpr_count: *(\d+)", blocks[0]).group(1)) <= vgprs
+
+
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
 def test_splitter_hop_kernels_with_one_handler_per_workgroup_fit_four_waves_per_simd(tmp_path):
     """1024 workgroups of 256 threads (256 channels x 4 bands, rank 12) are ONE round on the device only at four waves per
     SIMD, i.e. with at most 128 VGPRs; twice in round 3 a harmless-looking change of the source took the one-hop kernel from
