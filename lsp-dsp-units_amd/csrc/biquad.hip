@@ -45,6 +45,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 namespace
@@ -840,7 +841,34 @@ namespace
         const float        *in[STREAM_CHAIN_BLOCKS];
         float              *out[STREAM_CHAIN_PTRS];
     };
+    // The arguments of the two stream kernels as they lie in the kernarg segment: every argument at its natural alignment, in
+    // the order of the parameter list.  The loop over the sub-blocks re-reads from there what it needs of them once a turn
+    // (a scalar load where it is used) instead of holding it in registers the sections have no room for.
+    struct stream_kernargs
+    {
+        stream_args a;
+        size_t out_stride, in_stride;
+        int n;
+        const float *tab;
+        float *state;
+        const uint32_t *nsec;
+        int max_sec, cap;
+    };
+    struct stream_chain_kernargs
+    {
+        stream_chain_args c;
+        size_t out_stride, in_stride;
+        int n, cap;
+    };
     struct stream_cell { float d0, d1; uint32_t seq, pad; };
+    // what a turn of the stream's loop tells its sections: the sub-block hands on the recurrence's own end state (not the
+    // scan's), it is the launch's last one, its last chunk is a lane's second one
+    constexpr uint32_t F_EXACT = 1, F_FINAL = 2, F_SAVE_HI = 4;
+    // A value taken HERE: the compiler sees a new value come out of an empty statement, so what is computed from it is
+    // computed behind this point and not once in front of the loop, to be held in a register (or a spill lane) all the way
+    // round.  `here`: wave-uniform, in a scalar register; `here_v`: per lane.  No instruction either way.
+    template <class T> __device__ __forceinline__ T here(T v) { asm volatile("" : "+s"(v)); return v; }
+    template <class T> __device__ __forceinline__ T here_v(T v) { asm volatile("" : "+v"(v)); return v; }
     typedef volatile __attribute__((address_space(3))) stream_cell lds_cell;    // ds_read / ds_write, in program order
 
     // QLDS: the per-lane operand of the scan ((P^2)^(lane % 16 + 1), 16 bytes per lane and section) waits in LDS for the whole
@@ -879,10 +907,13 @@ namespace
         auto stage_mem = [&](int k) -> float * {
             return CHAIN ? pc->st[k].state + size_t(ch) * pc->st[k].max_sec * 2 : state + size_t(ch) * max_sec * 2; };
         const float *ctab = stage_tab(0);
-        float2 *const mem0 = reinterpret_cast<float2 *>(stage_mem(0));
         const int spb   = (n + SB - 1) / SB;                 // sub-blocks of a block
         const int total = (CHAIN ? pc->blocks : pa->blocks) * spb;
-        const int pred  = (wv + NW - 1) % NW;
+        // the launch's constants for the loop over the sub-blocks: read again where they are used (`here`)
+        using kargs = typename std::conditional<CHAIN, stream_chain_kernargs, stream_kernargs>::type;
+        typedef const __attribute__((address_space(4))) kargs ckargs;
+        ckargs *const ka = (ckargs *)__builtin_amdgcn_kernarg_segment_ptr();
+        auto ka_blocks = [](ckargs *q) -> int { if constexpr (CHAIN) return q->c.blocks; else return q->a.blocks; };
 
         typedef const __attribute__((address_space(4))) float cfloat;
         typedef const __attribute__((address_space(4))) v16f cv16f;
@@ -923,17 +954,35 @@ namespace
             r.a2 = U[4];
         };
 
-        float4 ld[LPT];
-        auto issue_loads = [&](int g, bool there = true)     // coalesced rows of sub-block g -> registers (!there: zeros, no traffic)
+        // Sub-block g of the stream is sub-block j of block k.  A wave goes on by NW sub-blocks at a time, which is at most
+        // NW carries from j into k: the loop carries the two counters and divides nothing.
+        const int k0 = wv / spb, j0 = wv - k0 * spb;
+        auto advance = [](int &k, int &j, int spb)
         {
-            const int k = g / spb, j = g - k * spb;
-            const float *blk = CHAIN ? pc->in[k] : pa->in[k];
+            j += NW;
+            while (j >= spb)
+            {
+                j -= spb;
+                ++k;
+            }
+        };
+        // A row piece of a sub-block is 16 bytes per lane, the pieces 1 KiB apart: the window of a sub-block's loads and stores
+        // starts at the sub-block (the same bytes in range as with a window over the whole row), and what is left of the
+        // offset is the lane's 16 t and a constant per piece.
+        const int t16 = 16 * t;
+
+        float4 ld[LPT];
+        // coalesced rows of sub-block j of block k -> registers (!there: zeros, no traffic)
+        auto issue_loads = [&](ckargs *q, int k, int j, int tq /* 16 t */, bool there = true)
+        {
+            const float *blk;
+            if constexpr (CHAIN) blk = q->c.in[k]; else blk = q->a.in[k];
             const __amdgpu_buffer_rsrc_t src = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<float *>(blk + size_t(ch) * in_stride), 0, there ? n * 4 : 0, BUFFER_DWORD3);
+                const_cast<float *>(blk + size_t(uint32_t(ch)) * q->in_stride + j * SB), 0, there ? (q->n - j * SB) * 4 : 0, BUFFER_DWORD3);
             #pragma unroll
             for (int q = 0; q < LPT; ++q)
             {
-                const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(src, (j * SB + 4 * (q * 64 + t)) * 4, 0, 0);
+                const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(src, tq + 1024 * q, 0, 0);
                 ld[q] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
             }
         };
@@ -941,7 +990,7 @@ namespace
         // the first tile's loads go out before anything else is asked of memory (section count, filter memory, tables):
         // those arrive underneath them
         if (wv < total)
-            issue_loads(wv);
+            issue_loads(ka, k0, j0, t16);
         // The rows are waited for at the top of every sub-block, with the stores of the sub-block before issued in between: the
         // wait may leave those eight stores in flight -- if the compiler's count of what follows the loads is the same on the way
         // INTO the loop as round it (it settles for the smaller of the two, and on the way in nothing followed the loads: the
@@ -998,18 +1047,32 @@ namespace
         }
         MI_STREAM_PROBE_BEGIN();
 
-        for (int g = wv; g < total; g += NW)
+        // Across the sections a turn of this loop keeps its three counters, one word of flags and two lane masks in scalar
+        // registers, beside the section's table (71 of them): everything else is formed again where it is used, in front of
+        // the sections and behind them, from the counters and the kernel arguments.
+        int k = k0, j = j0;
+        if (wv < total) for (int g = wv; ; )
         {
             MI_STREAM_PROBE(0);
-            const int k = g / spb, j = g - k * spb;
-            const int base  = j * SB;
-            const int valid = (n - base < SB) ? n - base : SB;       // multiple of L
-            const int last  = valid - 1;
-            const int t_last = last / W;
-            const bool save_hi = (last - t_last * W) >= L;
-            const bool saver   = (t == t_last);
-            const bool exact_out = (j & 1) || (j == spb - 1);        // how this sub-block hands its state on
-            const bool final_sb  = (g == total - 1);
+            ckargs *const qa = here(ka);
+            const int n_a = qa->n, spb_a = (n_a + SB - 1) / SB, total_a = ka_blocks(qa) * spb_a;
+            // A whole sub-block ends in lane 63's second chunk; only a block's last one may be shorter (a multiple of L).
+            int t_last = 63;
+            uint32_t flags = F_SAVE_HI;
+            if (j == spb_a - 1)
+            {
+                const int last = n_a - j * SB - 1;
+                t_last = last / W;
+                flags = ((last - t_last * W) >= L) ? F_SAVE_HI : 0u;
+                flags |= F_EXACT;
+            }
+            flags |= (j & 1) ? F_EXACT : 0u;                         // how this sub-block hands its state on
+            flags |= (g == total_a - 1) ? F_FINAL : 0u;
+            // The section loop sees the turn's wave-uniform conditions as bits of one scalar (taken `here`, so that they are
+            // not kept as a lane mask each) and its two publishing lanes as one mask each.
+            const int tl = here_v(t);
+            const bool scan_out = !(flags & F_EXACT) && tl == 63;
+            const bool end_out  = (flags & (F_EXACT | F_FINAL)) && tl == t_last;
             const uint32_t want = uint32_t(g), mine = uint32_t(g + 1);
 
             // The tile holds a lane's two chunks INTERLEAVED (first, second, first, second, ...): a 16-byte read is two
@@ -1024,8 +1087,12 @@ namespace
             }
             __builtin_amdgcn_wave_barrier();
             MI_STREAM_PROBE(1);
-            if (!CHAIN && g + NW < total)                    // (the chain asks later: see below)
-                issue_loads(g + NW);
+            if (!CHAIN && g + NW < total_a)                  // (the chain asks later: see below)
+            {
+                int kn = k, jn = j;
+                advance(kn, jn, spb_a);
+                issue_loads(qa, kn, jn, here_v(t16));      // (`here_v`: a sum, whose constants go to the instructions' own offset fields)
+            }
             #pragma unroll
             for (int q = 0; q < L / 2; ++q)
             {
@@ -1035,8 +1102,8 @@ namespace
             }
 
             // One section over the sub-block: `tb` holds its table on entry and the table at Tnext on exit; ci: its hand-over
-            // cell; mem2: where its state goes at the end of the launch; turn: what the issue priority goes round with.
-            auto section = [&](const float *Tnext, int qnext, int ci, float2 *mem2, int turn)
+            // cell; mem2(): where its state goes at the end of the launch; turn: what the issue priority goes round with.
+            auto section = [&](const float *Tnext, int qnext, int ci, auto mem2, int turn)
             {
 #if MI_STREAM_ROTATE
                 // The instruction arbiter of a SIMD serves its OLDEST wave first: of the four workgroups that share a CU --
@@ -1049,7 +1116,7 @@ namespace
                 // marks alone do, profiles/r04_experiments/biquad_stream_pace.txt; priorities switched by the 100 MHz
                 // clock instead of the progress: the same balance, no shorter.)
                 if ((turn & 3) == 0)
-                    switch (((turn >> 2) + (g / NW) + int(blockIdx.x >> 8)) & 3)
+                    switch (((turn >> 2) + (here(g) / NW) + (here(ch) >> 8)) & 3)
                     {
                         case 0: __builtin_amdgcn_s_setprio(3); break;
                         case 1: __builtin_amdgcn_s_setprio(2); break;
@@ -1057,8 +1124,9 @@ namespace
                         default: __builtin_amdgcn_s_setprio(0); break;
                     }
 #endif
-                lds_cell *const from = (lds_cell *)&cell[ci * NW + pred];
-                lds_cell *const to   = (lds_cell *)&cell[ci * NW + wv];
+                const int w = here(wv);                      // (the wave before it in the pipeline: from w, not carried beside it)
+                lds_cell *const from = (lds_cell *)&cell[ci * NW + ((w + NW - 1) & (NW - 1))];
+                lds_cell *const to   = (lds_cell *)&cell[ci * NW + w];
                 // asked for now, looked at after the dot products
                 uint32_t got = from->seq;
                 float c0 = from->d0, c1 = from->d1;
@@ -1103,7 +1171,7 @@ namespace
                     const v2f s2 = mat_fma(v2f{tb.m1[12], tb.m1[13]}, v2f{tb.m1[14], tb.m1[15]}, s, zero);
                     e = mat_fma(QLc0, QLc1, row3 ? s2 : s, e);
                 }
-                if (!exact_out && t == 63)                   // the scan's end state goes on (a full sub-block)
+                if (scan_out)                                // the scan's end state goes on (a full sub-block)
                 {
                     to->d0 = e.x;
                     to->d1 = e.y;
@@ -1133,23 +1201,27 @@ namespace
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 load_coefs(tb, Tnext);
-                if (saver && (exact_out || final_sb))
+                if (end_out)
                 {
-                    const float s0 = save_hi ? d0.y : d0.x, s1 = save_hi ? d1.y : d1.x;
-                    if (exact_out)
+                    const uint32_t f = here(flags);
+                    const float s0 = (f & F_SAVE_HI) ? d0.y : d0.x, s1 = (f & F_SAVE_HI) ? d1.y : d1.x;
+                    if (f & F_EXACT)
                     {
                         to->d0 = s0;
                         to->d1 = s1;
                         to->seq = mine;
                     }
-                    if (final_sb)                            // the memory the next call starts from
-                        *mem2 = make_float2(s0, s1);
+                    if (f & F_FINAL)                         // the memory the next call starts from
+                        *mem2() = make_float2(s0, s1);
                 }
             };
             // x (registers) -> the wave's tile (transposed) -> coalesced write-through store
             auto store_tile = [&](float *rows)
             {
-                const __amdgpu_buffer_rsrc_t dst = __builtin_amdgcn_make_buffer_rsrc(rows + size_t(ch) * out_stride, 0, n * 4, BUFFER_DWORD3);
+                ckargs *const q = here(ka);
+                const int base = here(j) * SB;
+                const __amdgpu_buffer_rsrc_t dst = __builtin_amdgcn_make_buffer_rsrc(rows + size_t(uint32_t(ch)) * q->out_stride + base, 0,
+                                                                                     (q->n - base) * 4, BUFFER_DWORD3);
                 #pragma unroll
                 for (int q = 0; q < L / 2; ++q)
                     *reinterpret_cast<float4 *>(&sx[t * PITCH + 4 * q]) = make_float4(x[2 * q].x, x[2 * q].y, x[2 * q + 1].x, x[2 * q + 1].y);
@@ -1159,20 +1231,23 @@ namespace
                 {
                     const int i = 4 * (q * 64 + t);
                     const float *d = &sx[(i / W) * PITCH + 2 * (i % L) + ((i % W) / L)];
-                    store_through(dst, base + i, make_float4(d[0], d[2], d[4], d[6]));
+                    store_through(dst, i, make_float4(d[0], d[2], d[4], d[6]));     // (the window starts at the sub-block)
                 }
                 __builtin_amdgcn_wave_barrier();
             };
 
             if constexpr (!CHAIN)
             {
-                for (int si = 0; si < ns; ++si)
+                const int nsx = here(ns);
+                for (int si = 0; si < nsx; ++si)
                 {
-                    const int snext = (si + 1 < ns) ? si + 1 : 0;
-                    section(ctab + size_t(snext) * TAB, snext, si, mem0 + si, si);
+                    const int snext = (si + 1 < nsx) ? si + 1 : 0;
+                    section(ctab + size_t(snext) * TAB, snext, si, [&]() -> float2 * {
+                        ckargs *const q = here(ka);
+                        return reinterpret_cast<float2 *>(q->state + size_t(uint32_t(ch)) * uint32_t(q->max_sec) * 2) + si; }, si);
                 }
                 MI_STREAM_PROBE(2);
-                store_tile(pa->out[k]);
+                store_tile(here(ka)->a.out[here(k)]);
             }
             else
             {
@@ -1205,7 +1280,7 @@ namespace
                     }
                     for (int si = 0; si < cur.ns; ++si)
                         section((si + 1 < cur.ns) ? cur.T + size_t(si + 1) * TAB : Tn, (si + 1 < cur.ns) ? lds0 + si + 1 : qn,
-                                lds0 + si, cur.mem2 + si, lds0 + si);
+                                lds0 + si, [&]() -> float2 * { return cur.mem2 + si; }, lds0 + si);
                     if (cur.slot >= 0)
                         store_tile(pc->out[k * pc->outs + cur.slot]);
                     if (BR && cur.branch)
@@ -1227,14 +1302,27 @@ namespace
                 // (asked for unconditionally -- behind the last sub-block from a window of no bytes: a conditional request would
                 // keep the registers of the rows alive across the whole iteration for the case that it is not made)
                 {
-                    const bool more = g + NW < total;
-                    issue_loads(more ? g + NW : g, more);
+                    ckargs *const q = here(ka);
+                    const int spb_q = (q->n + SB - 1) / SB;
+                    const bool more = g + NW < ka_blocks(q) * spb_q;
+                    int kn = k, jn = j;
+                    if (more)
+                        advance(kn, jn, spb_q);
+                    issue_loads(q, kn, jn, here_v(t16), more);
                 }
                 run_stage(std::false_type(), cur, ctab, lds0, 0);
                 MI_STREAM_PROBE(2);
             }
             MI_STREAM_PROBE(3);
             MI_STREAM_PROBE_ITER(g / NW);
+            {
+                ckargs *const q = here(ka);
+                const int spb_q = (q->n + SB - 1) / SB;
+                advance(k, j, spb_q);
+                g = here(g) + NW;
+                if (g >= ka_blocks(q) * spb_q)
+                    break;
+            }
         }
         MI_STREAM_PROBE_END();
     }
