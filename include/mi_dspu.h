@@ -1404,6 +1404,74 @@ int mi_sidechain_bank_premix(mi_sidechain_bank_t *bank, float *out, const float 
 int mi_sidechain_bank_process_premixed(mi_sidechain_bank_t *bank, float *out, const float *in, size_t count, size_t out_stride,
                                        size_t in_stride, void *stream);
 
+/* ---- stereo-field meters: correlometer and panometer banks --------------------------------------------------------------- */
+/*
+ * mi_correlometer_bank: `channels` x lsp::dspu::Correlometer (meters/Correlometer.h, src/main/meters/Correlometer.cpp), every
+ * channel with a period of its own: the normalised correlation of two rows, out = v / sqrt(a * b) over a sliding window of
+ * `period` samples (0 where a * b < 1e-10), v, a, b the window sums of x*y, x*x, y*y.  Per channel two rings of
+ * align(max_period + 0x400, 0x40) samples; per sample each sum takes in the head's term and gives up the tail's
+ * (sum += head - tail: product, product, difference, sum), and every `period` samples the three sums are formed anew from the
+ * rings, serially, oldest sample first, in two partial sums where the window wraps in the ring.  out,
+ * the sums, nHead and nWindow are the reference's bit for bit in float32; there is no clamp to [-1, 1], as there is none in the
+ * reference.  Rings, sums, nHead and nWindow live on the device: no host positions, so process calls can be captured into a
+ * graph and replayed.  Inputs are finite: NaN is out of scope.  Subnormals are kept.  Rows: [channels][stride].
+ */
+typedef struct mi_correlometer_bank mi_correlometer_bank_t;
+typedef struct { uint32_t period, capacity, max_period; } mi_correlometer_params_t;
+typedef struct { float v, a, b; uint32_t head, window; } mi_correlometer_state_t;          /* sCorr, nHead, nWindow */
+/* init(max_period) of every channel: period 0, nHead 0, sums and rings zero */
+int mi_correlometer_bank_create(mi_correlometer_bank_t **bank, uint32_t channels, uint32_t max_period);
+int mi_correlometer_bank_destroy(mi_correlometer_bank_t *bank);
+/* set_period(): clamped to max_period; an unchanged value is ignored, a changed one makes the next process() start with a
+ * refresh (nWindow = nPeriod).  A period of 0 is MI_EINVAL: the reference's process() never ends with it. */
+int mi_correlometer_bank_set_period(mi_correlometer_bank_t *bank, uint32_t channel, uint32_t period);
+/* clear() of one channel, or of every channel (channel = UINT32_MAX): rings and sums zero, nHead = nPeriod; nWindow stays */
+int mi_correlometer_bank_clear(mi_correlometer_bank_t *bank, uint32_t channel);
+/* What the setters left goes to the device (and the call waits for it).  process() runs it first.  On a stream being captured
+ * pending work is refused (MI_ESTATE): call it before the capture. */
+int mi_correlometer_bank_update_settings(mi_correlometer_bank_t *bank, void *stream);
+/* The channel's settings as set (HOST memory); its state as the work enqueued on `stream` leaves it (HOST memory; waits for
+ * the stream; not on a stream being captured: MI_ESTATE).  set_state writes the state as given (nHead modulo the capacity,
+ * nWindow at most the period) after the pending work, zero_rings != 0: with both rings zeroed. */
+int mi_correlometer_bank_get_params(const mi_correlometer_bank_t *bank, uint32_t channel, mi_correlometer_params_t *params);
+int mi_correlometer_bank_get_state(mi_correlometer_bank_t *bank, uint32_t channel, mi_correlometer_state_t *state, void *stream);
+int mi_correlometer_bank_set_state(mi_correlometer_bank_t *bank, uint32_t channel, const mi_correlometer_state_t *state,
+                                   uint32_t zero_rings, void *stream);
+/* process(dst, a, b, count).  out may be a or b (same stride).  While a channel still has period 0: MI_ESTATE naming it, and
+ * nothing is launched. */
+int mi_correlometer_bank_process(mi_correlometer_bank_t *bank, float *out, const float *a, const float *b, size_t count,
+                                 size_t out_stride, size_t a_stride, size_t b_stride, void *stream);
+
+/*
+ * mi_panometer_bank: `channels` x lsp::dspu::Panometer (meters/Panometer.h, src/main/meters/Panometer.cpp): the balance of two
+ * rows out of the window sums va, vb of their squares, which are what the two rings hold.  Per sample v = (v + head) - tail,
+ * two roundings; every `period` samples both sums are formed anew from the rings as in the correlometer bank.  Linear law:
+ * sl = sqrt(|va| * norm), sr = sqrt(|vb| * norm), out = sr / (sl + sr) where sl + sr > 1e-18, the default otherwise; equal
+ * power: the same without the roots and with 1e-36.  norm = 1 / period.  Bit for bit the reference's in float32 (the roots and
+ * the quotient correctly rounded).  Device state, capture, inputs and rows as for the correlometer bank.
+ */
+typedef struct mi_panometer_bank mi_panometer_bank_t;
+enum mi_pan_law { MI_PAN_LAW_LINEAR = 0, MI_PAN_LAW_EQUAL_POWER = 1 };                     /* pan_law_t */
+typedef struct { uint32_t period, capacity, max_period, law; float norm, default_pan; } mi_panometer_params_t;
+typedef struct { float value_a, value_b; uint32_t head, window; } mi_panometer_state_t;    /* fValueA, fValueB, nHead, nWindow */
+/* init(max_period) of every channel: period 0, equal power, default 0.5 */
+int mi_panometer_bank_create(mi_panometer_bank_t **bank, uint32_t channels, uint32_t max_period);
+int mi_panometer_bank_destroy(mi_panometer_bank_t *bank);
+/* set_period(): clamped; an unchanged value is ignored, a changed one zeroes both sums, sets norm and makes the next sample
+ * start with a refresh.  0 is MI_EINVAL.  set_pan_law (a law above EQUAL_POWER is MI_EINVAL) and set_default_pan just set. */
+int mi_panometer_bank_set_period(mi_panometer_bank_t *bank, uint32_t channel, uint32_t period);
+int mi_panometer_bank_set_pan_law(mi_panometer_bank_t *bank, uint32_t channel, uint32_t law);
+int mi_panometer_bank_set_default_pan(mi_panometer_bank_t *bank, uint32_t channel, float default_pan);
+/* clear(): the rings zero, nHead = nPeriod; the sums and nWindow stay */
+int mi_panometer_bank_clear(mi_panometer_bank_t *bank, uint32_t channel);
+int mi_panometer_bank_update_settings(mi_panometer_bank_t *bank, void *stream);
+int mi_panometer_bank_get_params(const mi_panometer_bank_t *bank, uint32_t channel, mi_panometer_params_t *params);
+int mi_panometer_bank_get_state(mi_panometer_bank_t *bank, uint32_t channel, mi_panometer_state_t *state, void *stream);
+int mi_panometer_bank_set_state(mi_panometer_bank_t *bank, uint32_t channel, const mi_panometer_state_t *state, uint32_t zero_rings,
+                                void *stream);
+int mi_panometer_bank_process(mi_panometer_bank_t *bank, float *out, const float *a, const float *b, size_t count,
+                              size_t out_stride, size_t a_stride, size_t b_stride, void *stream);
+
 /*
  * mi_splitter_bank: lsp::dspu::SpectralSplitter for `channels` channels sharing the settings
  * (util/SpectralSplitter.h:62-250, src/main/util/SpectralSplitter.cpp:62-361) -- the engine of lsp::dspu::FFTCrossover.

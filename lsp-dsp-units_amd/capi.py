@@ -163,6 +163,27 @@ class SidechainParams(ctypes.Structure):
                 ("source", c_uint32), ("flags", c_uint32), ("gain", c_float)]
 
 
+class CorrelometerParams(ctypes.Structure):
+    """mi_correlometer_params_t: the period as set, the rings' capacity and the longest period."""
+    _fields_ = [("period", c_uint32), ("capacity", c_uint32), ("max_period", c_uint32)]
+
+
+class CorrelometerState(ctypes.Structure):
+    """mi_correlometer_state_t: sCorr, nHead, nWindow."""
+    _fields_ = [("v", c_float), ("a", c_float), ("b", c_float), ("head", c_uint32), ("window", c_uint32)]
+
+
+class PanometerParams(ctypes.Structure):
+    """mi_panometer_params_t: the period as set, capacity, the longest period, enPanLaw, fNorm and fDefault."""
+    _fields_ = [("period", c_uint32), ("capacity", c_uint32), ("max_period", c_uint32), ("law", c_uint32), ("norm", c_float),
+                ("default_pan", c_float)]
+
+
+class PanometerState(ctypes.Structure):
+    """mi_panometer_state_t: fValueA, fValueB, nHead, nWindow."""
+    _fields_ = [("value_a", c_float), ("value_b", c_float), ("head", c_uint32), ("window", c_uint32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/mi_dspu.h must be listed here
 # (tests/test_abi.py parses the header and checks both directions).
 PROTOTYPES = {
@@ -489,6 +510,26 @@ PROTOTYPES = {
     "mi_sidechain_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_sidechain_bank_premix": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_sidechain_bank_process_premixed": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_correlometer_bank_create": (c_int, [POINTER(c_void_p), c_uint32, c_uint32]),
+    "mi_correlometer_bank_destroy": (c_int, [c_void_p]),
+    "mi_correlometer_bank_set_period": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_correlometer_bank_clear": (c_int, [c_void_p, c_uint32]),
+    "mi_correlometer_bank_update_settings": (c_int, [c_void_p, c_void_p]),
+    "mi_correlometer_bank_get_params": (c_int, [c_void_p, c_uint32, POINTER(CorrelometerParams)]),
+    "mi_correlometer_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(CorrelometerState), c_void_p]),
+    "mi_correlometer_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(CorrelometerState), c_uint32, c_void_p]),
+    "mi_correlometer_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_panometer_bank_create": (c_int, [POINTER(c_void_p), c_uint32, c_uint32]),
+    "mi_panometer_bank_destroy": (c_int, [c_void_p]),
+    "mi_panometer_bank_set_period": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_panometer_bank_set_pan_law": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_panometer_bank_set_default_pan": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_panometer_bank_clear": (c_int, [c_void_p, c_uint32]),
+    "mi_panometer_bank_update_settings": (c_int, [c_void_p, c_void_p]),
+    "mi_panometer_bank_get_params": (c_int, [c_void_p, c_uint32, POINTER(PanometerParams)]),
+    "mi_panometer_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(PanometerState), c_void_p]),
+    "mi_panometer_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(PanometerState), c_uint32, c_void_p]),
+    "mi_panometer_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_splitter_bank_create": (c_int, [POINTER(c_void_p), c_uint32, c_uint32, c_uint32]),
     "mi_splitter_bank_destroy": (c_int, [c_void_p]),
     "mi_splitter_bank_set_rank": (c_int, [c_void_p, c_uint32]),

@@ -92,6 +92,15 @@ namespace lsp
         };
         static_assert(sizeof(expander_knee_t) == 32 && sizeof(gate_knee_t) == 32, "lsp-dsp-lib layouts");
 
+        // lsp-dsp-lib's correlation state (Correlometer keeps one): the window sums of a*b, a*a and b*b
+        struct correlation_t
+        {
+            float v;
+            float a;
+            float b;
+        };
+        static_assert(sizeof(correlation_t) == 12, "lsp-dsp-lib layouts");
+
         // lsp-dsp-lib's per-thread context / init are no-ops here: there is no SIMD dispatch to select
         struct context_t { uint32_t top; uint32_t data[15]; };
         inline void init() {}

@@ -1620,6 +1620,112 @@ class SidechainBank:
             pass
 
 
+class _StereoMeterBank:
+    """What CorrelometerBank and PanometerBank share: two input rows per channel, sliding-window sums over per-channel rings on
+    the device, a period per channel."""
+    ALL = 0xFFFFFFFF
+    _name = None
+
+    def _fn(self, what):
+        return getattr(lib, "mi_%s_bank_%s" % (self._name, what))
+
+    def __init__(self, channels, max_period):
+        h = c_void_p()
+        check(getattr(lib, "mi_%s_bank_create" % self._name)(byref(h), channels, max_period))
+        self.handle, self.channels, self.max_period = h, channels, max_period
+
+    def set_period(self, channel, period):
+        check(self._fn("set_period")(self.handle, channel, period))
+
+    def clear(self, channel=ALL):
+        check(self._fn("clear")(self.handle, channel))
+
+    def update_settings(self, stream=None):
+        check(self._fn("update_settings")(self.handle, _stream(stream)))
+
+    def process(self, out, a, b, count, out_stride=None, a_stride=None, b_stride=None, stream=None):
+        """process(dst, a, b, count); out may be a or b (in place)."""
+        check(self._fn("process")(self.handle, _ptr(out), _ptr(a), _ptr(b), count, count if out_stride is None else out_stride,
+                                  count if a_stride is None else a_stride, count if b_stride is None else b_stride, _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            self._fn("destroy")(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CorrelometerBank(_StereoMeterBank):
+    """`channels` x lsp::dspu::Correlometer (mi_correlometer_bank_*): the normalised correlation of two rows over a sliding
+    window, every channel with a period of its own."""
+    _name = "correlometer"
+
+    def configure(self, channel, period):
+        """Every setter of one channel."""
+        self.set_period(channel, period)
+
+    def get_params(self, channel):
+        from .capi import CorrelometerParams
+        p = CorrelometerParams()
+        check(lib.mi_correlometer_bank_get_params(self.handle, channel, byref(p)))
+        return {"period": p.period, "capacity": p.capacity, "max_period": p.max_period}
+
+    def get_state(self, channel, stream=None):
+        """sCorr's v, a, b as numpy float32, nHead and nWindow of the channel."""
+        from .capi import CorrelometerState
+        s = CorrelometerState()
+        check(lib.mi_correlometer_bank_get_state(self.handle, channel, byref(s), _stream(stream)))
+        return {"v": np.float32(s.v), "a": np.float32(s.a), "b": np.float32(s.b), "head": s.head, "window": s.window}
+
+    def set_state(self, channel, v, a, b, head, window, zero_rings=False, stream=None):
+        from .capi import CorrelometerState
+        s = CorrelometerState(float(v), float(a), float(b), head, window)
+        check(lib.mi_correlometer_bank_set_state(self.handle, channel, byref(s), 1 if zero_rings else 0, _stream(stream)))
+
+
+class PanometerBank(_StereoMeterBank):
+    """`channels` x lsp::dspu::Panometer (mi_panometer_bank_*): the balance of two rows out of the window sums of their squares,
+    linear or equal-power law, every channel with settings of its own."""
+    _name = "panometer"
+    PAN_LAW_LINEAR, PAN_LAW_EQUAL_POWER = range(2)
+
+    def set_pan_law(self, channel, law):
+        check(lib.mi_panometer_bank_set_pan_law(self.handle, channel, law))
+
+    def set_default_pan(self, channel, default_pan):
+        check(lib.mi_panometer_bank_set_default_pan(self.handle, channel, float(default_pan)))
+
+    def configure(self, channel, period, law=PAN_LAW_EQUAL_POWER, default_pan=0.5):
+        """Every setter of one channel."""
+        self.set_period(channel, period)
+        self.set_pan_law(channel, law)
+        self.set_default_pan(channel, default_pan)
+
+    def get_params(self, channel):
+        from .capi import PanometerParams
+        p = PanometerParams()
+        check(lib.mi_panometer_bank_get_params(self.handle, channel, byref(p)))
+        return {"period": p.period, "capacity": p.capacity, "max_period": p.max_period, "law": p.law, "norm": np.float32(p.norm),
+                "default_pan": np.float32(p.default_pan)}
+
+    def get_state(self, channel, stream=None):
+        """fValueA and fValueB as numpy float32, nHead and nWindow of the channel."""
+        from .capi import PanometerState
+        s = PanometerState()
+        check(lib.mi_panometer_bank_get_state(self.handle, channel, byref(s), _stream(stream)))
+        return {"value_a": np.float32(s.value_a), "value_b": np.float32(s.value_b), "head": s.head, "window": s.window}
+
+    def set_state(self, channel, value_a, value_b, head, window, zero_rings=False, stream=None):
+        from .capi import PanometerState
+        s = PanometerState(float(value_a), float(value_b), head, window)
+        check(lib.mi_panometer_bank_set_state(self.handle, channel, byref(s), 1 if zero_rings else 0, _stream(stream)))
+
+
 class LoudnessBank:
     """`meters` x lsp::dspu::LoudnessMeter(channels) sharing one configuration (mi_loudness_bank_*)."""
     WEIGHT_NONE, WEIGHT_A, WEIGHT_B, WEIGHT_C, WEIGHT_D, WEIGHT_K = range(6)
