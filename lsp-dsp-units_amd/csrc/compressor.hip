@@ -152,7 +152,7 @@ namespace
     }
 } // namespace
 
-struct mi_compressor_bank : mi_dynamics::bank<mi_compressor_settings_t, mi_compressor_params_t, device_state>
+struct mi_compressor_bank : mi_bank::settings_bank<mi_compressor_settings_t, mi_compressor_params_t, device_state>
 {
     static constexpr const char *NAME = "mi_compressor_bank";
 
@@ -170,6 +170,7 @@ struct mi_compressor_bank : mi_dynamics::bank<mi_compressor_settings_t, mi_compr
         p.k[0].gain = p.k[1].gain = 1.0f;
         return p;
     }
+    static device_state fresh_state() { return device_state{}; }
     static void compute(const mi_compressor_settings_t &s, mi_compressor_params_t &p) { compute_params(s, p); }
     template <class... Args> static void launch(dim3 grid, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, Args... args)
     {
@@ -181,12 +182,12 @@ namespace mi
 {
     int compressor_bank_set_params(mi_compressor_bank_t *b, uint32_t channel, const mi_compressor_params_t *p)
     {
-        return mi_dynamics::set_params(b, "compressor_bank_set_params", channel, p);
+        return mi_bank::set_params(b, "compressor_bank_set_params", channel, p);
     }
 
     int compressor_bank_set_state(mi_compressor_bank_t *b, uint32_t channel, float envelope, float peak, uint32_t hold, hipStream_t st)
     {
-        return mi_dynamics::set_state(b, "compressor_bank_set_state", channel, device_state{ envelope, peak, hold, 0 }, true, st);
+        return mi_bank::set_state(b, "compressor_bank_set_state", channel, device_state{ envelope, peak, hold, 0 }, true, st);
     }
 }
 
@@ -202,12 +203,12 @@ int mi_compressor_compute_params(const mi_compressor_settings_t *settings, mi_co
 
 int mi_compressor_bank_create(mi_compressor_bank_t **bank, uint32_t channels)           // Compressor.cpp:46-83
 {
-    return mi_dynamics::create(bank, "mi_compressor_bank_create", channels);
+    return mi_bank::create(bank, "mi_compressor_bank_create", channels);
 }
 
 int mi_compressor_bank_destroy(mi_compressor_bank_t *b)
 {
-    return mi_dynamics::destroy(b);
+    return mi_bank::destroy(b);
 }
 
 int mi_compressor_bank_set_sample_rate(mi_compressor_bank_t *b, uint32_t channel, uint32_t sample_rate)    // :420-426
@@ -294,17 +295,17 @@ int mi_compressor_bank_set_ratio(mi_compressor_bank_t *b, uint32_t channel, floa
 
 int mi_compressor_bank_update_settings(mi_compressor_bank_t *b, void *stream)                              // :89-220
 {
-    return mi_dynamics::update_settings(b, "mi_compressor_bank_update_settings", stream);
+    return mi_bank::update_settings(b, "mi_compressor_bank_update_settings", stream);
 }
 
 int mi_compressor_bank_clear(mi_compressor_bank_t *b, void *stream)
 {
-    return mi_dynamics::clear(b, "mi_compressor_bank_clear", stream);
+    return mi_bank::clear(b, "mi_compressor_bank_clear", stream);
 }
 
 int mi_compressor_bank_get_params(const mi_compressor_bank_t *b, uint32_t channel, mi_compressor_params_t *params)
 {
-    return mi_dynamics::get_params(b, "mi_compressor_bank_get_params", channel, params);
+    return mi_bank::get_params(b, "mi_compressor_bank_get_params", channel, params);
 }
 
 int mi_compressor_bank_get_state(mi_compressor_bank_t *b, uint32_t channel, float *envelope, float *peak, uint32_t *hold,

@@ -86,70 +86,55 @@ namespace
     }
 } // namespace
 
-struct mi_correlometer_bank
+struct mi_correlometer_bank : bank_core
 {
-    bank_core core;
 };
 
 extern "C" {
 
 int mi_correlometer_bank_create(mi_correlometer_bank_t **bank, uint32_t channels, uint32_t max_period)       // :68-101
 {
-    MI_REQUIRE(bank != nullptr, MI_EINVAL, "mi_correlometer_bank_create: NULL result pointer");
-    *bank = nullptr;
-    mi_correlometer_bank *b = new (std::nothrow) mi_correlometer_bank();
-    MI_REQUIRE(b != nullptr, MI_ENOMEM, "mi_correlometer_bank_create: out of host memory");
-    const int r = core_create(b->core, "mi_correlometer_bank", channels, max_period);
-    if (r != MI_OK)
-    {
-        delete b;
-        return r;
-    }
-    *bank = b;
-    return MI_OK;
+    return core_create(bank, "mi_correlometer_bank_create", "mi_correlometer_bank", channels, max_period);
 }
 
 int mi_correlometer_bank_destroy(mi_correlometer_bank_t *b)
 {
-    if (b == nullptr)
-        return MI_OK;
-    core_destroy(b->core);
-    delete b;
-    return MI_OK;
+    return core_destroy(b);
 }
 
 int mi_correlometer_bank_set_period(mi_correlometer_bank_t *b, uint32_t channel, uint32_t period)            // :103-111
 {
     MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_correlometer_bank_set_period: NULL bank");
-    return core_set_period(b->core, channel, period, P_WINDOW);            // CF_UPDATE: nWindow = nPeriod at the next process()
+    return core_set_period(*b, channel, period, P_WINDOW);            // CF_UPDATE: nWindow = nPeriod at the next process()
 }
 
 int mi_correlometer_bank_clear(mi_correlometer_bank_t *b, uint32_t channel)                                  // :122-132
 {
     MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_correlometer_bank_clear: NULL bank");
-    return core_clear(b->core, channel, true);
+    return core_clear(*b, channel, true);
 }
 
 int mi_correlometer_bank_update_settings(mi_correlometer_bank_t *b, void *stream)
 {
     MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_correlometer_bank_update_settings: NULL bank");
-    return core_update(b->core, mi::as_stream(stream));
+    return core_update(*b, mi::as_stream(stream));
 }
 
 int mi_correlometer_bank_get_params(const mi_correlometer_bank_t *b, uint32_t channel, mi_correlometer_params_t *params)
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_correlometer_bank_get_params: NULL bank");
-    MI_REQUIRE(channel < b->core.channels && params != nullptr, MI_EINVAL, "mi_correlometer_bank_get_params: bad argument");
-    params->period = b->core.cfg[channel].period, params->capacity = b->core.capacity, params->max_period = b->core.max_period;
+    const int r = mi_bank::get_checks(b, "mi_correlometer_bank_get_params", channel, params);
+    if (r != MI_OK)
+        return r;
+    params->period = b->cfg[channel].period, params->capacity = b->capacity, params->max_period = b->max_period;
     return MI_OK;
 }
 
 int mi_correlometer_bank_get_state(mi_correlometer_bank_t *b, uint32_t channel, mi_correlometer_state_t *state, void *stream)
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_correlometer_bank_get_state: NULL bank");
-    MI_REQUIRE(channel < b->core.channels && state != nullptr, MI_EINVAL, "mi_correlometer_bank_get_state: bad argument");
     meter_state s;
-    const int r = mi::read_state(&s, b->core.d_state + channel, mi::as_stream(stream));
+    int r = mi_bank::get_checks(b, "mi_correlometer_bank_get_state", channel, state);
+    if (r == MI_OK)
+        r = mi_bank::get_state(b, "mi_correlometer_bank_get_state", channel, &s, stream);
     if (r != MI_OK)
         return r;
     state->v = s.sum[0], state->a = s.sum[1], state->b = s.sum[2], state->head = s.head, state->window = s.window;
@@ -162,20 +147,20 @@ int mi_correlometer_bank_set_state(mi_correlometer_bank_t *b, uint32_t channel, 
     MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_correlometer_bank_set_state: NULL bank");
     MI_REQUIRE(state != nullptr, MI_EINVAL, "mi_correlometer_bank_set_state: NULL state");
     const meter_state s = { { state->v, state->a, state->b }, state->head, state->window };
-    return core_set_state(b->core, channel, s, zero_rings != 0, mi::as_stream(stream));
+    return core_set_state(*b, channel, s, zero_rings != 0, mi::as_stream(stream));
 }
 
 int mi_correlometer_bank_process(mi_correlometer_bank_t *b, float *out, const float *a, const float *in_b, size_t count,
                                  size_t out_stride, size_t a_stride, size_t b_stride, void *stream)           // :134-184
 {
     MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_correlometer_bank_process: NULL bank");
-    bank_core &k = b->core;
+    bank_core &k = *b;
     hipStream_t st = mi::as_stream(stream);
     const int r = core_update(k, st);
     if (r != MI_OK || count == 0)
         return r;
     uint32_t vec = 0;
-    const int c = core_check(k, out, a, in_b, count, out_stride, a_stride, b_stride, &vec);
+    const int c = core_check(k, "mi_correlometer_bank_process", out, a, in_b, count, out_stride, a_stride, b_stride, &vec);
     if (c != MI_OK)
         return c;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;

@@ -273,7 +273,7 @@ namespace
 
 } // namespace
 
-struct mi_dynproc_bank : mi_dynamics::bank<mi_dynproc_settings_t, mi_dynproc_params_t, device_state>
+struct mi_dynproc_bank : mi_bank::settings_bank<mi_dynproc_settings_t, mi_dynproc_params_t, device_state>
 {
     static constexpr const char *NAME = "mi_dynproc_bank";
 
@@ -290,6 +290,7 @@ struct mi_dynproc_bank : mi_dynamics::bank<mi_dynproc_settings_t, mi_dynproc_par
         p.attacks = p.releases = 1;
         return p;
     }
+    static device_state fresh_state() { return device_state{}; }
     static void compute(const mi_dynproc_settings_t &s, mi_dynproc_params_t &p) { mi_dynproc_compute_params(&s, &p); }
     template <class... Args> static void launch(dim3 grid, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, Args... args)
     {
@@ -319,17 +320,17 @@ namespace mi
 {
     int dynproc_bank_set_params(mi_dynproc_bank_t *b, uint32_t channel, const mi_dynproc_params_t *p)
     {
-        const int r = mi_dynamics::set_params_checks(b, "dynproc_bank_set_params", channel, p);
+        const int r = mi_bank::set_params_checks(b, "dynproc_bank_set_params", channel, p);
         if (r != MI_OK)
             return r;
         MI_REQUIRE(p->splines <= uint32_t(DOTS) && p->attacks >= 1 && p->attacks <= uint32_t(RANGES) && p->releases >= 1 &&
                    p->releases <= uint32_t(RANGES), MI_EINVAL, "dynproc_bank_set_params: counts out of range");
-        return mi_dynamics::set_params_store(b, channel, p);
+        return mi_bank::set_params_store(b, channel, p);
     }
 
     int dynproc_bank_set_state(mi_dynproc_bank_t *b, uint32_t channel, float envelope, float peak, uint32_t hold, hipStream_t st)
     {
-        return mi_dynamics::set_state(b, "dynproc_bank_set_state", channel, device_state{ envelope, peak, hold, 0 }, true, st);
+        return mi_bank::set_state(b, "dynproc_bank_set_state", channel, device_state{ envelope, peak, hold, 0 }, true, st);
     }
 }
 
@@ -337,12 +338,12 @@ extern "C" {
 
 int mi_dynproc_bank_create(mi_dynproc_bank_t **bank, uint32_t channels)                 // DynamicProcessor.cpp:43-74
 {
-    return mi_dynamics::create(bank, "mi_dynproc_bank_create", channels);
+    return mi_bank::create(bank, "mi_dynproc_bank_create", channels);
 }
 
 int mi_dynproc_bank_destroy(mi_dynproc_bank_t *b)
 {
-    return mi_dynamics::destroy(b);
+    return mi_bank::destroy(b);
 }
 
 int mi_dynproc_bank_set_sample_rate(mi_dynproc_bank_t *b, uint32_t channel, uint32_t sample_rate)         // :80-86
@@ -452,17 +453,17 @@ int mi_dynproc_bank_set_hold(mi_dynproc_bank_t *b, uint32_t channel, float hold)
 
 int mi_dynproc_bank_update_settings(mi_dynproc_bank_t *b, void *stream)                                    // :339-395
 {
-    return mi_dynamics::update_settings(b, "mi_dynproc_bank_update_settings", stream);
+    return mi_bank::update_settings(b, "mi_dynproc_bank_update_settings", stream);
 }
 
 int mi_dynproc_bank_clear(mi_dynproc_bank_t *b, void *stream)
 {
-    return mi_dynamics::clear(b, "mi_dynproc_bank_clear", stream);
+    return mi_bank::clear(b, "mi_dynproc_bank_clear", stream);
 }
 
 int mi_dynproc_bank_get_params(const mi_dynproc_bank_t *b, uint32_t channel, mi_dynproc_params_t *params)
 {
-    return mi_dynamics::get_params(b, "mi_dynproc_bank_get_params", channel, params);
+    return mi_bank::get_params(b, "mi_dynproc_bank_get_params", channel, params);
 }
 
 int mi_dynproc_bank_get_state(mi_dynproc_bank_t *b, uint32_t channel, float *envelope, float *peak, uint32_t *hold,

@@ -147,7 +147,7 @@ namespace
     }
 } // namespace
 
-struct mi_expander_bank : mi_dynamics::bank<mi_expander_settings_t, mi_expander_params_t, device_state>
+struct mi_expander_bank : mi_bank::settings_bank<mi_expander_settings_t, mi_expander_params_t, device_state>
 {
     static constexpr const char *NAME = "mi_expander_bank";
 
@@ -164,6 +164,7 @@ struct mi_expander_bank : mi_dynamics::bank<mi_expander_settings_t, mi_expander_
         p.upward = 1;
         return p;
     }
+    static device_state fresh_state() { return device_state{}; }
     static void compute(const mi_expander_settings_t &s, mi_expander_params_t &p) { compute_params(s, p); }
     template <class... Args> static void launch(dim3 grid, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, Args... args)
     {
@@ -175,12 +176,12 @@ namespace mi
 {
     int expander_bank_set_params(mi_expander_bank_t *b, uint32_t channel, const mi_expander_params_t *p)
     {
-        return mi_dynamics::set_params(b, "expander_bank_set_params", channel, p);
+        return mi_bank::set_params(b, "expander_bank_set_params", channel, p);
     }
 
     int expander_bank_set_state(mi_expander_bank_t *b, uint32_t channel, float envelope, float peak, uint32_t hold, hipStream_t st)
     {
-        return mi_dynamics::set_state(b, "expander_bank_set_state", channel, device_state{ envelope, peak, hold, 0 }, true, st);
+        return mi_bank::set_state(b, "expander_bank_set_state", channel, device_state{ envelope, peak, hold, 0 }, true, st);
     }
 }
 
@@ -196,12 +197,12 @@ int mi_expander_compute_params(const mi_expander_settings_t *settings, mi_expand
 
 int mi_expander_bank_create(mi_expander_bank_t **bank, uint32_t channels)               // Expander.cpp:70-101
 {
-    return mi_dynamics::create(bank, "mi_expander_bank_create", channels);
+    return mi_bank::create(bank, "mi_expander_bank_create", channels);
 }
 
 int mi_expander_bank_destroy(mi_expander_bank_t *b)
 {
-    return mi_dynamics::destroy(b);
+    return mi_bank::destroy(b);
 }
 
 int mi_expander_bank_set_sample_rate(mi_expander_bank_t *b, uint32_t channel, uint32_t sample_rate)       // :157-163
@@ -278,17 +279,17 @@ int mi_expander_bank_set_ratio(mi_expander_bank_t *b, uint32_t channel, float ra
 
 int mi_expander_bank_update_settings(mi_expander_bank_t *b, void *stream)                                  // :200-245
 {
-    return mi_dynamics::update_settings(b, "mi_expander_bank_update_settings", stream);
+    return mi_bank::update_settings(b, "mi_expander_bank_update_settings", stream);
 }
 
 int mi_expander_bank_clear(mi_expander_bank_t *b, void *stream)
 {
-    return mi_dynamics::clear(b, "mi_expander_bank_clear", stream);
+    return mi_bank::clear(b, "mi_expander_bank_clear", stream);
 }
 
 int mi_expander_bank_get_params(const mi_expander_bank_t *b, uint32_t channel, mi_expander_params_t *params)
 {
-    return mi_dynamics::get_params(b, "mi_expander_bank_get_params", channel, params);
+    return mi_bank::get_params(b, "mi_expander_bank_get_params", channel, params);
 }
 
 int mi_expander_bank_get_state(mi_expander_bank_t *b, uint32_t channel, float *envelope, float *peak, uint32_t *hold,

@@ -243,7 +243,7 @@ namespace
 
 } // namespace
 
-struct mi_gate_bank : mi_dynamics::bank<mi_gate_settings_t, mi_gate_params_t, gate_state>
+struct mi_gate_bank : mi_bank::settings_bank<mi_gate_settings_t, mi_gate_params_t, gate_state>
 {
     static constexpr const char *NAME = "mi_gate_bank";
 
@@ -254,6 +254,7 @@ struct mi_gate_bank : mi_dynamics::bank<mi_gate_settings_t, mi_gate_params_t, ga
         return s;
     }
     static mi_gate_params_t fresh_params() { return mi_gate_params_t{}; }
+    static gate_state fresh_state() { return gate_state{}; }
     static void compute(const mi_gate_settings_t &s, mi_gate_params_t &p) { compute_params(s, p); }
     template <class... Args> static void launch(dim3 grid, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, Args... args)
     {
@@ -265,12 +266,12 @@ namespace mi
 {
     int gate_bank_set_params(mi_gate_bank_t *b, uint32_t channel, const mi_gate_params_t *p)
     {
-        return mi_dynamics::set_params(b, "gate_bank_set_params", channel, p);
+        return mi_bank::set_params(b, "gate_bank_set_params", channel, p);
     }
 
     int gate_bank_set_state(mi_gate_bank_t *b, uint32_t channel, float envelope, float peak, uint32_t hold, uint32_t curve, hipStream_t st)
     {
-        return mi_dynamics::set_state(b, "gate_bank_set_state", channel, gate_state{ envelope, peak, hold, curve }, curve <= 1, st);
+        return mi_bank::set_state(b, "gate_bank_set_state", channel, gate_state{ envelope, peak, hold, curve }, curve <= 1, st);
     }
 }
 
@@ -286,12 +287,12 @@ int mi_gate_compute_params(const mi_gate_settings_t *settings, mi_gate_params_t 
 
 int mi_gate_bank_create(mi_gate_bank_t **bank, uint32_t channels)                       // Gate.cpp:41-74
 {
-    return mi_dynamics::create(bank, "mi_gate_bank_create", channels);
+    return mi_bank::create(bank, "mi_gate_bank_create", channels);
 }
 
 int mi_gate_bank_destroy(mi_gate_bank_t *b)
 {
-    return mi_dynamics::destroy(b);
+    return mi_bank::destroy(b);
 }
 
 int mi_gate_bank_set_sample_rate(mi_gate_bank_t *b, uint32_t channel, uint32_t sample_rate)               // :138-144
@@ -357,24 +358,24 @@ int mi_gate_bank_set_hold(mi_gate_bank_t *b, uint32_t channel, float hold)      
 
 int mi_gate_bank_update_settings(mi_gate_bank_t *b, void *stream)                                          // :180-205
 {
-    return mi_dynamics::update_settings(b, "mi_gate_bank_update_settings", stream);
+    return mi_bank::update_settings(b, "mi_gate_bank_update_settings", stream);
 }
 
 int mi_gate_bank_clear(mi_gate_bank_t *b, void *stream)
 {
-    return mi_dynamics::clear(b, "mi_gate_bank_clear", stream);
+    return mi_bank::clear(b, "mi_gate_bank_clear", stream);
 }
 
 int mi_gate_bank_get_params(const mi_gate_bank_t *b, uint32_t channel, mi_gate_params_t *params)
 {
-    return mi_dynamics::get_params(b, "mi_gate_bank_get_params", channel, params);
+    return mi_bank::get_params(b, "mi_gate_bank_get_params", channel, params);
 }
 
 int mi_gate_bank_get_state(mi_gate_bank_t *b, uint32_t channel, float *envelope, float *peak, uint32_t *hold, uint32_t *curve,
                            void *stream)
 {
     gate_state s;
-    const int r = mi_dynamics::get_state(b, "mi_gate_bank_get_state", channel, &s, stream);
+    const int r = mi_bank::get_state(b, "mi_gate_bank_get_state", channel, &s, stream);
     if (r != MI_OK)
         return r;
     if (envelope != nullptr) *envelope = s.e;

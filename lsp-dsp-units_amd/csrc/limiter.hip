@@ -21,6 +21,7 @@
 //
 // Inputs are finite: NaN is out of scope.  The patch, the tmp product and k round every operation on its own; divisions are
 // IEEE-rounded.
+#include "bank_core.h"
 #include "limiter_bank.h"
 #include "tile_chain_device.h"
 
@@ -289,9 +290,8 @@ namespace
     }
 } // namespace
 
-struct mi_limiter_bank
+struct mi_limiter_bank : mi_bank::tables<dev_params, limiter_state>     // params: what update_settings computed; up: of params and shapes
 {
-    uint32_t                            channels = 0;
     uint32_t                            max_sample_rate = 0;
     float                               max_lookahead = 0.0f;   // fMaxLookahead, ms
     uint32_t                            ml = 0;                 // nMaxLookahead
@@ -299,11 +299,7 @@ struct mi_limiter_bank
     std::vector<mi_limiter_settings_t>  cfg;            // the setters' values; threshold is fReqThreshold
     std::vector<float>                  thr;            // fThreshold
     std::vector<uint32_t>               update;         // nUpdate
-    std::vector<dev_params>             params;         // what update_settings computed
     std::vector<float>                  shapes;         // [channels][shape_cap]
-    mi::dirty_range                     up;             // where params and shapes differ from the device
-    dev_params                         *d_params = nullptr;     // [channels]
-    limiter_state                      *d_state = nullptr;      // [channels]
     float                              *d_window = nullptr;     // [channels][4 ml]
     float                              *d_history = nullptr;    // [channels][ml]
     float                              *d_shapes = nullptr;     // [channels][shape_cap]
@@ -378,68 +374,74 @@ namespace
         MI_HIP_CHECK(hipGetLastError());
         return MI_OK;
     }
+
+    constexpr size_t COUNT_LIMIT = size_t(1) << 30;     // of the samples of one call
+
+    // what create() does to the new, empty bank
+    int limiter_init(mi_limiter_bank *b, uint32_t channels, uint32_t max_sample_rate, float max_lookahead_ms, float mlf)
+    {
+        static_assert((size_t(4) * MI_LIMITER_MAX_LOOKAHEAD + size_t(3) * CHUNK) * sizeof(float) + 256 <= LDS_LIMIT, "the chunk's LDS");
+        b->channels = channels;
+        b->max_sample_rate = max_sample_rate;
+        b->max_lookahead = max_lookahead_ms;
+        b->ml = uint32_t(mlf);
+        b->shape_cap = mi::limiter_patch_capacity(b->ml);
+        b->cfg.assign(channels, fresh_settings());
+        b->thr.assign(channels, 1.0f);
+        b->update.assign(channels, UP_ALL);
+        b->shapes.assign(size_t(channels) * b->shape_cap, 0.0f);
+        const int r = mi_bank::alloc(*b, "mi_limiter_bank_create", dev_params{}, limiter_state{});
+        if (r != MI_OK)
+            return r;
+        const size_t wbytes = size_t(channels) * (4 * b->ml) * sizeof(float), hbytes = size_t(channels) * b->ml * sizeof(float);
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_window), wbytes + 16);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_history), hbytes + 16);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_shapes), b->shapes.size() * sizeof(float));
+        if (e == hipSuccess) e = hipMemset(b->d_shapes, 0, b->shapes.size() * sizeof(float));
+        // a chunk of 8192 samples at the largest ML takes all of a workgroup's LDS
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(limiter_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                     int(LDS_LIMIT - 256));
+        if (e == hipSuccess)
+        {
+            hipLaunchKernelGGL(limiter_clear_kernel, dim3(channels), dim3(256), 0, nullptr, b->d_state, b->d_window, b->d_history, b->ml);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        MI_REQUIRE(e == hipSuccess, MI_EHIP, "mi_limiter_bank_create: %s", hipGetErrorString(e));
+        return MI_OK;
+    }
 } // namespace
 
 extern "C" {
 
 int mi_limiter_bank_create(mi_limiter_bank_t **bank, uint32_t channels, uint32_t max_sample_rate, float max_lookahead_ms)   // :47-109
 {
-    MI_REQUIRE(bank != nullptr, MI_EINVAL, "mi_limiter_bank_create: NULL result pointer");
-    *bank = nullptr;
-    MI_REQUIRE(channels > 0 && channels <= (1u << 20), MI_EINVAL, "mi_limiter_bank_create: channels must be 1 .. 1048576");
+    int r = mi_bank::open_checks(bank, "mi_limiter_bank_create", channels);
+    if (r != MI_OK)
+        return r;
     MI_REQUIRE(max_lookahead_ms >= 0.0f && max_lookahead_ms <= 1e6f, MI_EINVAL, "mi_limiter_bank_create: bad maximum look-ahead");
     const float mlf = (max_lookahead_ms * 0.001f) * float(max_sample_rate);         // millis_to_samples, :89
     MI_REQUIRE(mlf < float(MI_LIMITER_MAX_LOOKAHEAD + 1), MI_EINVAL,
                "mi_limiter_bank_create: a maximum look-ahead of %.0f samples exceeds MI_LIMITER_MAX_LOOKAHEAD = %d", double(mlf),
                MI_LIMITER_MAX_LOOKAHEAD);
-    MI_REQUIRE(mi_dspu_device_count() > 0, MI_ENODEV, "no HIP device available (there is no CPU fallback)");
-    static_assert((size_t(4) * MI_LIMITER_MAX_LOOKAHEAD + size_t(3) * CHUNK) * sizeof(float) + 256 <= LDS_LIMIT, "the chunk's LDS");
-    mi_limiter_bank *b = new (std::nothrow) mi_limiter_bank();
-    MI_REQUIRE(b != nullptr, MI_ENOMEM, "mi_limiter_bank_create: out of host memory");
-    b->channels = channels;
-    b->max_sample_rate = max_sample_rate;
-    b->max_lookahead = max_lookahead_ms;
-    b->ml = uint32_t(mlf);
-    b->shape_cap = mi::limiter_patch_capacity(b->ml);
-    b->cfg.assign(channels, fresh_settings());
-    b->thr.assign(channels, 1.0f);
-    b->update.assign(channels, UP_ALL);
-    b->params.assign(channels, dev_params{});
-    b->shapes.assign(size_t(channels) * b->shape_cap, 0.0f);
-    const size_t wbytes = size_t(channels) * (4 * b->ml) * sizeof(float), hbytes = size_t(channels) * b->ml * sizeof(float);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_params), size_t(channels) * sizeof(dev_params));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_state), size_t(channels) * sizeof(limiter_state));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_window), wbytes + 16);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_history), hbytes + 16);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_shapes), b->shapes.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(b->d_params, b->params.data(), size_t(channels) * sizeof(dev_params), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(b->d_shapes, 0, b->shapes.size() * sizeof(float));
-    // a chunk of 8192 samples at the largest ML takes all of a workgroup's LDS
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(limiter_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 int(LDS_LIMIT - 256));
-    if (e == hipSuccess)
+    r = mi_bank::open_new(bank, "mi_limiter_bank_create");
+    if (r != MI_OK)
+        return r;
+    r = limiter_init(*bank, channels, max_sample_rate, max_lookahead_ms, mlf);
+    if (r != MI_OK)
     {
-        hipLaunchKernelGGL(limiter_clear_kernel, dim3(channels), dim3(256), 0, nullptr, b->d_state, b->d_window, b->d_history, b->ml);
-        e = hipGetLastError();
+        mi_limiter_bank_destroy(*bank);
+        *bank = nullptr;
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess)
-    {
-        mi_limiter_bank_destroy(b);
-        return mi::fail(MI_EHIP, "mi_limiter_bank_create: %s", hipGetErrorString(e));
-    }
-    *bank = b;
-    return MI_OK;
+    return r;
 }
 
 int mi_limiter_bank_destroy(mi_limiter_bank_t *b)
 {
     if (b == nullptr)
         return MI_OK;
-    (void)hipFree(b->d_params); (void)hipFree(b->d_state); (void)hipFree(b->d_window); (void)hipFree(b->d_history);
-    (void)hipFree(b->d_shapes);
-    delete b;
-    return MI_OK;
+    (void)hipFree(b->d_window); (void)hipFree(b->d_history); (void)hipFree(b->d_shapes);
+    return mi_bank::destroy(b);
 }
 
 int mi_limiter_bank_set_sample_rate(mi_limiter_bank_t *b, uint32_t channel, uint32_t sample_rate)          // :154-162
@@ -577,10 +579,10 @@ int mi_limiter_bank_clear(mi_limiter_bank_t *b, void *stream)
 
 int mi_limiter_bank_get_params(const mi_limiter_bank_t *b, uint32_t channel, mi_limiter_params_t *params)
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_limiter_bank_get_params: NULL bank");
-    MI_REQUIRE(channel < b->channels && params != nullptr, MI_EINVAL, "mi_limiter_bank_get_params: bad argument");
-    *params = b->params[channel].p;
-    return MI_OK;
+    const int r = mi_bank::get_checks(b, "mi_limiter_bank_get_params", channel, params);
+    if (r == MI_OK)
+        *params = b->params[channel].p;
+    return r;
 }
 
 int mi_limiter_bank_get_patch(mi_limiter_bank_t *b, uint32_t channel, float *shape, size_t capacity, uint32_t *count, void *stream)
@@ -614,10 +616,8 @@ int mi_limiter_bank_get_latency(mi_limiter_bank_t *b, uint32_t channel, uint32_t
 int mi_limiter_bank_get_state(mi_limiter_bank_t *b, uint32_t channel, uint32_t *head, float *envelope, uint32_t *patches,
                               uint32_t *chunks, uint32_t *overrun, void *stream)
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_limiter_bank_get_state: NULL bank");
-    MI_REQUIRE(channel < b->channels, MI_EINVAL, "mi_limiter_bank_get_state: channel %u out of range", channel);
     limiter_state s;
-    const int r = mi::read_state(&s, b->d_state + channel, mi::as_stream(stream));
+    const int r = mi_bank::get_state(b, "mi_limiter_bank_get_state", channel, &s, stream);
     if (r != MI_OK)
         return r;
     if (head != nullptr) *head = s.head;
@@ -636,11 +636,11 @@ int mi_limiter_bank_process(mi_limiter_bank_t *b, float *gain, const float *sc, 
     const int r = limiter_update(b, st);
     if (r != MI_OK || count == 0)
         return r;
-    MI_REQUIRE(gain != nullptr && sc != nullptr, MI_EINVAL, "mi_limiter_bank_process: NULL buffer");
-    MI_REQUIRE(count < (size_t(1) << 30), MI_EINVAL, "mi_limiter_bank_process: count %zu too large", count);
-    MI_REQUIRE(b->channels == 1 || (gain_stride >= count && sc_stride >= count), MI_EINVAL,
-               "mi_limiter_bank_process: strides (%zu, %zu) shorter than count %zu", gain_stride, sc_stride, count);
-    MI_REQUIRE(gain != sc || gain_stride == sc_stride, MI_EINVAL, "mi_limiter_bank_process: in place with different strides");
+    const int k = mi_bank::check_rows("mi_limiter_bank_process", b->channels, count, COUNT_LIMIT,
+                                      { { gain, gain_stride, count, mi_bank::REQUIRED | mi_bank::OUTPUT },
+                                        { sc, sc_stride, count, mi_bank::REQUIRED } });
+    if (k != MI_OK)
+        return k;
     return limiter_launch(b, gain, nullptr, sc, count, gain_stride, 0, sc_stride, st);
 }
 
@@ -652,12 +652,11 @@ int mi_limiter_bank_process_apply(mi_limiter_bank_t *b, float *dst, const float 
     const int r = limiter_update(b, st);
     if (r != MI_OK || count == 0)
         return r;
-    MI_REQUIRE(dst != nullptr && audio != nullptr && sc != nullptr, MI_EINVAL, "mi_limiter_bank_process_apply: NULL buffer");
-    MI_REQUIRE(count < (size_t(1) << 30), MI_EINVAL, "mi_limiter_bank_process_apply: count %zu too large", count);
-    MI_REQUIRE(b->channels == 1 || (dst_stride >= count && audio_stride >= count && sc_stride >= count), MI_EINVAL,
-               "mi_limiter_bank_process_apply: strides (%zu, %zu, %zu) shorter than count %zu", dst_stride, audio_stride, sc_stride, count);
-    MI_REQUIRE((dst != audio || dst_stride == audio_stride) && (dst != sc || dst_stride == sc_stride), MI_EINVAL,
-               "mi_limiter_bank_process_apply: in place with different strides");
+    const int k = mi_bank::check_rows("mi_limiter_bank_process_apply", b->channels, count, COUNT_LIMIT,
+                                      { { dst, dst_stride, count, mi_bank::REQUIRED | mi_bank::OUTPUT },
+                                        { audio, audio_stride, count, mi_bank::REQUIRED }, { sc, sc_stride, count, mi_bank::REQUIRED } });
+    if (k != MI_OK)
+        return k;
     return limiter_launch(b, dst, audio, sc, count, dst_stride, audio_stride, sc_stride, st);
 }
 

@@ -13,6 +13,7 @@
 // their 8 (N - 1) values phase by phase (coefficients in scalar registers, packed multiplies and adds for a <= 10, a tap
 // loop over LDS for a = 62) into one LDS plane per phase; then the tile's N x 8 x BLOCK outputs leave as contiguous
 // 16-byte stores, lane by lane adjacent, each lane picking its four values out of the planes.
+#include "bank_core.h"
 #include "lanczos_device.h"
 
 #include <new>
@@ -416,14 +417,13 @@ namespace
         return MI_OK;
     }
 
+    // rows of count x times samples.  in_place: dst may be src (process()); upsample() and downsample() refuse that themselves
     int os_check(const mi_oversampler_bank *b, const char *what, const void *dst, const void *src, size_t count, size_t dst_stride,
-                 size_t src_stride, size_t dst_times, size_t src_times)
+                 size_t src_stride, size_t dst_times, size_t src_times, bool in_place)
     {
-        MI_REQUIRE(dst != nullptr && src != nullptr, MI_EINVAL, "%s: NULL buffer", what);
-        MI_REQUIRE(count < (size_t(1) << 27), MI_EINVAL, "%s: count %zu too large", what, count);
-        MI_REQUIRE(b->channels == 1 || (dst_stride >= count * dst_times && src_stride >= count * src_times), MI_EINVAL,
-                   "%s: strides (%zu, %zu) shorter than the rows of %zu samples", what, dst_stride, src_stride, count);
-        return MI_OK;
+        return mi_bank::check_rows(what, b->channels, count, size_t(1) << 27,
+                                   { { dst, dst_stride, count * dst_times, mi_bank::REQUIRED | (in_place ? mi_bank::OUTPUT : 0u) },
+                                     { src, src_stride, count * src_times, mi_bank::REQUIRED } });
     }
 } // namespace
 
@@ -442,22 +442,22 @@ int mi_oversampler_coefficients(uint32_t mode, float *h, size_t *count)
 
 int mi_oversampler_bank_create(mi_oversampler_bank_t **bank, uint32_t channels)        // Oversampler.cpp:53-93
 {
-    MI_REQUIRE(bank != nullptr, MI_EINVAL, "mi_oversampler_bank_create: NULL result pointer");
+    int r = mi_bank::open(bank, "mi_oversampler_bank_create", channels, 65535u);
+    if (r != MI_OK)
+        return r;
+    mi_oversampler_bank *b = *bank;
     *bank = nullptr;
-    MI_REQUIRE(channels > 0 && channels <= 65535u, MI_EINVAL, "mi_oversampler_bank_create: channels must be 1 .. 65535");
-    MI_REQUIRE(mi_dspu_device_count() > 0, MI_ENODEV, "no HIP device available (there is no CPU fallback)");
-    mi_oversampler_bank *b = new (std::nothrow) mi_oversampler_bank();
     f32x2 *table = new (std::nothrow) f32x2[TABLE_PAIRS];
-    if (b == nullptr || table == nullptr)
+    if (table == nullptr)
     {
-        delete b; delete[] table;
+        delete b;
         return mi::fail(MI_ENOMEM, "mi_oversampler_bank_create: out of host memory");
     }
     b->channels = channels;
     for (int a : LATENCIES)
         for (int n : FACTORS)
             phase_pairs(n, a, table + table_offset(n, a));
-    int r = mi_biquad_bank_create(&b->biquads, channels, FILTER_SECTIONS);
+    r = mi_biquad_bank_create(&b->biquads, channels, FILTER_SECTIONS);
     hipError_t e = hipSuccess;
     if (r == MI_OK)
     {
@@ -610,7 +610,7 @@ int mi_oversampler_bank_upsample(mi_oversampler_bank_t *b, float *dst, const flo
     if (count == 0)
         return MI_OK;
     const size_t n = size_t(mode_times(b->mode));
-    const int r = os_check(b, "mi_oversampler_bank_upsample", dst, src, count, dst_stride, src_stride, n, 1);
+    const int r = os_check(b, "mi_oversampler_bank_upsample", dst, src, count, dst_stride, src_stride, n, 1, false);
     if (r != MI_OK)
         return r;
     MI_REQUIRE(dst != src, MI_EINVAL, "mi_oversampler_bank_upsample: dst and src must not overlap");
@@ -627,7 +627,7 @@ int mi_oversampler_bank_downsample(mi_oversampler_bank_t *b, float *dst, const f
     if (count == 0)
         return MI_OK;
     const size_t n = size_t(mode_times(b->mode));
-    int r = os_check(b, "mi_oversampler_bank_downsample", dst, src, count, dst_stride, src_stride, 1, n);
+    int r = os_check(b, "mi_oversampler_bank_downsample", dst, src, count, dst_stride, src_stride, 1, n, false);
     if (r != MI_OK)
         return r;
     MI_REQUIRE(dst != src, MI_EINVAL, "mi_oversampler_bank_downsample: dst and src must not overlap");
@@ -654,10 +654,9 @@ int mi_oversampler_bank_process(mi_oversampler_bank_t *b, float *dst, const floa
     MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_oversampler_bank_process: NULL bank");
     if (count == 0)
         return MI_OK;
-    int r = os_check(b, "mi_oversampler_bank_process", dst, src, count, dst_stride, src_stride, 1, 1);
+    int r = os_check(b, "mi_oversampler_bank_process", dst, src, count, dst_stride, src_stride, 1, 1, true);
     if (r != MI_OK)
         return r;
-    MI_REQUIRE(dst != src || dst_stride == src_stride, MI_EINVAL, "mi_oversampler_bank_process: in place with different strides");
     hipStream_t st = mi::as_stream(stream);
     if (b->mode == MI_OM_NONE)                              // :731-737: the callback sees the base-rate rows, or a copy happens
     {

@@ -86,53 +86,37 @@ namespace
     }
 } // namespace
 
-struct mi_panometer_bank
+struct mi_panometer_bank : bank_core
 {
-    bank_core core;
 };
 
 extern "C" {
 
 int mi_panometer_bank_create(mi_panometer_bank_t **bank, uint32_t channels, uint32_t max_period)             // :71-100
 {
-    MI_REQUIRE(bank != nullptr, MI_EINVAL, "mi_panometer_bank_create: NULL result pointer");
-    *bank = nullptr;
-    mi_panometer_bank *b = new (std::nothrow) mi_panometer_bank();
-    MI_REQUIRE(b != nullptr, MI_ENOMEM, "mi_panometer_bank_create: out of host memory");
-    const int r = core_create(b->core, "mi_panometer_bank", channels, max_period);
-    if (r != MI_OK)
-    {
-        delete b;
-        return r;
-    }
-    *bank = b;
-    return MI_OK;
+    return core_create(bank, "mi_panometer_bank_create", "mi_panometer_bank", channels, max_period);
 }
 
 int mi_panometer_bank_destroy(mi_panometer_bank_t *b)
 {
-    if (b == nullptr)
-        return MI_OK;
-    core_destroy(b->core);
-    delete b;
-    return MI_OK;
+    return core_destroy(b);
 }
 
 int mi_panometer_bank_set_period(mi_panometer_bank_t *b, uint32_t channel, uint32_t period)                  // :112-123
 {
     MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_panometer_bank_set_period: NULL bank");
-    return core_set_period(b->core, channel, period, P_WINDOW | P_ZERO_SUMS);      // at once: nWindow = nPeriod, both sums 0
+    return core_set_period(*b, channel, period, P_WINDOW | P_ZERO_SUMS);      // at once: nWindow = nPeriod, both sums 0
 }
 
 int mi_panometer_bank_set_pan_law(mi_panometer_bank_t *b, uint32_t channel, uint32_t law)                    // :102-105
 {
     MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_panometer_bank_set_pan_law: NULL bank");
-    MI_REQUIRE(channel < b->core.channels, MI_EINVAL, "mi_panometer_bank_set_pan_law: channel %u out of range", channel);
+    MI_REQUIRE(channel < b->channels, MI_EINVAL, "mi_panometer_bank_set_pan_law: channel %u out of range", channel);
     MI_REQUIRE(law <= MI_PAN_LAW_EQUAL_POWER, MI_EINVAL, "mi_panometer_bank_set_pan_law: law %u", law);
-    if (b->core.cfg[channel].law != law)
+    if (b->cfg[channel].law != law)
     {
-        b->core.cfg[channel].law = law;
-        b->core.up.touch(channel);
+        b->cfg[channel].law = law;
+        b->up.touch(channel);
     }
     return MI_OK;
 }
@@ -140,11 +124,11 @@ int mi_panometer_bank_set_pan_law(mi_panometer_bank_t *b, uint32_t channel, uint
 int mi_panometer_bank_set_default_pan(mi_panometer_bank_t *b, uint32_t channel, float default_pan)           // :107-110
 {
     MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_panometer_bank_set_default_pan: NULL bank");
-    MI_REQUIRE(channel < b->core.channels, MI_EINVAL, "mi_panometer_bank_set_default_pan: channel %u out of range", channel);
-    if (memcmp(&b->core.cfg[channel].dflt, &default_pan, sizeof(float)) != 0)
+    MI_REQUIRE(channel < b->channels, MI_EINVAL, "mi_panometer_bank_set_default_pan: channel %u out of range", channel);
+    if (memcmp(&b->cfg[channel].dflt, &default_pan, sizeof(float)) != 0)
     {
-        b->core.cfg[channel].dflt = default_pan;
-        b->core.up.touch(channel);
+        b->cfg[channel].dflt = default_pan;
+        b->up.touch(channel);
     }
     return MI_OK;
 }
@@ -152,31 +136,32 @@ int mi_panometer_bank_set_default_pan(mi_panometer_bank_t *b, uint32_t channel, 
 int mi_panometer_bank_clear(mi_panometer_bank_t *b, uint32_t channel)                                        // :125-131
 {
     MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_panometer_bank_clear: NULL bank");
-    return core_clear(b->core, channel, false);
+    return core_clear(*b, channel, false);
 }
 
 int mi_panometer_bank_update_settings(mi_panometer_bank_t *b, void *stream)
 {
     MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_panometer_bank_update_settings: NULL bank");
-    return core_update(b->core, mi::as_stream(stream));
+    return core_update(*b, mi::as_stream(stream));
 }
 
 int mi_panometer_bank_get_params(const mi_panometer_bank_t *b, uint32_t channel, mi_panometer_params_t *params)
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_panometer_bank_get_params: NULL bank");
-    MI_REQUIRE(channel < b->core.channels && params != nullptr, MI_EINVAL, "mi_panometer_bank_get_params: bad argument");
-    const channel_cfg &c = b->core.cfg[channel];
-    params->period = c.period, params->capacity = b->core.capacity, params->max_period = b->core.max_period, params->law = c.law;
+    const int r = mi_bank::get_checks(b, "mi_panometer_bank_get_params", channel, params);
+    if (r != MI_OK)
+        return r;
+    const channel_cfg &c = b->cfg[channel];
+    params->period = c.period, params->capacity = b->capacity, params->max_period = b->max_period, params->law = c.law;
     params->norm = c.norm, params->default_pan = c.dflt;
     return MI_OK;
 }
 
 int mi_panometer_bank_get_state(mi_panometer_bank_t *b, uint32_t channel, mi_panometer_state_t *state, void *stream)
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_panometer_bank_get_state: NULL bank");
-    MI_REQUIRE(channel < b->core.channels && state != nullptr, MI_EINVAL, "mi_panometer_bank_get_state: bad argument");
     meter_state s;
-    const int r = mi::read_state(&s, b->core.d_state + channel, mi::as_stream(stream));
+    int r = mi_bank::get_checks(b, "mi_panometer_bank_get_state", channel, state);
+    if (r == MI_OK)
+        r = mi_bank::get_state(b, "mi_panometer_bank_get_state", channel, &s, stream);
     if (r != MI_OK)
         return r;
     state->value_a = s.sum[0], state->value_b = s.sum[1], state->head = s.head, state->window = s.window;
@@ -189,20 +174,20 @@ int mi_panometer_bank_set_state(mi_panometer_bank_t *b, uint32_t channel, const 
     MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_panometer_bank_set_state: NULL bank");
     MI_REQUIRE(state != nullptr, MI_EINVAL, "mi_panometer_bank_set_state: NULL state");
     const meter_state s = { { state->value_a, state->value_b, 0.0f }, state->head, state->window };
-    return core_set_state(b->core, channel, s, zero_rings != 0, mi::as_stream(stream));
+    return core_set_state(*b, channel, s, zero_rings != 0, mi::as_stream(stream));
 }
 
 int mi_panometer_bank_process(mi_panometer_bank_t *b, float *out, const float *a, const float *in_b, size_t count,
                               size_t out_stride, size_t a_stride, size_t b_stride, void *stream)              // :133-216
 {
     MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_panometer_bank_process: NULL bank");
-    bank_core &k = b->core;
+    bank_core &k = *b;
     hipStream_t st = mi::as_stream(stream);
     const int r = core_update(k, st);
     if (r != MI_OK || count == 0)
         return r;
     uint32_t vec = 0;
-    const int c = core_check(k, out, a, in_b, count, out_stride, a_stride, b_stride, &vec);
+    const int c = core_check(k, "mi_panometer_bank_process", out, a, in_b, count, out_stride, a_stride, b_stride, &vec);
     if (c != MI_OK)
         return c;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;

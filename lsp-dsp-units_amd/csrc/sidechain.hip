@@ -19,6 +19,7 @@
 // rounded (sqrt_rn): out, fRmsValue, nRefresh and the position match tests/sidechain_ref.py bit for bit.
 //
 // Inputs are finite: NaN is out of scope.  Subnormals are kept (the float32 denormal mode is on).
+#include "bank_core.h"
 #include "sidechain_bank.h"
 #include "tile_chain_device.h"
 
@@ -360,17 +361,13 @@ namespace
     struct channel_cfg { uint32_t sample_rate; float reactivity; uint32_t mode, source, flags; float gain; };
 } // namespace
 
-struct mi_sidechain_bank
+struct mi_sidechain_bank : mi_bank::tables<mi_sidechain_params_t, device_state>     // params: what update_settings computed
 {
-    uint32_t                                channels = 0, inputs = 1;
+    uint32_t                                inputs = 1;
     float                                   max_reactivity = 0.0f;
     std::vector<channel_cfg>                cfg;            // the setters' values; flags: nFlags
     std::vector<uint8_t>                    pend;           // P_* of every channel
-    std::vector<mi_sidechain_params_t>      params;         // what update_settings computed
-    mi::dirty_range                         up;             // where params differs from the device table
     bool                                    work = true;    // some channel has flags or pend set
-    mi_sidechain_params_t                  *d_params = nullptr;     // [channels]
-    device_state                           *d_state = nullptr;      // [channels]
     ring_desc                              *d_desc = nullptr;
     float                                  *d_ring = nullptr;       // [channels][ring_stride]
     size_t                                  ring_stride = 0;
@@ -460,7 +457,7 @@ namespace
             const channel_cfg &c = b->cfg[ch];
             b->params[ch].mode = c.mode, b->params[ch].source = c.source, b->params[ch].flags = c.flags & MI_SCF_MIDSIDE, b->params[ch].gain = c.gain;
         }
-        return mi::upload_dirty("mi_sidechain_bank", b->d_params, b->params.data(), b->up, st);
+        return mi_bank::upload(*b, "mi_sidechain_bank", st);
     }
 
     int sc_launch(mi_sidechain_bank *b, float *out, const float *in0, const float *in1, size_t count, size_t out_stride,
@@ -476,18 +473,36 @@ namespace
         return MI_OK;
     }
 
-    // the checks the three sample entries share
-    int sc_check(const mi_sidechain_bank *b, const char *what, const float *out, const float *in0, const float *in1, size_t count,
+    // the checks the three sample entries share: in0 may be missing (silence); in1 counts only beside it in a bank of two inputs
+    int sc_check(const mi_sidechain_bank *b, const char *entry, const float *out, const float *in0, const float *in1, size_t count,
                  size_t out_stride, size_t in0_stride, size_t in1_stride, bool two)
     {
-        MI_REQUIRE(out != nullptr, MI_EINVAL, "mi_sidechain_bank_%s: NULL output", what);
-        MI_REQUIRE(!two || in0 == nullptr || in1 != nullptr, MI_EINVAL, "mi_sidechain_bank_%s: a bank of two inputs without the second one", what);
-        MI_REQUIRE(count < (size_t(1) << 31), MI_EINVAL, "mi_sidechain_bank_%s: count %zu too large", what, count);
         const bool second = two && in0 != nullptr;
-        MI_REQUIRE(b->channels == 1 || (out_stride >= count && (in0 == nullptr || in0_stride >= count) && (!second || in1_stride >= count)),
-                   MI_EINVAL, "mi_sidechain_bank_%s: strides (%zu, %zu, %zu) shorter than count %zu", what, out_stride, in0_stride, in1_stride, count);
-        MI_REQUIRE((out != in0 || out_stride == in0_stride) && (!second || out != in1 || out_stride == in1_stride), MI_EINVAL,
-                   "mi_sidechain_bank_%s: in place with different strides", what);
+        const int r = mi_bank::check_rows(entry, b->channels, count, size_t(1) << 31,
+                                          { { out, out_stride, count, mi_bank::REQUIRED | mi_bank::OUTPUT }, { in0, in0_stride, count, 0 },
+                                            { second ? in1 : nullptr, in1_stride, count, 0 } });
+        if (r != MI_OK)
+            return r;
+        MI_REQUIRE(!second || in1 != nullptr, MI_EINVAL, "%s: a bank of two inputs without the second one", entry);
+        return MI_OK;
+    }
+} // namespace
+
+namespace
+{
+    // what create() does to the new, empty bank
+    int sc_init(mi_sidechain_bank *b, uint32_t channels, uint32_t inputs, float max_reactivity_ms)
+    {
+        b->channels = channels, b->inputs = inputs, b->max_reactivity = max_reactivity_ms;
+        b->cfg.assign(channels, channel_cfg{ 0, 0.0f, MI_SCM_RMS, MI_SCS_MIDDLE, MI_SCF_UPDATE | MI_SCF_CLEAR, 1.0f });
+        b->pend.assign(channels, P_RING);                           // a ring for the sample rate 0 until one is set
+        b->up.lo = 0, b->up.hi = channels;
+        const int r = mi_bank::alloc(*b, "mi_sidechain_bank_create", fresh_params(), device_state{});
+        if (r != MI_OK)
+            return r;
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_desc), sizeof(ring_desc));
+        if (e == hipSuccess) e = hipMemset(b->d_desc, 0, sizeof(ring_desc));
+        MI_REQUIRE(e == hipSuccess, MI_EHIP, "mi_sidechain_bank_create: %s", hipGetErrorString(e));
         return MI_OK;
     }
 } // namespace
@@ -547,40 +562,29 @@ int mi_sidechain_compute_params(uint32_t sample_rate, float max_reactivity, floa
 
 int mi_sidechain_bank_create(mi_sidechain_bank_t **bank, uint32_t channels, uint32_t inputs, float max_reactivity_ms)     // :67-86
 {
-    MI_REQUIRE(bank != nullptr, MI_EINVAL, "mi_sidechain_bank_create: NULL result pointer");
-    *bank = nullptr;
-    MI_REQUIRE(channels > 0 && channels <= (1u << 20), MI_EINVAL, "mi_sidechain_bank_create: channels must be 1 .. 1048576");
+    int r = mi_bank::open_checks(bank, "mi_sidechain_bank_create", channels);
+    if (r != MI_OK)
+        return r;
     MI_REQUIRE(inputs == 1 || inputs == 2, MI_EINVAL, "mi_sidechain_bank_create: %u inputs (1 or 2)", inputs);
     MI_REQUIRE(max_reactivity_ms >= 0.0f && max_reactivity_ms <= 1e6f, MI_EINVAL, "mi_sidechain_bank_create: maximum reactivity %g ms", double(max_reactivity_ms));
-    MI_REQUIRE(mi_dspu_device_count() > 0, MI_ENODEV, "no HIP device available (there is no CPU fallback)");
-    mi_sidechain_bank *b = new (std::nothrow) mi_sidechain_bank();
-    MI_REQUIRE(b != nullptr, MI_ENOMEM, "mi_sidechain_bank_create: out of host memory");
-    b->channels = channels, b->inputs = inputs, b->max_reactivity = max_reactivity_ms;
-    b->cfg.assign(channels, channel_cfg{ 0, 0.0f, MI_SCM_RMS, MI_SCS_MIDDLE, MI_SCF_UPDATE | MI_SCF_CLEAR, 1.0f });
-    b->pend.assign(channels, P_RING);                           // a ring for the sample rate 0 until one is set
-    b->params.assign(channels, fresh_params());
-    b->up.lo = 0, b->up.hi = channels;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_params), size_t(channels) * sizeof(mi_sidechain_params_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_state), size_t(channels) * sizeof(device_state));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_desc), sizeof(ring_desc));
-    if (e == hipSuccess) e = hipMemset(b->d_state, 0, size_t(channels) * sizeof(device_state));
-    if (e == hipSuccess) e = hipMemset(b->d_desc, 0, sizeof(ring_desc));
-    if (e != hipSuccess)
+    r = mi_bank::open_new(bank, "mi_sidechain_bank_create");
+    if (r != MI_OK)
+        return r;
+    r = sc_init(*bank, channels, inputs, max_reactivity_ms);
+    if (r != MI_OK)
     {
-        mi_sidechain_bank_destroy(b);
-        return mi::fail(MI_EHIP, "mi_sidechain_bank_create: %s", hipGetErrorString(e));
+        mi_sidechain_bank_destroy(*bank);
+        *bank = nullptr;
     }
-    *bank = b;
-    return MI_OK;
+    return r;
 }
 
 int mi_sidechain_bank_destroy(mi_sidechain_bank_t *b)
 {
     if (b == nullptr)
         return MI_OK;
-    (void)hipFree(b->d_params); (void)hipFree(b->d_state); (void)hipFree(b->d_desc); (void)hipFree(b->d_ring);
-    delete b;
-    return MI_OK;
+    (void)hipFree(b->d_desc); (void)hipFree(b->d_ring);
+    return mi_bank::destroy(b);
 }
 
 int mi_sidechain_bank_set_sample_rate(mi_sidechain_bank_t *b, uint32_t channel, uint32_t sample_rate)     // :88-93
@@ -672,10 +676,10 @@ int mi_sidechain_bank_update_settings(mi_sidechain_bank_t *b, void *stream)     
 
 int mi_sidechain_bank_get_params(const mi_sidechain_bank_t *b, uint32_t channel, mi_sidechain_params_t *params)
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_sidechain_bank_get_params: NULL bank");
-    MI_REQUIRE(channel < b->channels && params != nullptr, MI_EINVAL, "mi_sidechain_bank_get_params: bad argument");
+    const int r = mi_bank::get_params(b, "mi_sidechain_bank_get_params", channel, params);
+    if (r != MI_OK)
+        return r;
     const channel_cfg &c = b->cfg[channel];
-    *params = b->params[channel];
     params->mode = c.mode, params->source = c.source, params->flags = c.flags, params->gain = c.gain;
     return MI_OK;
 }
@@ -683,10 +687,8 @@ int mi_sidechain_bank_get_params(const mi_sidechain_bank_t *b, uint32_t channel,
 int mi_sidechain_bank_get_state(mi_sidechain_bank_t *b, uint32_t channel, float *rms_value, uint32_t *refresh, uint32_t *position,
                                 void *stream)
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_sidechain_bank_get_state: NULL bank");
-    MI_REQUIRE(channel < b->channels, MI_EINVAL, "mi_sidechain_bank_get_state: channel %u out of range", channel);
     device_state s;
-    const int r = mi::read_state(&s, b->d_state + channel, mi::as_stream(stream));
+    const int r = mi_bank::get_state(b, "mi_sidechain_bank_get_state", channel, &s, stream);
     if (r != MI_OK)
         return r;
     if (rms_value != nullptr) *rms_value = s.rms;
@@ -704,7 +706,7 @@ int mi_sidechain_bank_process(mi_sidechain_bank_t *b, float *out, const float *i
     if (r != MI_OK || count == 0)
         return r;
     const bool two = b->inputs == 2;
-    const int k = sc_check(b, "process", out, in0, in1, count, out_stride, in0_stride, in1_stride, two);
+    const int k = sc_check(b, "mi_sidechain_bank_process", out, in0, in1, count, out_stride, in0_stride, in1_stride, two);
     if (k != MI_OK)
         return k;
     return sc_launch(b, out, in0, (two && in0 != nullptr) ? in1 : nullptr, count, out_stride, in0_stride, in1_stride, two, st);
@@ -719,7 +721,7 @@ int mi_sidechain_bank_premix(mi_sidechain_bank_t *b, float *out, const float *in
     if (r != MI_OK || count == 0)
         return r;
     const bool two = b->inputs == 2;
-    const int k = sc_check(b, "premix", out, in0, in1, count, out_stride, in0_stride, in1_stride, two);
+    const int k = sc_check(b, "mi_sidechain_bank_premix", out, in0, in1, count, out_stride, in0_stride, in1_stride, two);
     if (k != MI_OK)
         return k;
     MI_REQUIRE(b->channels <= 65535u, MI_EINVAL, "mi_sidechain_bank_premix: more than 65535 channels");
@@ -740,7 +742,7 @@ int mi_sidechain_bank_process_premixed(mi_sidechain_bank_t *b, float *out, const
     const int r = sc_update(b, st);
     if (r != MI_OK || count == 0)
         return r;
-    const int k = sc_check(b, "process_premixed", out, in, nullptr, count, out_stride, in_stride, 0, false);
+    const int k = sc_check(b, "mi_sidechain_bank_process_premixed", out, in, nullptr, count, out_stride, in_stride, 0, false);
     if (k != MI_OK)
         return k;
     return sc_launch(b, out, in, nullptr, count, out_stride, in_stride, 0, false, st);

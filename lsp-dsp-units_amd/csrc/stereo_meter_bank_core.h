@@ -1,13 +1,11 @@
 // What the banks of correlometer.hip and panometer.hip share on the host: the setters' rules, update_settings(), the checks of
 // process() and the device tables.  Both banks keep, per channel, two rings of the bank's capacity, the sums, nHead and
 // nWindow on the device (no host positions: calls replay from a captured graph) and period, capacity, norm, law and default
-// in a device table uploaded by dirty range.  A setter only notes what the reference's setter does to the state; it reaches
-// the device at update_settings(), outside the hot path and never inside a capture.
+// in a device table uploaded by dirty range (the tables of bank_core.h).  A setter only notes what the reference's setter does
+// to the state; it reaches the device at update_settings(), outside the hot path and never inside a capture.
 #pragma once
+#include "bank_core.h"
 #include "stereo_meter_device.h"
-
-#include <new>
-#include <vector>
 
 namespace mi_stereo_meter
 {
@@ -21,56 +19,64 @@ namespace mi_stereo_meter
         uint8_t  pend = 0;
     };
 
-    struct bank_core
+    struct bank_core : mi_bank::tables<meter_params, meter_state>
     {
         const char                 *name = "";              // in messages
-        uint32_t                    channels = 0, max_period = 0, capacity = 0;
+        uint32_t                    max_period = 0, capacity = 0;
         uint32_t                    unset = 0;              // channels whose period is still 0
         std::vector<channel_cfg>    cfg;
-        std::vector<meter_params>   params;                 // what the device table holds, or will after the upload
-        mi::dirty_range             up;
         bool                        work = false;           // some channel has something pending
-        meter_params               *d_params = nullptr;     // [channels]
-        meter_state                *d_state = nullptr;      // [channels]
         float                      *d_rings = nullptr;      // [channels][2][ring_stride]
         size_t                      ring_stride = 0;
     };
 
-    inline void core_destroy(bank_core &b)
+    template <class Bank> int core_destroy(Bank *b)
     {
-        (void)hipFree(b.d_params); (void)hipFree(b.d_state); (void)hipFree(b.d_rings);
-        b.d_params = nullptr, b.d_state = nullptr, b.d_rings = nullptr;
+        if (b != nullptr)
+            (void)hipFree(b->d_rings);
+        return mi_bank::destroy(b);
     }
 
-    // init(max_period) of every channel: period 0, nHead 0, the sums and the rings zero
-    inline int core_create(bank_core &b, const char *name, uint32_t channels, uint32_t max_period)
+    // init(max_period) of every channel of a new, empty bank: period 0, nHead 0, the sums and the rings zero
+    inline int core_init(bank_core &b, const char *entry, const char *name, uint32_t channels, uint32_t max_period)
     {
-        MI_REQUIRE(channels > 0 && channels <= (1u << 20), MI_EINVAL, "%s_create: channels must be 1 .. 1048576", name);
-        MI_REQUIRE(max_period > 0 && max_period <= MAX_PERIOD, MI_EINVAL, "%s_create: a longest period of %u samples (1 .. %u)", name,
-                   max_period, MAX_PERIOD);
-        MI_REQUIRE(mi_dspu_device_count() > 0, MI_ENODEV, "no HIP device available (there is no CPU fallback)");
         b.name = name, b.channels = channels, b.max_period = max_period, b.capacity = ring_capacity(max_period);
         b.ring_stride = b.capacity;
-        MI_REQUIRE(b.ring_stride * 2 * channels < (size_t(1) << 33), MI_ENOMEM, "%s_create: %u pairs of rings of %u samples are too much",
-                   name, channels, b.capacity);
+        MI_REQUIRE(b.ring_stride * 2 * channels < (size_t(1) << 33), MI_ENOMEM, "%s: %u pairs of rings of %u samples are too much",
+                   entry, channels, b.capacity);
         b.unset = channels;
         b.cfg.assign(channels, channel_cfg());
         meter_params p = {};
         p.period = 0, p.capacity = b.capacity, p.norm = 0.0f, p.law = 1, p.dflt = 0.5f;
-        b.params.assign(channels, p);
         b.up.lo = 0, b.up.hi = channels;
+        const int r = mi_bank::alloc(b, entry, p, meter_state{});
+        if (r != MI_OK)
+            return r;
         const size_t ring_bytes = b.ring_stride * 2 * channels * sizeof(float);
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&b.d_params), size_t(channels) * sizeof(meter_params));
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b.d_state), size_t(channels) * sizeof(meter_state));
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b.d_rings), ring_bytes);
-        if (e == hipSuccess) e = hipMemset(b.d_state, 0, size_t(channels) * sizeof(meter_state));
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&b.d_rings), ring_bytes);
         if (e == hipSuccess) e = hipMemset(b.d_rings, 0, ring_bytes);
-        if (e != hipSuccess)
-        {
-            core_destroy(b);
-            return mi::fail(MI_EHIP, "%s_create: %s", name, hipGetErrorString(e));
-        }
+        MI_REQUIRE(e == hipSuccess, MI_EHIP, "%s: %s", entry, hipGetErrorString(e));
         return MI_OK;
+    }
+
+    // create(): the bank, and its channels as init(max_period) leaves them
+    template <class Bank> int core_create(Bank **bank, const char *entry, const char *name, uint32_t channels, uint32_t max_period)
+    {
+        int r = mi_bank::open_checks(bank, entry, channels);
+        if (r != MI_OK)
+            return r;
+        MI_REQUIRE(max_period > 0 && max_period <= MAX_PERIOD, MI_EINVAL, "%s: a longest period of %u samples (1 .. %u)", entry,
+                   max_period, MAX_PERIOD);
+        r = mi_bank::open_new(bank, entry);
+        if (r != MI_OK)
+            return r;
+        r = core_init(**bank, entry, name, channels, max_period);
+        if (r != MI_OK)
+        {
+            core_destroy(*bank);
+            *bank = nullptr;
+        }
+        return r;
     }
 
     // set_period(): clamped, an unchanged value ignored.  pend: what a change leaves to do (P_WINDOW for the Correlometer's
@@ -145,7 +151,7 @@ namespace mi_stereo_meter
             meter_params &p = b.params[ch];
             p.period = c.period, p.capacity = b.capacity, p.norm = c.norm, p.law = c.law, p.dflt = c.dflt;
         }
-        return mi::upload_dirty(b.name, b.d_params, b.params.data(), b.up, st);
+        return mi_bank::upload(b, b.name, st);
     }
 
     // the state of one channel as given: nHead inside the ring, nWindow at most the period
@@ -165,19 +171,18 @@ namespace mi_stereo_meter
     }
 
     // what process() checks once the settings are on the device and count > 0; vec: where 16-byte accesses are allowed
-    inline int core_check(const bank_core &b, const float *out, const float *a, const float *in_b, size_t count, size_t out_stride,
-                          size_t a_stride, size_t b_stride, uint32_t *vec)
+    inline int core_check(const bank_core &b, const char *entry, const float *out, const float *a, const float *in_b, size_t count,
+                          size_t out_stride, size_t a_stride, size_t b_stride, uint32_t *vec)
     {
         if (b.unset > 0)
             for (uint32_t ch = 0; ch < b.channels; ++ch)
-                MI_REQUIRE(b.cfg[ch].period > 0, MI_ESTATE, "%s_process: channel %u has no period yet (the reference's process() never "
-                                                            "ends with a period of 0); call set_period() first", b.name, ch);
-        MI_REQUIRE(out != nullptr && a != nullptr && in_b != nullptr, MI_EINVAL, "%s_process: NULL output or input", b.name);
-        MI_REQUIRE(count < (size_t(1) << 31), MI_EINVAL, "%s_process: count %zu too large", b.name, count);
-        MI_REQUIRE(b.channels == 1 || (out_stride >= count && a_stride >= count && b_stride >= count), MI_EINVAL,
-                   "%s_process: strides (%zu, %zu, %zu) shorter than count %zu", b.name, out_stride, a_stride, b_stride, count);
-        MI_REQUIRE((out != a || out_stride == a_stride) && (out != in_b || out_stride == b_stride), MI_EINVAL,
-                   "%s_process: in place with different strides", b.name);
+                MI_REQUIRE(b.cfg[ch].period > 0, MI_ESTATE, "%s: channel %u has no period yet (the reference's process() never "
+                                                            "ends with a period of 0); call set_period() first", entry, ch);
+        const int r = mi_bank::check_rows(entry, b.channels, count, size_t(1) << 31,
+                                          { { out, out_stride, count, mi_bank::REQUIRED | mi_bank::OUTPUT },
+                                            { a, a_stride, count, mi_bank::REQUIRED }, { in_b, b_stride, count, mi_bank::REQUIRED } });
+        if (r != MI_OK)
+            return r;
         *vec = (mi::aligned16(out, out_stride, b.channels) ? VEC_OUT : 0) | (mi::aligned16(a, a_stride, b.channels) ? VEC_A : 0) |
                (mi::aligned16(in_b, b_stride, b.channels) ? VEC_B : 0);
         return MI_OK;

@@ -10,6 +10,7 @@
 // process_max: the reference's (:238-272) returns 0.0f and looks at only `to_process` of the N * to_process oversampled
 // values.  Here it is what the header documents: the largest value process() would have written, with the state
 // advanced exactly as process() advances it.
+#include "bank_core.h"
 #include "lanczos_device.h"
 
 #include <new>
@@ -280,12 +281,11 @@ int mi_truepeak_coefficients(uint32_t times, float *h, size_t *count)
 
 int mi_truepeak_bank_create(mi_truepeak_bank_t **bank, uint32_t channels)            // TruePeakMeter.cpp:37-82
 {
-    MI_REQUIRE(bank != nullptr, MI_EINVAL, "mi_truepeak_bank_create: NULL result pointer");
+    const int r = mi_bank::open(bank, "mi_truepeak_bank_create", channels, 65535u);
+    if (r != MI_OK)
+        return r;
+    mi_truepeak_bank *b = *bank;
     *bank = nullptr;
-    MI_REQUIRE(channels > 0 && channels <= 65535u, MI_EINVAL, "mi_truepeak_bank_create: channels must be 1 .. 65535");
-    MI_REQUIRE(mi_dspu_device_count() > 0, MI_ENODEV, "no HIP device available (there is no CPU fallback)");
-    mi_truepeak_bank *b = new (std::nothrow) mi_truepeak_bank();
-    MI_REQUIRE(b != nullptr, MI_ENOMEM, "mi_truepeak_bank_create: out of host memory");
     b->channels = channels;
     f32x2 table[TABLE_PAIRS];
     for (int n : FACTORS)
@@ -358,11 +358,11 @@ int mi_truepeak_bank_process(mi_truepeak_bank_t *b, float *dst, const float *src
     const int r = tp_update(b, st);
     if (r != MI_OK || count == 0)
         return r;
-    MI_REQUIRE(dst != nullptr && src != nullptr, MI_EINVAL, "mi_truepeak_bank_process: NULL buffer");
-    MI_REQUIRE(count < (size_t(1) << 31), MI_EINVAL, "mi_truepeak_bank_process: count %zu too large", count);
-    MI_REQUIRE(b->channels == 1 || (dst_stride >= count && src_stride >= count), MI_EINVAL,
-               "mi_truepeak_bank_process: strides (%zu, %zu) shorter than count %zu", dst_stride, src_stride, count);
-    MI_REQUIRE(dst != src || dst_stride == src_stride, MI_EINVAL, "mi_truepeak_bank_process: in place with different strides");
+    const int k = mi_bank::check_rows("mi_truepeak_bank_process", b->channels, count, size_t(1) << 31,
+                                      { { dst, dst_stride, count, mi_bank::REQUIRED | mi_bank::OUTPUT },
+                                        { src, src_stride, count, mi_bank::REQUIRED } });
+    if (k != MI_OK)
+        return k;
     return tp_launch<false>(b, dst, src, uint32_t(count), dst_stride, src_stride, nullptr, st);
 }
 
@@ -380,10 +380,10 @@ int mi_truepeak_bank_process_max(mi_truepeak_bank_t *b, float *peaks, const floa
         MI_HIP_CHECK(hipMemsetAsync(peaks, 0, size_t(b->channels) * sizeof(float), st));
         return MI_OK;
     }
-    MI_REQUIRE(src != nullptr, MI_EINVAL, "mi_truepeak_bank_process_max: NULL input");
-    MI_REQUIRE(count < (size_t(1) << 31), MI_EINVAL, "mi_truepeak_bank_process_max: count %zu too large", count);
-    MI_REQUIRE(b->channels == 1 || src_stride >= count, MI_EINVAL,
-               "mi_truepeak_bank_process_max: stride %zu shorter than count %zu", src_stride, count);
+    const int k = mi_bank::check_rows("mi_truepeak_bank_process_max", b->channels, count, size_t(1) << 31,
+                                      { { src, src_stride, count, mi_bank::REQUIRED } });
+    if (k != MI_OK)
+        return k;
     return tp_launch<true>(b, nullptr, src, uint32_t(count), 0, src_stride, peaks, st);
 }
 
