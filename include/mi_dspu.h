@@ -1472,6 +1472,89 @@ int mi_panometer_bank_set_state(mi_panometer_bank_t *bank, uint32_t channel, con
 int mi_panometer_bank_process(mi_panometer_bank_t *bank, float *out, const float *a, const float *b, size_t count,
                               size_t out_stride, size_t a_stride, size_t b_stride, void *stream);
 
+/* ---- peak hold/decay meter and surge protector banks ---------------------------------------------------------------------- */
+/*
+ * mi_peakmeter_bank: `channels` x lsp::dspu::PeakMeter (meters/PeakMeter.h, src/main/meters/PeakMeter.cpp), every channel with
+ * settings of its own.  Per sample, with s = |x|: s >= peak: peak = s and the hold counter restarts; otherwise the counter runs
+ * down; otherwise peak *= tau.  fPeak and nCounter live on the device: calls can be captured into a graph and replayed.  The
+ * peak is the reference's bit for bit in float32; NaN and Inf samples behave as there; subnormals are kept.  A fresh meter has a
+ * release of 0 and with it tau = expf(-inf) = 0: the peak drops to 0 once the hold has run out.  Rows: [channels][stride].
+ */
+typedef struct mi_peakmeter_bank mi_peakmeter_bank_t;
+/* fTau, nHold; factor = expf(logf(fTau) * float(count)), formed on the host for the `count` of the last process_value() */
+typedef struct { float tau; uint32_t hold; float factor; uint32_t count; } mi_peakmeter_params_t;
+typedef struct { float peak; uint32_t counter; } mi_peakmeter_state_t;                     /* fPeak, nCounter */
+/* update_settings() of one meter without a bank or a device (times in milliseconds): fTau and nHold in host float32 with the C
+ * library's expf and logf, as the reference forms them; the factor is that of count 0.  MI_EINVAL where nHold is undefined (below). */
+int mi_peakmeter_compute_params(uint32_t sample_rate, float hold, float release, mi_peakmeter_params_t *params);
+int mi_peakmeter_bank_create(mi_peakmeter_bank_t **bank, uint32_t channels);               /* construct(): hold 5 ms, release 0 */
+int mi_peakmeter_bank_destroy(mi_peakmeter_bank_t *bank);
+/* The setters (times in milliseconds); an unchanged value is ignored.  nHold = uint32_t(millis_to_samples(rate, hold)) is
+ * undefined in the reference for a product that is negative, NaN or at least 2^32: a setter that would leave such a pair of rate
+ * and hold time is MI_EINVAL and changes nothing. */
+int mi_peakmeter_bank_set_sample_rate(mi_peakmeter_bank_t *bank, uint32_t channel, uint32_t sample_rate);
+int mi_peakmeter_bank_set_hold_time(mi_peakmeter_bank_t *bank, uint32_t channel, float hold);
+int mi_peakmeter_bank_set_release_time(mi_peakmeter_bank_t *bank, uint32_t channel, float release);
+int mi_peakmeter_bank_set_time(mi_peakmeter_bank_t *bank, uint32_t channel, float hold, float release);
+/* clear() of one channel, or of every channel (channel = UINT32_MAX): fPeak = 0, nCounter = 0, before the next launch */
+int mi_peakmeter_bank_clear(mi_peakmeter_bank_t *bank, uint32_t channel);
+/* What the setters and clear() left goes to the device (and the call waits for it).  Every process entry runs it first.  On a
+ * stream being captured pending work is refused (MI_ESTATE): call it before the capture. */
+int mi_peakmeter_bank_update_settings(mi_peakmeter_bank_t *bank, void *stream);
+/* fTau and nHold as update_settings() computes them (HOST memory); set_params() sets the two as given (factor and count of
+ * *params are not looked at).  The state as the work enqueued on `stream` leaves it, after what is pending (HOST memory; waits
+ * for the stream; not on a stream being captured: MI_ESTATE).  A counter above the hold is taken down to it by the next launch,
+ * as update_settings() does in the reference. */
+int mi_peakmeter_bank_get_params(const mi_peakmeter_bank_t *bank, uint32_t channel, mi_peakmeter_params_t *params);
+int mi_peakmeter_bank_set_params(mi_peakmeter_bank_t *bank, uint32_t channel, const mi_peakmeter_params_t *params);
+int mi_peakmeter_bank_get_state(mi_peakmeter_bank_t *bank, uint32_t channel, mi_peakmeter_state_t *state, void *stream);
+int mi_peakmeter_bank_set_state(mi_peakmeter_bank_t *bank, uint32_t channel, const mi_peakmeter_state_t *state, void *stream);
+/* process(dst, src, count) and process(src, count): dst NULL updates the state only; dst may be src (same stride).  peaks: NULL,
+ * or a DEVICE array of `channels` floats that receives every channel's return value, the peak after the last sample. */
+int mi_peakmeter_bank_process(mi_peakmeter_bank_t *bank, float *dst, const float *src, float *peaks, size_t count,
+                              size_t dst_stride, size_t src_stride, void *stream);
+/* process(value, count), one block-rate step of every channel: values is a DEVICE array of `channels` floats, peaks as above.
+ * The decay factor expf(logf(fTau) * float(count)) is formed on the host, with the libm the reference uses, and kept in the
+ * parameter table: a call whose count differs from the last one's uploads it, and is refused inside a stream capture like a
+ * setter (MI_ESTATE).  count is at most UINT32_MAX. */
+int mi_peakmeter_bank_process_value(mi_peakmeter_bank_t *bank, float *peaks, const float *values, size_t count, void *stream);
+
+/*
+ * mi_surge_bank: `channels` x lsp::dspu::SurgeProtector (dynamics/SurgeProtector.h, src/main/dynamics/SurgeProtector.cpp): a gain
+ * that fades in (square root of a linear ramp over transition_max samples) once the level row reaches on_threshold, and out
+ * once it stayed below off_threshold for shutdown_max samples.  The compares are >=, so a NaN level never passes.  fGain, both
+ * counters and the flag live on the device; the gain is the reference's bit for bit.  The reference's counters are size_t, the
+ * bank's are 32 bits wide.  Rows: [channels][stride].
+ */
+typedef struct mi_surge_bank mi_surge_bank_t;
+typedef struct { uint32_t transition_max, shutdown_max; float on_threshold, off_threshold; } mi_surge_params_t;
+typedef struct { float gain; uint32_t transition_time, shutdown_time, on; } mi_surge_state_t;   /* fGain, nTransitionTime, nShutdownTime, bOn */
+int mi_surge_bank_create(mi_surge_bank_t **bank, uint32_t channels);                       /* construct(): everything 0 */
+int mi_surge_bank_destroy(mi_surge_bank_t *bank);
+/* The setters (times in samples).  set_transition_time and set_shutdown_time clamp the live counter at once in the reference,
+ * and reset() clears bOn and nTransitionTime: the bank records these in call order and applies them to the device state before
+ * the next launch or state access, so set_transition_time(5) followed by (100) leaves a counter of at most 5.  reset() takes a
+ * channel, or UINT32_MAX for all. */
+int mi_surge_bank_set_transition_time(mi_surge_bank_t *bank, uint32_t channel, uint32_t samples);
+int mi_surge_bank_set_shutdown_time(mi_surge_bank_t *bank, uint32_t channel, uint32_t samples);
+int mi_surge_bank_set_on_threshold(mi_surge_bank_t *bank, uint32_t channel, float threshold);
+int mi_surge_bank_set_off_threshold(mi_surge_bank_t *bank, uint32_t channel, float threshold);
+int mi_surge_bank_set_threshold(mi_surge_bank_t *bank, uint32_t channel, float on, float off);
+int mi_surge_bank_reset(mi_surge_bank_t *bank, uint32_t channel);
+/* The settings as set (HOST memory).  The state after what is recorded and enqueued (HOST memory; waits for the stream; not on
+ * a stream being captured: MI_ESTATE).  set_state refuses a transition counter above transition_max, a shutdown counter above
+ * shutdown_max and a flag above 1 (MI_EINVAL).  There is no update_settings(): a process call (one of count 0 will do) sends
+ * what the setters left, and inside a stream capture refuses to (MI_ESTATE); get_state() before the capture sends it too. */
+int mi_surge_bank_get_params(const mi_surge_bank_t *bank, uint32_t channel, mi_surge_params_t *params);
+int mi_surge_bank_get_state(mi_surge_bank_t *bank, uint32_t channel, mi_surge_state_t *state, void *stream);
+int mi_surge_bank_set_state(mi_surge_bank_t *bank, uint32_t channel, const mi_surge_state_t *state, void *stream);
+/* process(out, in, count): the gain into out; out NULL (process(in, count)) moves the state only; out may be in (same stride).
+ * process_mul: out[i] *= gain, out read and written; out may be in. */
+int mi_surge_bank_process(mi_surge_bank_t *bank, float *out, const float *in, size_t count, size_t out_stride, size_t in_stride,
+                          void *stream);
+int mi_surge_bank_process_mul(mi_surge_bank_t *bank, float *out, const float *in, size_t count, size_t out_stride,
+                              size_t in_stride, void *stream);
+
 /*
  * mi_splitter_bank: lsp::dspu::SpectralSplitter for `channels` channels sharing the settings
  * (util/SpectralSplitter.h:62-250, src/main/util/SpectralSplitter.cpp:62-361) -- the engine of lsp::dspu::FFTCrossover.

@@ -184,6 +184,26 @@ class PanometerState(ctypes.Structure):
     _fields_ = [("value_a", c_float), ("value_b", c_float), ("head", c_uint32), ("window", c_uint32)]
 
 
+class PeakMeterParams(ctypes.Structure):
+    """mi_peakmeter_params_t: fTau, nHold, and the decay factor of process_value() for `count` samples."""
+    _fields_ = [("tau", c_float), ("hold", c_uint32), ("factor", c_float), ("count", c_uint32)]
+
+
+class PeakMeterState(ctypes.Structure):
+    """mi_peakmeter_state_t: fPeak, nCounter."""
+    _fields_ = [("peak", c_float), ("counter", c_uint32)]
+
+
+class SurgeParams(ctypes.Structure):
+    """mi_surge_params_t: nTransitionMax, nShutdownMax, fOnThreshold, fOffThreshold."""
+    _fields_ = [("transition_max", c_uint32), ("shutdown_max", c_uint32), ("on_threshold", c_float), ("off_threshold", c_float)]
+
+
+class SurgeState(ctypes.Structure):
+    """mi_surge_state_t: fGain, nTransitionTime, nShutdownTime, bOn."""
+    _fields_ = [("gain", c_float), ("transition_time", c_uint32), ("shutdown_time", c_uint32), ("on", c_uint32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/mi_dspu.h must be listed here
 # (tests/test_abi.py parses the header and checks both directions).
 PROTOTYPES = {
@@ -530,6 +550,34 @@ PROTOTYPES = {
     "mi_panometer_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(PanometerState), c_void_p]),
     "mi_panometer_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(PanometerState), c_uint32, c_void_p]),
     "mi_panometer_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_peakmeter_compute_params": (c_int, [c_uint32, c_float, c_float, POINTER(PeakMeterParams)]),
+    "mi_peakmeter_bank_create": (c_int, [POINTER(c_void_p), c_uint32]),
+    "mi_peakmeter_bank_destroy": (c_int, [c_void_p]),
+    "mi_peakmeter_bank_set_sample_rate": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_peakmeter_bank_set_hold_time": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_peakmeter_bank_set_release_time": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_peakmeter_bank_set_time": (c_int, [c_void_p, c_uint32, c_float, c_float]),
+    "mi_peakmeter_bank_clear": (c_int, [c_void_p, c_uint32]),
+    "mi_peakmeter_bank_update_settings": (c_int, [c_void_p, c_void_p]),
+    "mi_peakmeter_bank_get_params": (c_int, [c_void_p, c_uint32, POINTER(PeakMeterParams)]),
+    "mi_peakmeter_bank_set_params": (c_int, [c_void_p, c_uint32, POINTER(PeakMeterParams)]),
+    "mi_peakmeter_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(PeakMeterState), c_void_p]),
+    "mi_peakmeter_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(PeakMeterState), c_void_p]),
+    "mi_peakmeter_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_peakmeter_bank_process_value": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mi_surge_bank_create": (c_int, [POINTER(c_void_p), c_uint32]),
+    "mi_surge_bank_destroy": (c_int, [c_void_p]),
+    "mi_surge_bank_set_transition_time": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_surge_bank_set_shutdown_time": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_surge_bank_set_on_threshold": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_surge_bank_set_off_threshold": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_surge_bank_set_threshold": (c_int, [c_void_p, c_uint32, c_float, c_float]),
+    "mi_surge_bank_reset": (c_int, [c_void_p, c_uint32]),
+    "mi_surge_bank_get_params": (c_int, [c_void_p, c_uint32, POINTER(SurgeParams)]),
+    "mi_surge_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(SurgeState), c_void_p]),
+    "mi_surge_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(SurgeState), c_void_p]),
+    "mi_surge_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_surge_bank_process_mul": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_splitter_bank_create": (c_int, [POINTER(c_void_p), c_uint32, c_uint32, c_uint32]),
     "mi_splitter_bank_destroy": (c_int, [c_void_p]),
     "mi_splitter_bank_set_rank": (c_int, [c_void_p, c_uint32]),

@@ -1726,6 +1726,162 @@ class PanometerBank(_StereoMeterBank):
         check(lib.mi_panometer_bank_set_state(self.handle, channel, byref(s), 1 if zero_rings else 0, _stream(stream)))
 
 
+def _opt(x):
+    return None if x is None else _ptr(x)
+
+
+class PeakMeterBank:
+    """`channels` x lsp::dspu::PeakMeter (mi_peakmeter_bank_*): a peak hold/decay follower per channel, fPeak and nCounter on the
+    device."""
+    ALL = 0xFFFFFFFF
+
+    def __init__(self, channels):
+        h = c_void_p()
+        check(lib.mi_peakmeter_bank_create(byref(h), channels))
+        self.handle, self.channels = h, channels
+
+    def set_sample_rate(self, channel, sample_rate):
+        check(lib.mi_peakmeter_bank_set_sample_rate(self.handle, channel, sample_rate))
+
+    def set_hold_time(self, channel, hold):
+        check(lib.mi_peakmeter_bank_set_hold_time(self.handle, channel, float(hold)))
+
+    def set_release_time(self, channel, release):
+        check(lib.mi_peakmeter_bank_set_release_time(self.handle, channel, float(release)))
+
+    def set_time(self, channel, hold, release):
+        check(lib.mi_peakmeter_bank_set_time(self.handle, channel, float(hold), float(release)))
+
+    def configure(self, channel, sample_rate, hold, release):
+        """Every setter of one channel (times in milliseconds)."""
+        self.set_sample_rate(channel, sample_rate)
+        self.set_time(channel, hold, release)
+
+    def clear(self, channel=ALL):
+        check(lib.mi_peakmeter_bank_clear(self.handle, channel))
+
+    def update_settings(self, stream=None):
+        check(lib.mi_peakmeter_bank_update_settings(self.handle, _stream(stream)))
+
+    def get_params(self, channel):
+        """fTau as numpy float32 and nHold as update_settings() computes them."""
+        from .capi import PeakMeterParams
+        p = PeakMeterParams()
+        check(lib.mi_peakmeter_bank_get_params(self.handle, channel, byref(p)))
+        return {"tau": np.float32(p.tau), "hold": p.hold, "factor": np.float32(p.factor), "count": p.count}
+
+    def set_params(self, channel, tau, hold):
+        from .capi import PeakMeterParams
+        p = PeakMeterParams(float(tau), hold, 0.0, 0)
+        check(lib.mi_peakmeter_bank_set_params(self.handle, channel, byref(p)))
+
+    def get_state(self, channel, stream=None):
+        from .capi import PeakMeterState
+        s = PeakMeterState()
+        check(lib.mi_peakmeter_bank_get_state(self.handle, channel, byref(s), _stream(stream)))
+        return {"peak": np.float32(s.peak), "counter": s.counter}
+
+    def set_state(self, channel, peak, counter, stream=None):
+        from .capi import PeakMeterState
+        s = PeakMeterState(float(peak), counter)
+        check(lib.mi_peakmeter_bank_set_state(self.handle, channel, byref(s), _stream(stream)))
+
+    def process(self, dst, src, count, peaks=None, dst_stride=None, src_stride=None, stream=None):
+        """process(dst, src, count); dst None: the state only; dst may be src.  peaks: a device array of `channels` floats for the
+        peak after the last sample, or None."""
+        check(lib.mi_peakmeter_bank_process(self.handle, _opt(dst), _opt(src), _opt(peaks), count,
+                                            count if dst_stride is None else dst_stride,
+                                            count if src_stride is None else src_stride, _stream(stream)))
+
+    def process_value(self, peaks, values, count, stream=None):
+        """process(value, count) of every channel: values and peaks are device arrays of `channels` floats (peaks may be None)."""
+        check(lib.mi_peakmeter_bank_process_value(self.handle, _opt(peaks), _opt(values), count, _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            lib.mi_peakmeter_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SurgeProtectorBank:
+    """`channels` x lsp::dspu::SurgeProtector (mi_surge_bank_*): a fade-in when the level row appears, a fade-out when it stops."""
+    ALL = 0xFFFFFFFF
+
+    def __init__(self, channels):
+        h = c_void_p()
+        check(lib.mi_surge_bank_create(byref(h), channels))
+        self.handle, self.channels = h, channels
+
+    def set_transition_time(self, channel, samples):
+        check(lib.mi_surge_bank_set_transition_time(self.handle, channel, samples))
+
+    def set_shutdown_time(self, channel, samples):
+        check(lib.mi_surge_bank_set_shutdown_time(self.handle, channel, samples))
+
+    def set_on_threshold(self, channel, threshold):
+        check(lib.mi_surge_bank_set_on_threshold(self.handle, channel, float(threshold)))
+
+    def set_off_threshold(self, channel, threshold):
+        check(lib.mi_surge_bank_set_off_threshold(self.handle, channel, float(threshold)))
+
+    def set_threshold(self, channel, on, off):
+        check(lib.mi_surge_bank_set_threshold(self.handle, channel, float(on), float(off)))
+
+    def configure(self, channel, transition, shutdown, on, off):
+        """Every setter of one channel (times in samples)."""
+        self.set_transition_time(channel, transition)
+        self.set_shutdown_time(channel, shutdown)
+        self.set_threshold(channel, on, off)
+
+    def reset(self, channel=ALL):
+        check(lib.mi_surge_bank_reset(self.handle, channel))
+
+    def get_params(self, channel):
+        from .capi import SurgeParams
+        p = SurgeParams()
+        check(lib.mi_surge_bank_get_params(self.handle, channel, byref(p)))
+        return {"transition_max": p.transition_max, "shutdown_max": p.shutdown_max, "on_threshold": np.float32(p.on_threshold),
+                "off_threshold": np.float32(p.off_threshold)}
+
+    def get_state(self, channel, stream=None):
+        from .capi import SurgeState
+        s = SurgeState()
+        check(lib.mi_surge_bank_get_state(self.handle, channel, byref(s), _stream(stream)))
+        return {"gain": np.float32(s.gain), "transition_time": s.transition_time, "shutdown_time": s.shutdown_time, "on": s.on}
+
+    def set_state(self, channel, gain, transition_time, shutdown_time, on, stream=None):
+        from .capi import SurgeState
+        s = SurgeState(float(gain), transition_time, shutdown_time, int(on))
+        check(lib.mi_surge_bank_set_state(self.handle, channel, byref(s), _stream(stream)))
+
+    def process(self, out, inp, count, out_stride=None, in_stride=None, stream=None):
+        """process(out, in, count): the gain into out; out None: the state only; out may be inp."""
+        check(lib.mi_surge_bank_process(self.handle, _opt(out), _opt(inp), count, count if out_stride is None else out_stride,
+                                        count if in_stride is None else in_stride, _stream(stream)))
+
+    def process_mul(self, out, inp, count, out_stride=None, in_stride=None, stream=None):
+        """process_mul(out, in, count): out *= gain; out may be inp."""
+        check(lib.mi_surge_bank_process_mul(self.handle, _opt(out), _opt(inp), count, count if out_stride is None else out_stride,
+                                            count if in_stride is None else in_stride, _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            lib.mi_surge_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class LoudnessBank:
     """`meters` x lsp::dspu::LoudnessMeter(channels) sharing one configuration (mi_loudness_bank_*)."""
     WEIGHT_NONE, WEIGHT_A, WEIGHT_B, WEIGHT_C, WEIGHT_D, WEIGHT_K = range(6)
