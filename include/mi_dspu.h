@@ -1555,6 +1555,69 @@ int mi_surge_bank_process(mi_surge_bank_t *bank, float *out, const float *in, si
 int mi_surge_bank_process_mul(mi_surge_bank_t *bank, float *out, const float *in, size_t count, size_t out_stride,
                               size_t in_stride, void *stream);
 
+/* ---- bypass and crossfade banks: click-free switching ------------------------------------------------------------------------ */
+/*
+ * mi_bypass_bank: `channels` x lsp::dspu::Bypass (ctl/Bypass.h, src/main/ctl/Bypass.cpp).  The gain runs from 0 (dry) to 1 (wet)
+ * as the running float32 sum fGain += fDelta, one step per sample, and every ramp sample is mixed with the gain before the
+ * step; once the ramp is over the rest of the block is a copy or a scale of the one input that is left.  nState, fDelta and
+ * fGain live on the device and are the reference's bit for bit, as is the output.  The channels of a call may be in different
+ * states.  Rows: [channels][stride].
+ */
+typedef struct mi_bypass_bank mi_bypass_bank_t;
+enum { MI_BYPASS_ON = 0, MI_BYPASS_ACTIVE = 1, MI_BYPASS_OFF = 2 };                        /* Bypass::state_t */
+typedef struct { uint32_t state; float delta; float gain; } mi_bypass_state_t;             /* nState, fDelta, fGain */
+int mi_bypass_bank_create(mi_bypass_bank_t **bank, uint32_t channels);                     /* construct(): S_OFF, 0, 0 */
+int mi_bypass_bank_destroy(mi_bypass_bank_t *bank);
+/* init(sample_rate, time) of a channel, or of all (channel = UINT32_MAX): S_OFF, fDelta = 1 / max(float(sample_rate) * time, 1),
+ * fGain = 1, in host float32.  A NaN time, or a product of 2^32 and more, is MI_EINVAL and changes nothing. */
+int mi_bypass_bank_init(mi_bypass_bank_t *bank, uint32_t channel, int sample_rate, float time);
+/* set_bypass(bypass) of a channel, or of all.  *changed: the reference's return value; for all channels the number of
+ * channels that changed, and changed may then be NULL.  init and set_bypass are recorded in call order and reach the device
+ * state in front of the next launch or state access.  For a channel whose fDelta is finite and not 0 the answer is known on
+ * the host; for any other (never initialised, or set so by set_state) the state is read back on the stream of the bank's
+ * last process or state call: that waits for the stream, and is MI_ESTATE while the stream is being captured. */
+int mi_bypass_bank_set_bypass(mi_bypass_bank_t *bank, uint32_t channel, int bypass, int *changed);
+int mi_bypass_bank_bypassing(mi_bypass_bank_t *bank, uint32_t channel, int *bypassing, void *stream);
+/* The state after what is recorded and enqueued (HOST memory; waits for the stream; not on a stream being captured:
+ * MI_ESTATE).  set_state takes any bits: the kernel's comparisons are the reference's, NaN and 0 included. */
+int mi_bypass_bank_get_state(mi_bypass_bank_t *bank, uint32_t channel, mi_bypass_state_t *state, void *stream);
+int mi_bypass_bank_set_state(mi_bypass_bank_t *bank, uint32_t channel, const mi_bypass_state_t *state, void *stream);
+/* process, process_wet, process_drywet: dry may be NULL; dst may be dry or wet (same stride); the gains are scalars of the
+ * call.  A call with nothing recorded can be captured into a graph and replayed: a replay goes on with the ramp.  What is
+ * recorded is refused inside a capture (MI_ESTATE); count 0 changes nothing. */
+int mi_bypass_bank_process(mi_bypass_bank_t *bank, float *dst, const float *dry, const float *wet, size_t count, size_t dst_stride,
+                           size_t dry_stride, size_t wet_stride, void *stream);
+int mi_bypass_bank_process_wet(mi_bypass_bank_t *bank, float *dst, const float *dry, const float *wet, float wet_gain, size_t count,
+                               size_t dst_stride, size_t dry_stride, size_t wet_stride, void *stream);
+int mi_bypass_bank_process_drywet(mi_bypass_bank_t *bank, float *dst, const float *dry, const float *wet, float dry_gain,
+                                  float wet_gain, size_t count, size_t dst_stride, size_t dry_stride, size_t wet_stride,
+                                  void *stream);
+
+/*
+ * mi_crossfade_bank: `channels` x lsp::dspu::Crossfade (ctl/Crossfade.h, src/main/ctl/Crossfade.cpp): after toggle() the output
+ * goes from fade_out to fade_in over nSamples samples, with the same running sum.  nCounter, fDelta and fGain live on the
+ * device; nSamples and an exact copy of nCounter (every process call takes min(nCounter, count) off it) are kept on the host,
+ * so toggle() and remaining() never wait.  The reference's counters are size_t, the bank's are 32 bits wide.
+ */
+typedef struct mi_crossfade_bank mi_crossfade_bank_t;
+typedef struct { uint32_t counter; float delta; float gain; } mi_crossfade_state_t;        /* nCounter, fDelta, fGain */
+int mi_crossfade_bank_create(mi_crossfade_bank_t **bank, uint32_t channels);               /* construct(): 0, 0, 0, 1 */
+int mi_crossfade_bank_destroy(mi_crossfade_bank_t *bank);
+/* init(sample_rate, time): nSamples = max(ssize_t(float(sample_rate) * time), 1); MI_EINVAL as for the bypass bank */
+int mi_crossfade_bank_init(mi_crossfade_bank_t *bank, uint32_t channel, int sample_rate, float time);
+/* toggle() and reset() of a channel, or of all (UINT32_MAX): recorded, and on the device in front of the next launch or state
+ * access.  *toggled: whether the channel was idle and now fades; for all channels how many do (toggled may then be NULL). */
+int mi_crossfade_bank_toggle(mi_crossfade_bank_t *bank, uint32_t channel, int *toggled);
+int mi_crossfade_bank_reset(mi_crossfade_bank_t *bank, uint32_t channel);
+int mi_crossfade_bank_remaining(const mi_crossfade_bank_t *bank, uint32_t channel, size_t *remaining);
+int mi_crossfade_bank_get_state(mi_crossfade_bank_t *bank, uint32_t channel, mi_crossfade_state_t *state, void *stream);
+int mi_crossfade_bank_set_state(mi_crossfade_bank_t *bank, uint32_t channel, const mi_crossfade_state_t *state, void *stream);
+/* process(dst, fade_out, fade_in, count): either input may be NULL, or both (silence; the fade moves on all the same); dst
+ * may be either input (same stride).  The counters are positions held on the host: capture a call through
+ * mi_dspu_graph_begin_capture / end_capture, which refuse a capture during which a fade ran (a replay would not move them). */
+int mi_crossfade_bank_process(mi_crossfade_bank_t *bank, float *dst, const float *fade_out, const float *fade_in, size_t count,
+                              size_t dst_stride, size_t out_stride, size_t in_stride, void *stream);
+
 /*
  * mi_splitter_bank: lsp::dspu::SpectralSplitter for `channels` channels sharing the settings
  * (util/SpectralSplitter.h:62-250, src/main/util/SpectralSplitter.cpp:62-361) -- the engine of lsp::dspu::FFTCrossover.

@@ -204,6 +204,16 @@ class SurgeState(ctypes.Structure):
     _fields_ = [("gain", c_float), ("transition_time", c_uint32), ("shutdown_time", c_uint32), ("on", c_uint32)]
 
 
+class BypassState(ctypes.Structure):
+    """mi_bypass_state_t: nState (0 on, 1 active, 2 off), fDelta, fGain."""
+    _fields_ = [("state", c_uint32), ("delta", c_float), ("gain", c_float)]
+
+
+class CrossfadeState(ctypes.Structure):
+    """mi_crossfade_state_t: nCounter, fDelta, fGain."""
+    _fields_ = [("counter", c_uint32), ("delta", c_float), ("gain", c_float)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/mi_dspu.h must be listed here
 # (tests/test_abi.py parses the header and checks both directions).
 PROTOTYPES = {
@@ -578,6 +588,25 @@ PROTOTYPES = {
     "mi_surge_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(SurgeState), c_void_p]),
     "mi_surge_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_surge_bank_process_mul": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_bypass_bank_create": (c_int, [POINTER(c_void_p), c_uint32]),
+    "mi_bypass_bank_destroy": (c_int, [c_void_p]),
+    "mi_bypass_bank_init": (c_int, [c_void_p, c_uint32, c_int, c_float]),
+    "mi_bypass_bank_set_bypass": (c_int, [c_void_p, c_uint32, c_int, POINTER(c_int)]),
+    "mi_bypass_bank_bypassing": (c_int, [c_void_p, c_uint32, POINTER(c_int), c_void_p]),
+    "mi_bypass_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(BypassState), c_void_p]),
+    "mi_bypass_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(BypassState), c_void_p]),
+    "mi_bypass_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_bypass_bank_process_wet": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_bypass_bank_process_drywet": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_crossfade_bank_create": (c_int, [POINTER(c_void_p), c_uint32]),
+    "mi_crossfade_bank_destroy": (c_int, [c_void_p]),
+    "mi_crossfade_bank_init": (c_int, [c_void_p, c_uint32, c_int, c_float]),
+    "mi_crossfade_bank_toggle": (c_int, [c_void_p, c_uint32, POINTER(c_int)]),
+    "mi_crossfade_bank_reset": (c_int, [c_void_p, c_uint32]),
+    "mi_crossfade_bank_remaining": (c_int, [c_void_p, c_uint32, POINTER(c_size_t)]),
+    "mi_crossfade_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(CrossfadeState), c_void_p]),
+    "mi_crossfade_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(CrossfadeState), c_void_p]),
+    "mi_crossfade_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_splitter_bank_create": (c_int, [POINTER(c_void_p), c_uint32, c_uint32, c_uint32]),
     "mi_splitter_bank_destroy": (c_int, [c_void_p]),
     "mi_splitter_bank_set_rank": (c_int, [c_void_p, c_uint32]),

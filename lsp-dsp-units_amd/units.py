@@ -1882,6 +1882,134 @@ class SurgeProtectorBank:
             pass
 
 
+def _word_and_floats(struct, word, a, b):
+    """A state struct of one uint32 and two float32 with the floats' bits as given (a NaN keeps its payload)."""
+    return struct.from_buffer_copy(np.uint32(word).tobytes() + np.float32(a).tobytes() + np.float32(b).tobytes())
+
+
+class BypassBank:
+    """`channels` x lsp::dspu::Bypass (mi_bypass_bank_*): a click-free switch between a dry and a wet row, nState, fDelta and
+    fGain on the device."""
+    ALL = 0xFFFFFFFF
+    S_ON, S_ACTIVE, S_OFF = 0, 1, 2
+
+    def __init__(self, channels):
+        h = c_void_p()
+        check(lib.mi_bypass_bank_create(byref(h), channels))
+        self.handle, self.channels = h, channels
+
+    def init(self, channel, sample_rate, time=0.005):
+        check(lib.mi_bypass_bank_init(self.handle, channel, int(sample_rate), float(time)))
+
+    def set_bypass(self, channel, bypass):
+        """set_bypass(bypass): whether the channel changed direction; for ALL, how many did."""
+        n = c_int()
+        check(lib.mi_bypass_bank_set_bypass(self.handle, channel, 1 if bypass else 0, byref(n)))
+        return n.value if channel == self.ALL else bool(n.value)
+
+    def bypassing(self, channel, stream=None):
+        v = c_int()
+        check(lib.mi_bypass_bank_bypassing(self.handle, channel, byref(v), _stream(stream)))
+        return bool(v.value)
+
+    def get_state(self, channel, stream=None):
+        from .capi import BypassState
+        s = BypassState()
+        check(lib.mi_bypass_bank_get_state(self.handle, channel, byref(s), _stream(stream)))
+        return {"state": s.state, "delta": np.frombuffer(bytes(s), np.float32)[1], "gain": np.frombuffer(bytes(s), np.float32)[2]}
+
+    def set_state(self, channel, state, delta, gain, stream=None):
+        from .capi import BypassState
+        s = _word_and_floats(BypassState, state, delta, gain)
+        check(lib.mi_bypass_bank_set_state(self.handle, channel, byref(s), _stream(stream)))
+
+    @staticmethod
+    def _rows(count, dst_stride, dry_stride, wet_stride):
+        """count and the three strides of a process call, each stride `count` where it is not given"""
+        return (count, count if dst_stride is None else dst_stride, count if dry_stride is None else dry_stride,
+                count if wet_stride is None else wet_stride)
+
+    def process(self, dst, dry, wet, count, dst_stride=None, dry_stride=None, wet_stride=None, stream=None):
+        """process(dst, dry, wet, count); dry may be None; dst may be dry or wet."""
+        check(lib.mi_bypass_bank_process(self.handle, _opt(dst), _opt(dry), _opt(wet),
+                                         *self._rows(count, dst_stride, dry_stride, wet_stride), _stream(stream)))
+
+    def process_wet(self, dst, dry, wet, wet_gain, count, dst_stride=None, dry_stride=None, wet_stride=None, stream=None):
+        check(lib.mi_bypass_bank_process_wet(self.handle, _opt(dst), _opt(dry), _opt(wet), float(wet_gain),
+                                             *self._rows(count, dst_stride, dry_stride, wet_stride), _stream(stream)))
+
+    def process_drywet(self, dst, dry, wet, dry_gain, wet_gain, count, dst_stride=None, dry_stride=None, wet_stride=None, stream=None):
+        check(lib.mi_bypass_bank_process_drywet(self.handle, _opt(dst), _opt(dry), _opt(wet), float(dry_gain), float(wet_gain),
+                                                *self._rows(count, dst_stride, dry_stride, wet_stride), _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            lib.mi_bypass_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CrossfadeBank:
+    """`channels` x lsp::dspu::Crossfade (mi_crossfade_bank_*): after toggle() the output goes from fade_out to fade_in."""
+    ALL = 0xFFFFFFFF
+
+    def __init__(self, channels):
+        h = c_void_p()
+        check(lib.mi_crossfade_bank_create(byref(h), channels))
+        self.handle, self.channels = h, channels
+
+    def init(self, channel, sample_rate, time=0.005):
+        check(lib.mi_crossfade_bank_init(self.handle, channel, int(sample_rate), float(time)))
+
+    def toggle(self, channel):
+        """toggle(): whether a fade started; for ALL, on how many channels."""
+        n = c_int()
+        check(lib.mi_crossfade_bank_toggle(self.handle, channel, byref(n)))
+        return n.value if channel == self.ALL else bool(n.value)
+
+    def reset(self, channel=ALL):
+        check(lib.mi_crossfade_bank_reset(self.handle, channel))
+
+    def remaining(self, channel):
+        from ctypes import c_size_t
+        v = c_size_t()
+        check(lib.mi_crossfade_bank_remaining(self.handle, channel, byref(v)))
+        return v.value
+
+    def get_state(self, channel, stream=None):
+        from .capi import CrossfadeState
+        s = CrossfadeState()
+        check(lib.mi_crossfade_bank_get_state(self.handle, channel, byref(s), _stream(stream)))
+        return {"counter": s.counter, "delta": np.frombuffer(bytes(s), np.float32)[1], "gain": np.frombuffer(bytes(s), np.float32)[2]}
+
+    def set_state(self, channel, counter, delta, gain, stream=None):
+        from .capi import CrossfadeState
+        s = _word_and_floats(CrossfadeState, counter, delta, gain)
+        check(lib.mi_crossfade_bank_set_state(self.handle, channel, byref(s), _stream(stream)))
+
+    def process(self, dst, fade_out, fade_in, count, dst_stride=None, out_stride=None, in_stride=None, stream=None):
+        """process(dst, fade_out, fade_in, count); either input may be None, or both; dst may be either input."""
+        check(lib.mi_crossfade_bank_process(self.handle, _opt(dst), _opt(fade_out), _opt(fade_in), count,
+                                            count if dst_stride is None else dst_stride, count if out_stride is None else out_stride,
+                                            count if in_stride is None else in_stride, _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            lib.mi_crossfade_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class LoudnessBank:
     """`meters` x lsp::dspu::LoudnessMeter(channels) sharing one configuration (mi_loudness_bank_*)."""
     WEIGHT_NONE, WEIGHT_A, WEIGHT_B, WEIGHT_C, WEIGHT_D, WEIGHT_K = range(6)
