@@ -78,7 +78,8 @@ int         mi_dspu_event_elapsed_ms(float *ms, void *start, void *stop);
  *   MI_DSPU_TEST_PATH=a,b,..  TEST HOOK, not a tuning knob: sends calls down another LIVE path of the library -- one that other
  *                             inputs take anyway -- so that differential tests can hold two paths against each other:
  *                             blocks_loop, conv_batch_finish, conv_frame_per_launch, crossover_unfused, ilufs_rows_apart,
- *                             loudness_scalar, splitter_hop_launches, analyzer_strobe_per_launch
+ *                             loudness_scalar, splitter_hop_launches, analyzer_strobe_per_launch, dyndelay_serial,
+ *                             dyndelay_parallel
  */
 /*
  * Arm a pair of events for the calling thread: the next hot-path kernel this
@@ -1748,6 +1749,54 @@ int mi_ring_bank_append(mi_ring_bank_t *bank, const float *in, size_t count, siz
 int mi_ring_bank_get(mi_ring_bank_t *bank, float *out, size_t offset, size_t count, size_t out_stride, size_t *read, void *stream);
 /* size(), head position and tail_position(offset), RingBuffer.cpp:140-145. */
 int mi_ring_bank_info(const mi_ring_bank_t *bank, size_t offset, uint32_t *capacity, uint32_t *head, uint32_t *tail_position);
+
+/*
+ * mi_dyndelay_bank: `channels` x lsp::dspu::DynamicDelay (util/DynamicDelay.h, src/main/util/DynamicDelay.cpp): a delay line
+ * whose delay, feedback gain and feedback delay come per sample from three rows.  Per sample (DynamicDelay.cpp:101-116):
+ *     shift = clamp(ssize_t(delay[i]), 0, max_size);  tail = head - shift;  feed = size_t(float(tail) + clamp(fdelay[i], 0, shift))
+ *     line[head] = in[i];  s = line[tail];  line[feed] += s * fgain[i];  out[i] = line[tail];  ++head
+ * (positions modulo the capacity).  The feed index is the reference's float32 sum; the product and the sum round separately; out
+ * is read after the feedback was added.  out, the line and the head have the reference's bits.  nHead lives per channel on
+ * the device, so a process call takes no decision on the host and can be captured in a graph.
+ * Where the reference's behaviour is undefined the bank defines it: delay converts with saturation (a NaN delay is 0, a delay
+ * beyond the range of ssize_t is max_size), and a NaN fdelay counts as 0.  in and fgain may hold anything (Inf, NaN,
+ * subnormals, -0) and follow IEEE arithmetic bit for bit.
+ */
+typedef struct mi_dyndelay_bank mi_dyndelay_bank_t;
+typedef struct { uint32_t head; } mi_dyndelay_state_t;                                      /* nHead */
+/* init(max_size), DynamicDelay.cpp:65-89: capacity = d - d % 0x400 + 0x800 floats with d = max_size + 1, zeroed; head 0.
+ * MI_EINVAL for a capacity above 2^24 floats: the feed index is formed as float32(tail) + ..., and a tail of 2^24 or more
+ * would no longer be exact in float32, in the reference as here. */
+int mi_dyndelay_bank_create(mi_dyndelay_bank_t **bank, uint32_t channels, size_t max_size);
+int mi_dyndelay_bank_destroy(mi_dyndelay_bank_t *bank);
+/* max_delay(), capacity() and nHead of one channel; any of the three may be NULL.  The head is read with a synchronised copy
+ * on the NULL stream (use get_state for another stream). */
+int mi_dyndelay_bank_get(const mi_dyndelay_bank_t *bank, uint32_t channel, uint32_t *max_delay, uint32_t *capacity, uint32_t *head);
+/* nHead of a channel, read and written with a synchronised copy: MI_ESTATE on a stream that is being captured.
+ * set_state: MI_EINVAL for a head outside the line. */
+int mi_dyndelay_bank_get_state(mi_dyndelay_bank_t *bank, uint32_t channel, mi_dyndelay_state_t *state, void *stream);
+int mi_dyndelay_bank_set_state(mi_dyndelay_bank_t *bank, uint32_t channel, const mi_dyndelay_state_t *state, void *stream);
+/* clear(), DynamicDelay.cpp:91-95: every line and every head to zero, on the stream */
+int mi_dyndelay_bank_clear(mi_dyndelay_bank_t *bank, void *stream);
+/* process(out, in, delay, fgain, fdelay, samples), DynamicDelay.cpp:97-118: five device arrays [channels][stride], all required.
+ * All inputs of a stretch of 0x400 samples are read before any of its outputs is stored: out may be any of the four inputs,
+ * with the same stride. */
+int mi_dyndelay_bank_process(mi_dyndelay_bank_t *bank, float *out, const float *in, const float *delay, const float *fgain,
+                             const float *fdelay, size_t count, size_t out_stride, size_t in_stride, size_t delay_stride,
+                             size_t fgain_stride, size_t fdelay_stride, void *stream);
+/* copy(s), DynamicDelay.cpp:124-148, on the device: the newest min(capacities) samples of the source line go to the end of the
+ * destination line, zeros in front of them, the destination's head to 0.  The banks may be the same; the lines may not. */
+int mi_dyndelay_bank_copy(mi_dyndelay_bank_t *dst_bank, uint32_t dst_channel, mi_dyndelay_bank_t *src_bank, uint32_t src_channel,
+                          void *stream);
+/* `count` floats of a channel's line from position `offset` on, to and from HOST memory (dump(), tests, a caller that seeds a
+ * line); synchronised copies, MI_ESTATE on a capturing stream */
+int mi_dyndelay_bank_read_line(mi_dyndelay_bank_t *bank, uint32_t channel, float *host, size_t offset, size_t count, void *stream);
+int mi_dyndelay_bank_write_line(mi_dyndelay_bank_t *bank, uint32_t channel, const float *host, size_t offset, size_t count, void *stream);
+/* Debug counters, written by the kernel only while counting is on: how many steps ran one per lane (parallel) out of how
+ * many in all, over every channel since counting was switched on (which zeroes them).  Both calls synchronise the stream and
+ * are refused on a capturing one; a graph captured while counting goes on counting.  steps: MI_ESTATE while not counting. */
+int mi_dyndelay_bank_count_steps(mi_dyndelay_bank_t *bank, int on, void *stream);
+int mi_dyndelay_bank_steps(mi_dyndelay_bank_t *bank, uint64_t *parallel, uint64_t *total, void *stream);
 
 /*
  * Host-only introspection of the per-section device table (no GPU needed): the

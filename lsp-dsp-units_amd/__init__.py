@@ -12,7 +12,7 @@ Import with ``importlib.import_module("lsp-dsp-units_amd")`` (the directory
 name carries the reference's name and is not a Python identifier).
 """
 from .capi import LIB_PATH, MiError, check, lib          # noqa: F401
-from .units import (AnalyzerBank, AutoGainBank, BiquadBank, BypassBank, Comm, CompressorBank, ConvolverBank, CorrelometerBank, CrossfadeBank, CrossoverBank, DelayBank, DeviceBuffer, DynFilterBank, DynamicProcessorBank, EqualizerBank,  # noqa: F401
+from .units import (AnalyzerBank, AutoGainBank, BiquadBank, BypassBank, Comm, CompressorBank, ConvolverBank, CorrelometerBank, CrossfadeBank, CrossoverBank, DelayBank, DeviceBuffer, DynFilterBank, DynamicDelayBank, DynamicProcessorBank, EqualizerBank,  # noqa: F401
                     ExpanderBank, GateBank, ILUFSBank, LimiterBank, LoudnessBank, OversamplerBank, PanometerBank,
                     PeakMeterBank, RingBank, SidechainBank, SimpleAutoGainBank,
                     SpectralBank, SurgeProtectorBank, SplitterBank, TruePeakBank, crossover_fft_mask,

@@ -1,7 +1,7 @@
 """ctypes declarations for include/mi_dspu.h (one line per exported symbol)."""
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_size_t, c_uint32, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_size_t, c_uint32, c_uint64, c_void_p
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libmi_dspu.so")
 
@@ -212,6 +212,11 @@ class BypassState(ctypes.Structure):
 class CrossfadeState(ctypes.Structure):
     """mi_crossfade_state_t: nCounter, fDelta, fGain."""
     _fields_ = [("counter", c_uint32), ("delta", c_float), ("gain", c_float)]
+
+
+class DynDelayState(ctypes.Structure):
+    """mi_dyndelay_state_t: nHead."""
+    _fields_ = [("head", c_uint32)]
 
 
 # name -> (restype, argtypes); every symbol declared in include/mi_dspu.h must be listed here
@@ -646,6 +651,19 @@ PROTOTYPES = {
     "mi_equalizer_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_equalizer_bank_process_blocks": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_equalizer_bank_info": (c_int, [c_void_p, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_int), POINTER(c_uint32)]),
+    "mi_dyndelay_bank_create": (c_int, [POINTER(c_void_p), c_uint32, c_size_t]),
+    "mi_dyndelay_bank_destroy": (c_int, [c_void_p]),
+    "mi_dyndelay_bank_get": (c_int, [c_void_p, c_uint32, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32)]),
+    "mi_dyndelay_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(DynDelayState), c_void_p]),
+    "mi_dyndelay_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(DynDelayState), c_void_p]),
+    "mi_dyndelay_bank_clear": (c_int, [c_void_p, c_void_p]),
+    "mi_dyndelay_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t,
+                                         c_size_t, c_size_t, c_void_p]),
+    "mi_dyndelay_bank_copy": (c_int, [c_void_p, c_uint32, c_void_p, c_uint32, c_void_p]),
+    "mi_dyndelay_bank_read_line": (c_int, [c_void_p, c_uint32, c_void_p, c_size_t, c_size_t, c_void_p]),
+    "mi_dyndelay_bank_write_line": (c_int, [c_void_p, c_uint32, c_void_p, c_size_t, c_size_t, c_void_p]),
+    "mi_dyndelay_bank_count_steps": (c_int, [c_void_p, c_int, c_void_p]),
+    "mi_dyndelay_bank_steps": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), c_void_p]),
     "mi_delay_bank_create": (c_int, [POINTER(c_void_p), c_uint32, c_size_t]),
     "mi_delay_bank_destroy": (c_int, [c_void_p]),
     "mi_delay_bank_set_delay": (c_int, [c_void_p, c_uint32, c_size_t]),

@@ -598,6 +598,79 @@ class DelayBank:
             pass
 
 
+class DynamicDelayBank:
+    """`channels` x lsp::dspu::DynamicDelay (mi_dyndelay_bank_*): delay, feedback gain and feedback delay per sample from three
+    rows; the lines and nHead on the device."""
+
+    def __init__(self, channels, max_size):
+        h = c_void_p()
+        check(lib.mi_dyndelay_bank_create(byref(h), channels, max_size))
+        self.handle, self.channels = h, channels
+        info = self.get(0, head=False)
+        self.max_delay, self.capacity = info["max_delay"], info["capacity"]
+
+    def get(self, channel=0, head=True):
+        v = [c_uint32() for _ in range(3)]
+        check(lib.mi_dyndelay_bank_get(self.handle, channel, byref(v[0]), byref(v[1]), byref(v[2]) if head else None))
+        return dict(zip(("max_delay", "capacity", "head"), [x.value for x in v][:3 if head else 2]))
+
+    def get_state(self, channel, stream=None):
+        from .capi import DynDelayState
+        s = DynDelayState()
+        check(lib.mi_dyndelay_bank_get_state(self.handle, channel, byref(s), _stream(stream)))
+        return {"head": s.head}
+
+    def set_state(self, channel, head, stream=None):
+        from .capi import DynDelayState
+        s = DynDelayState(int(head))
+        check(lib.mi_dyndelay_bank_set_state(self.handle, channel, byref(s), _stream(stream)))
+
+    def clear(self, stream=None):
+        check(lib.mi_dyndelay_bank_clear(self.handle, _stream(stream)))
+
+    def process(self, out, inp, delay, fgain, fdelay, count, out_stride=None, in_stride=None, delay_stride=None, fgain_stride=None,
+                fdelay_stride=None, stream=None):
+        """process(out, in, delay, fgain, fdelay, count); out may be any of the four inputs (same stride)."""
+        strides = [count if s is None else s for s in (out_stride, in_stride, delay_stride, fgain_stride, fdelay_stride)]
+        check(lib.mi_dyndelay_bank_process(self.handle, _opt(out), _opt(inp), _opt(delay), _opt(fgain), _opt(fdelay), count, *strides,
+                                           _stream(stream)))
+
+    def copy(self, channel, src, src_channel, stream=None):
+        """copy(s): line `channel` of this bank takes the newest samples of line `src_channel` of the bank `src`."""
+        check(lib.mi_dyndelay_bank_copy(self.handle, channel, src.handle, src_channel, _stream(stream)))
+
+    def read_line(self, channel, offset=0, count=None, stream=None):
+        n = self.capacity - offset if count is None else count
+        a = np.empty(n, np.float32)
+        check(lib.mi_dyndelay_bank_read_line(self.handle, channel, a.ctypes.data_as(c_void_p), offset, n, _stream(stream)))
+        return a
+
+    def write_line(self, channel, values, offset=0, stream=None):
+        a = np.ascontiguousarray(values, dtype=np.float32)
+        check(lib.mi_dyndelay_bank_write_line(self.handle, channel, a.ctypes.data_as(c_void_p), offset, a.size, _stream(stream)))
+
+    def count_steps(self, on=True, stream=None):
+        """Debug counters of the kernel: switched on (and zeroed) or off."""
+        check(lib.mi_dyndelay_bank_count_steps(self.handle, 1 if on else 0, _stream(stream)))
+
+    def steps(self, stream=None):
+        """(steps that ran one per lane, steps in all) since count_steps()."""
+        p, t = ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib.mi_dyndelay_bank_steps(self.handle, byref(p), byref(t), _stream(stream)))
+        return p.value, t.value
+
+    def close(self):
+        if self.handle:
+            lib.mi_dyndelay_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class RingBank:
     """`channels` x lsp::dspu::RingBuffer on the device."""
 
