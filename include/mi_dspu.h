@@ -1798,6 +1798,155 @@ int mi_dyndelay_bank_write_line(mi_dyndelay_bank_t *bank, uint32_t channel, cons
 int mi_dyndelay_bank_count_steps(mi_dyndelay_bank_t *bank, int on, void *stream);
 int mi_dyndelay_bank_steps(mi_dyndelay_bank_t *bank, uint64_t *parallel, uint64_t *total, void *stream);
 
+/* ---- oscillator bank (phase-accumulator waveforms) --------------------------------------------------------------------- */
+/*
+ * mi_oscillator_bank: `channels` x lsp::dspu::Oscillator (util/Oscillator.h, src/main/util/Oscillator.cpp): nine plain and five
+ * band-limited (BL) waveforms from a uint32_t phase accumulator, nPhaseAcc = (nPhaseAcc + nFreqCtrlWord) & nPhaseAccMask
+ * (:373).  The phase of sample i of a call is (p0 + i w) & mask in closed form, so a row splits along time as well as across
+ * channels; the value of a sample depends on its phase alone.  nPhaseAcc lives per channel on the device: process takes no
+ * decision on the host and can be captured in a graph.  The settings words and coefficients are computed on the host as the
+ * reference computes them (update_settings, :151-357, its mix of double and float kept), loop-invariant divisions included.
+ *
+ * All non-sinusoid functions, and everything behind the sine (the product by the amplitude, the DC, add and mul), have the
+ * reference's bits.  SINUSOIDS: the reference's sin(fAcc2Phase * nPhaseAcc) is the float overload, so its bits are those of its
+ * C library's sinf.  The bank forms the argument as the reference does (float(phase) rounded to nearest even, one float
+ * product; the squared functions (0.5f * fAcc2Phase) * float(phase)) and takes the float64 sine of that float32 argument,
+ * rounded once to float32 (S*).  glibc's sinf is within one ulp of S*.
+ *
+ * The BL functions synthesise N * count samples with the step nFreqCtrlWord / N into scratch rows and go through
+ * mi_oversampler_bank_downsample of an oversampler bank that the oscillator bank owns (:479-628; one downsample per call: the
+ * reference's chunks of PROCESS_BUF_LIMIT_SIZE / N change no value, the filter's state runs on).  That bank has one mode and one
+ * rate: the channels with a BL function must agree in sample rate and oversampler mode (update_settings: MI_EINVAL otherwise;
+ * use two banks).  The oversampler follows the first BL channel, or channel 0 where there is none.
+ *
+ * What the bank defines where the reference does not:
+ *   - trapezoid, :430-443: with fFallRatio == 0, nPoints[1] == nPoints[2], and a phase exactly there satisfies two of the
+ *     five ifs (:433 and :439); the reference then writes two values for one sample and runs past its buffer.  The bank
+ *     writes exactly one value per sample: the first branch, in source order, that holds.
+ *   - nFreqCtrlWord (and every other word) comes from a floating-point to uint32_t conversion that is undefined for a negative,
+ *     too large or NaN value.  The bank converts through int64_t and keeps the low 32 bits, NaN and what does not fit int64_t
+ *     as 0: what the x86-64 build of the reference does.
+ *   - nSampleRate starts at size_t(-1): a channel whose rate was never set refuses process with MI_ESTATE.
+ *   - get_periods (:635-689): after a refill (:675-684, every call without skipped periods has one) the read position t has had
+ *     the whole buffer size subtracted and is negative, and vSynthBuffer[size_t(t)] reads in front of the buffer, out of
+ *     vProcessBuffer.  Bank and class read 0.0f for a position in front of the buffer.  A call with skipped periods that fits
+ *     one buffer never refills and has the reference's values.  A period that is not positive and finite is refused (MI_EINVAL;
+ *     the class writes nothing): the reference's loops do not end for it.  Positions of the buffer that no fill of the channel's
+ *     get_periods calls has written read 0.0f (in the reference vSynthBuffer also holds what process_* staged there).
+ */
+typedef struct mi_oscillator_bank mi_oscillator_bank_t;
+enum
+{
+    MI_FG_SINE, MI_FG_COSINE, MI_FG_SQUARED_SINE, MI_FG_SQUARED_COSINE, MI_FG_RECTANGULAR, MI_FG_SAWTOOTH, MI_FG_TRAPEZOID,
+    MI_FG_PULSETRAIN, MI_FG_PARABOLIC, MI_FG_BL_RECTANGULAR, MI_FG_BL_SAWTOOTH, MI_FG_BL_TRAPEZOID, MI_FG_BL_PULSETRAIN,
+    MI_FG_BL_PARABOLIC                                                                      /* fg_function_t, Oscillator.h:33-49 */
+};
+enum { MI_DC_WAVEDC, MI_DC_ZERO };                                                          /* dc_reference_t, Oscillator.h:51-55 */
+enum { MI_OSC_OVERWRITE, MI_OSC_ADD, MI_OSC_MUL };                                          /* process_overwrite / _add / _mul */
+/* The members of one oscillator (Oscillator.h:116-151) without its buffers, and what the host knows of nPhaseAcc: with
+ * phase_known the accumulator IS `phase`; otherwise it is (the device's + phase) & mask.  Host only. */
+typedef struct mi_oscillator_settings
+{
+    uint32_t    function;                                   /* enFunction */
+    float       amplitude, frequency, dc_offset;
+    uint32_t    dc_reference;
+    float       referenced_dc, init_phase;
+    uint64_t    sample_rate;                                /* nSampleRate: UINT64_MAX until set */
+    uint32_t    bits, mask;                                 /* nPhaseAccBits, nPhaseAccMask */
+    float       acc2phase;
+    uint32_t    freq_word, init_word;
+    uint32_t    sq_invert;          float sq_amplitude, sq_wave_dc;                                     /* sSquaredSinusoid */
+    float       duty;               uint32_t duty_word;     float rect_wave_dc, rect_atten;             /* sRectangular */
+    float       width;              uint32_t width_word;    float saw_coeffs[4], saw_wave_dc, saw_atten; /* sSawtooth */
+    float       raise_ratio, fall_ratio; uint32_t points[4]; float trap_coeffs[4], trap_wave_dc, trap_atten; /* sTrapezoid */
+    float       pos_ratio, neg_ratio; uint32_t train[3];    float pulse_wave_dc, pulse_atten;           /* sPulse */
+    uint32_t    par_invert;         float par_amplitude, par_width; uint32_t par_word; float par_wave_dc, par_atten; /* sParabolic */
+    uint32_t    oversampling, over_mode, freq_word_over;
+    uint32_t    sync;                                       /* bSync */
+    uint32_t    phase_known, phase;
+    uint32_t    unset_rate_ok;                              /* the C++ class: a rate of size_t(-1) is processed with, as the reference does */
+} mi_oscillator_settings_t;
+/* The setters of Oscillator.h:207-257 and Oscillator.cpp:749-890, with the reference's clamps and refusals (a refused value
+ * changes nothing and is no error) */
+enum
+{
+    MI_OSC_SET_FUNCTION, MI_OSC_SET_FREQUENCY, MI_OSC_SET_SAMPLE_RATE, MI_OSC_SET_PHASE, MI_OSC_SET_PHASE_ACCUMULATOR_BITS,
+    MI_OSC_SET_DC_OFFSET, MI_OSC_SET_DC_REFERENCE, MI_OSC_SET_AMPLITUDE, MI_OSC_SET_DUTY_RATIO, MI_OSC_SET_WIDTH,
+    MI_OSC_SET_TRAPEZOID_RATIOS, MI_OSC_SET_PULSETRAIN_RATIOS, MI_OSC_SET_PARABOLIC_WIDTH, MI_OSC_SET_SQUARED_SINUSOID_INVERSION,
+    MI_OSC_SET_PARABOLIC_INVERSION, MI_OSC_SET_OVERSAMPLER_MODE, MI_OSC_RESET_PHASE_ACCUMULATOR, MI_OSC_SETTERS
+};
+/* construct(), :42-117; one setter (a, b: its arguments; integers and flags as their value; MI_EINVAL for an unknown setter, a
+ * function above MI_FG_BL_PARABOLIC, a DC reference above MI_DC_ZERO or an oversampler mode above MI_OM_LANCZOS_8X24BIT);
+ * update_settings(), :151-357 without the oversamplers' part.  No device needed. */
+int mi_oscillator_settings_init(mi_oscillator_settings_t *s);
+int mi_oscillator_settings_set(mi_oscillator_settings_t *s, uint32_t setter, double a, double b);
+int mi_oscillator_settings_update(mi_oscillator_settings_t *s);
+
+int mi_oscillator_bank_create(mi_oscillator_bank_t **bank, uint32_t channels);              /* construct() + init(), :42-135 */
+int mi_oscillator_bank_destroy(mi_oscillator_bank_t *bank);                                 /* :137-149 */
+/* One setter of one channel (MI_OSC_SET_*, as mi_oscillator_settings_set), and by name */
+int mi_oscillator_bank_set(mi_oscillator_bank_t *bank, uint32_t channel, uint32_t setter, double a, double b);
+int mi_oscillator_bank_set_function(mi_oscillator_bank_t *bank, uint32_t channel, uint32_t function);           /* .h:240-244 */
+int mi_oscillator_bank_set_frequency(mi_oscillator_bank_t *bank, uint32_t channel, float frequency);            /* .h:250-257 */
+int mi_oscillator_bank_set_sample_rate(mi_oscillator_bank_t *bank, uint32_t channel, size_t sample_rate);       /* .h:221-229 */
+int mi_oscillator_bank_set_phase(mi_oscillator_bank_t *bank, uint32_t channel, float phase);                    /* :749-757 */
+int mi_oscillator_bank_set_phase_accumulator_bits(mi_oscillator_bank_t *bank, uint32_t channel, uint32_t bits); /* .h:207-215 */
+int mi_oscillator_bank_set_dc_offset(mi_oscillator_bank_t *bank, uint32_t channel, float dc_offset);            /* :765-771 */
+int mi_oscillator_bank_set_dc_reference(mi_oscillator_bank_t *bank, uint32_t channel, uint32_t reference);      /* :773-777 */
+int mi_oscillator_bank_set_amplitude(mi_oscillator_bank_t *bank, uint32_t channel, float amplitude);            /* :883-890 */
+int mi_oscillator_bank_set_duty_ratio(mi_oscillator_bank_t *bank, uint32_t channel, float duty);                /* :797-804 */
+int mi_oscillator_bank_set_width(mi_oscillator_bank_t *bank, uint32_t channel, float width);                    /* :806-817 */
+int mi_oscillator_bank_set_trapezoid_ratios(mi_oscillator_bank_t *bank, uint32_t channel, float raise, float fall);    /* :819-838 */
+int mi_oscillator_bank_set_pulsetrain_ratios(mi_oscillator_bank_t *bank, uint32_t channel, float pos, float neg);      /* :840-858 */
+int mi_oscillator_bank_set_parabolic_width(mi_oscillator_bank_t *bank, uint32_t channel, float width);          /* :860-872 */
+int mi_oscillator_bank_set_squared_sinusoid_inversion(mi_oscillator_bank_t *bank, uint32_t channel, int invert); /* :779-786 */
+int mi_oscillator_bank_set_parabolic_inversion(mi_oscillator_bank_t *bank, uint32_t channel, int invert);       /* :788-795 */
+int mi_oscillator_bank_set_oversampler_mode(mi_oscillator_bank_t *bank, uint32_t channel, uint32_t mode);       /* :874-881 */
+/* (set_sample_rate and set_oversampler_mode: the channels that have a BL function must agree in both, see above; the
+ * disagreement is reported by update_settings and process, MI_EINVAL) */
+int mi_oscillator_bank_reset_phase_accumulator(mi_oscillator_bank_t *bank, uint32_t channel);                   /* .h:234 */
+/* needs_update(), .h:192-195: bSync of the channel */
+int mi_oscillator_bank_needs_update(const mi_oscillator_bank_t *bank, uint32_t channel, int *yes);
+/* update_settings(), :151-357, of every channel whose bSync is set.  The phase move of :164-166 depends on the device's phase:
+ * the host records the pending change (subtract the old init word, add the new one; or the value itself after a reset) and the
+ * next process applies it on the device; there is no read-back.  Changed records are sent to the device: MI_ESTATE on a stream
+ * that is being captured if there is anything to send. */
+int mi_oscillator_bank_update_settings(mi_oscillator_bank_t *bank, void *stream);
+/* The channel's members as update_settings left them */
+int mi_oscillator_bank_get_settings(const mi_oscillator_bank_t *bank, uint32_t channel, mi_oscillator_settings_t *settings);
+/* ... and set as they stand: members that mi_oscillator_settings_* computed elsewhere (the C++ class does).  With phase_known the
+ * phase goes to the device with the next process.  MI_EINVAL for a function, an oversampler mode, a width or an oversampling out
+ * of range. */
+int mi_oscillator_bank_set_settings(mi_oscillator_bank_t *bank, uint32_t channel, const mi_oscillator_settings_t *settings);
+int mi_oscillator_bank_get_exact_frequency(const mi_oscillator_bank_t *bank, uint32_t channel, float *frequency);      /* .h:262-265 */
+int mi_oscillator_bank_get_exact_phase(const mi_oscillator_bank_t *bank, uint32_t channel, float *phase);              /* :759-763 */
+/* process_overwrite / process_add / process_mul, :691-747, by `op`: dst [channels][dst_stride] device rows of `count` samples.
+ * update_settings() runs first, as in the reference.  src [channels][src_stride] is read by add and mul only and may be NULL:
+ * 0.0f + s and 0.0f * s then, as fill_zero followed by add2 / mul2 gives.  Every lane reads its src values before it stores:
+ * dst may be src, with the same stride.  A BL function needs scratch rows of N * count floats: they grow outside a capture
+ * (reserve), MI_ESTATE inside one. */
+int mi_oscillator_bank_process(mi_oscillator_bank_t *bank, float *dst, const float *src, size_t count, size_t dst_stride,
+                               size_t src_stride, uint32_t op, void *stream);
+/* Scratch rows for BL calls of up to `count` samples at the largest oversampling (8), the oversampler's own included */
+int mi_oscillator_bank_reserve(mi_oscillator_bank_t *bank, size_t count);
+/* mi_oversampler_bank_set_exact of the bank's oversampler */
+int mi_oscillator_bank_set_exact(mi_oscillator_bank_t *bank, int on);
+/* nPhaseAcc of a channel (pending changes applied), read and written with a synchronised copy: MI_ESTATE on a capturing stream */
+typedef struct { uint32_t phase; } mi_oscillator_state_t;
+int mi_oscillator_bank_get_state(mi_oscillator_bank_t *bank, uint32_t channel, mi_oscillator_state_t *state, void *stream);
+int mi_oscillator_bank_set_state(mi_oscillator_bank_t *bank, uint32_t channel, const mi_oscillator_state_t *state, void *stream);
+/* get_periods(dst, periods, periodsSkip, samples), :635-689, of one channel: dst is a DEVICE row of `samples` floats.  The loop runs
+ * on the host with the reference's float arithmetic; every fill is a launch from a phase of its own that starts at
+ * nInitPhaseWord, into a row of 12 * 1024 floats that the channel keeps between calls (its stale contents are read, as :683
+ * has it), for a BL function through an oversampler bank of the channel's own (sOverGetPeriods; made at the first such call, it
+ * follows set_exact); the picks are a gather kernel.  Synchronous; MI_ESTATE on a capturing stream.  nPhaseAcc and the
+ * streaming oversampler are not touched. */
+int mi_oscillator_bank_get_periods(mi_oscillator_bank_t *bank, uint32_t channel, float *dst, size_t periods, size_t periods_skip,
+                                   size_t samples, void *stream);
+/* The oversampled rows of the last BL call ([channels][stride] device floats, N * count of them per row; NULL before the first):
+ * what went into the downsampler.  For tests that feed them to an oversampler bank of their own. */
+int mi_oscillator_bank_synth_rows(const mi_oscillator_bank_t *bank, const float **rows, size_t *stride);
+
 /*
  * Host-only introspection of the per-section device table (no GPU needed): the
  * chunk-parallel form of the TDF-II section used by the kernel.

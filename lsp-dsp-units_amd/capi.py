@@ -219,6 +219,28 @@ class DynDelayState(ctypes.Structure):
     _fields_ = [("head", c_uint32)]
 
 
+class OscillatorState(ctypes.Structure):
+    """mi_oscillator_state_t: nPhaseAcc."""
+    _fields_ = [("phase", c_uint32)]
+
+
+class OscillatorSettings(ctypes.Structure):
+    """mi_oscillator_settings_t: the members of one lsp::dspu::Oscillator and what the host knows of its phase."""
+    _fields_ = [("function", c_uint32), ("amplitude", c_float), ("frequency", c_float), ("dc_offset", c_float), ("dc_reference", c_uint32),
+                ("referenced_dc", c_float), ("init_phase", c_float), ("sample_rate", c_uint64), ("bits", c_uint32), ("mask", c_uint32),
+                ("acc2phase", c_float), ("freq_word", c_uint32), ("init_word", c_uint32),
+                ("sq_invert", c_uint32), ("sq_amplitude", c_float), ("sq_wave_dc", c_float),
+                ("duty", c_float), ("duty_word", c_uint32), ("rect_wave_dc", c_float), ("rect_atten", c_float),
+                ("width", c_float), ("width_word", c_uint32), ("saw_coeffs", c_float * 4), ("saw_wave_dc", c_float), ("saw_atten", c_float),
+                ("raise_ratio", c_float), ("fall_ratio", c_float), ("points", c_uint32 * 4), ("trap_coeffs", c_float * 4),
+                ("trap_wave_dc", c_float), ("trap_atten", c_float),
+                ("pos_ratio", c_float), ("neg_ratio", c_float), ("train", c_uint32 * 3), ("pulse_wave_dc", c_float), ("pulse_atten", c_float),
+                ("par_invert", c_uint32), ("par_amplitude", c_float), ("par_width", c_float), ("par_word", c_uint32),
+                ("par_wave_dc", c_float), ("par_atten", c_float),
+                ("oversampling", c_uint32), ("over_mode", c_uint32), ("freq_word_over", c_uint32), ("sync", c_uint32),
+                ("phase_known", c_uint32), ("phase", c_uint32), ("unset_rate_ok", c_uint32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/mi_dspu.h must be listed here
 # (tests/test_abi.py parses the header and checks both directions).
 PROTOTYPES = {
@@ -664,6 +686,42 @@ PROTOTYPES = {
     "mi_dyndelay_bank_write_line": (c_int, [c_void_p, c_uint32, c_void_p, c_size_t, c_size_t, c_void_p]),
     "mi_dyndelay_bank_count_steps": (c_int, [c_void_p, c_int, c_void_p]),
     "mi_dyndelay_bank_steps": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), c_void_p]),
+    "mi_oscillator_settings_init": (c_int, [POINTER(OscillatorSettings)]),
+    "mi_oscillator_settings_set": (c_int, [POINTER(OscillatorSettings), c_uint32, c_double, c_double]),
+    "mi_oscillator_settings_update": (c_int, [POINTER(OscillatorSettings)]),
+    "mi_oscillator_bank_create": (c_int, [POINTER(c_void_p), c_uint32]),
+    "mi_oscillator_bank_destroy": (c_int, [c_void_p]),
+    "mi_oscillator_bank_set": (c_int, [c_void_p, c_uint32, c_uint32, c_double, c_double]),
+    "mi_oscillator_bank_set_function": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_oscillator_bank_set_frequency": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_oscillator_bank_set_sample_rate": (c_int, [c_void_p, c_uint32, c_size_t]),
+    "mi_oscillator_bank_set_phase": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_oscillator_bank_set_phase_accumulator_bits": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_oscillator_bank_set_dc_offset": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_oscillator_bank_set_dc_reference": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_oscillator_bank_set_amplitude": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_oscillator_bank_set_duty_ratio": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_oscillator_bank_set_width": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_oscillator_bank_set_trapezoid_ratios": (c_int, [c_void_p, c_uint32, c_float, c_float]),
+    "mi_oscillator_bank_set_pulsetrain_ratios": (c_int, [c_void_p, c_uint32, c_float, c_float]),
+    "mi_oscillator_bank_set_parabolic_width": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_oscillator_bank_set_squared_sinusoid_inversion": (c_int, [c_void_p, c_uint32, c_int]),
+    "mi_oscillator_bank_set_parabolic_inversion": (c_int, [c_void_p, c_uint32, c_int]),
+    "mi_oscillator_bank_set_oversampler_mode": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_oscillator_bank_reset_phase_accumulator": (c_int, [c_void_p, c_uint32]),
+    "mi_oscillator_bank_needs_update": (c_int, [c_void_p, c_uint32, POINTER(c_int)]),
+    "mi_oscillator_bank_update_settings": (c_int, [c_void_p, c_void_p]),
+    "mi_oscillator_bank_get_settings": (c_int, [c_void_p, c_uint32, POINTER(OscillatorSettings)]),
+    "mi_oscillator_bank_set_settings": (c_int, [c_void_p, c_uint32, POINTER(OscillatorSettings)]),
+    "mi_oscillator_bank_get_exact_frequency": (c_int, [c_void_p, c_uint32, POINTER(c_float)]),
+    "mi_oscillator_bank_get_exact_phase": (c_int, [c_void_p, c_uint32, POINTER(c_float)]),
+    "mi_oscillator_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_uint32, c_void_p]),
+    "mi_oscillator_bank_reserve": (c_int, [c_void_p, c_size_t]),
+    "mi_oscillator_bank_set_exact": (c_int, [c_void_p, c_int]),
+    "mi_oscillator_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(OscillatorState), c_void_p]),
+    "mi_oscillator_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(OscillatorState), c_void_p]),
+    "mi_oscillator_bank_get_periods": (c_int, [c_void_p, c_uint32, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_oscillator_bank_synth_rows": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_size_t)]),
     "mi_delay_bank_create": (c_int, [POINTER(c_void_p), c_uint32, c_size_t]),
     "mi_delay_bank_destroy": (c_int, [c_void_p]),
     "mi_delay_bank_set_delay": (c_int, [c_void_p, c_uint32, c_size_t]),

@@ -671,6 +671,103 @@ class DynamicDelayBank:
             pass
 
 
+class OscillatorBank:
+    """`channels` x lsp::dspu::Oscillator (mi_oscillator_bank_*): phase-accumulator waveforms; nPhaseAcc on the device."""
+    OVERWRITE, ADD, MUL = 0, 1, 2
+    SETTERS = ("function", "frequency", "sample_rate", "phase", "phase_accumulator_bits", "dc_offset", "dc_reference", "amplitude",
+               "duty_ratio", "width", "trapezoid_ratios", "pulsetrain_ratios", "parabolic_width", "squared_sinusoid_inversion",
+               "parabolic_inversion", "oversampler_mode")
+
+    def __init__(self, channels):
+        h = c_void_p()
+        check(lib.mi_oscillator_bank_create(byref(h), channels))
+        self.handle, self.channels = h, channels
+
+    def set(self, channel, setter, a=0.0, b=0.0):
+        """One setter by its MI_OSC_SET_* number."""
+        check(lib.mi_oscillator_bank_set(self.handle, channel, setter, float(a), float(b)))
+
+    def __getattr__(self, name):
+        # set_<name>(channel, value[, second]): the reference's setters, each one its own C entry
+        if name.startswith("set_") and name[4:] in self.SETTERS:
+            fn = getattr(lib, "mi_oscillator_bank_" + name)
+            return lambda channel, *values: check(fn(self.handle, channel, *values))
+        raise AttributeError(name)
+
+    def reset_phase_accumulator(self, channel):
+        check(lib.mi_oscillator_bank_reset_phase_accumulator(self.handle, channel))
+
+    def needs_update(self, channel):
+        v = c_int()
+        check(lib.mi_oscillator_bank_needs_update(self.handle, channel, byref(v)))
+        return bool(v.value)
+
+    def update_settings(self, stream=None):
+        check(lib.mi_oscillator_bank_update_settings(self.handle, _stream(stream)))
+
+    def get_settings(self, channel):
+        from .capi import OscillatorSettings
+        s = OscillatorSettings()
+        check(lib.mi_oscillator_bank_get_settings(self.handle, channel, byref(s)))
+        return s
+
+    def set_settings(self, channel, settings):
+        check(lib.mi_oscillator_bank_set_settings(self.handle, channel, byref(settings)))
+
+    def get_exact_frequency(self, channel):
+        v = c_float()
+        check(lib.mi_oscillator_bank_get_exact_frequency(self.handle, channel, byref(v)))
+        return v.value
+
+    def get_exact_phase(self, channel):
+        v = c_float()
+        check(lib.mi_oscillator_bank_get_exact_phase(self.handle, channel, byref(v)))
+        return v.value
+
+    def process(self, dst, count, src=None, op=0, dst_stride=None, src_stride=None, stream=None):
+        """process_overwrite / process_add / process_mul by `op`; dst may be src (same stride); src may be None."""
+        check(lib.mi_oscillator_bank_process(self.handle, _opt(dst), _opt(src), count, count if dst_stride is None else dst_stride,
+                                             count if src_stride is None else src_stride, op, _stream(stream)))
+
+    def reserve(self, count):
+        check(lib.mi_oscillator_bank_reserve(self.handle, count))
+
+    def set_exact(self, on=True):
+        check(lib.mi_oscillator_bank_set_exact(self.handle, 1 if on else 0))
+
+    def get_state(self, channel, stream=None):
+        from .capi import OscillatorState
+        s = OscillatorState()
+        check(lib.mi_oscillator_bank_get_state(self.handle, channel, byref(s), _stream(stream)))
+        return {"phase": s.phase}
+
+    def set_state(self, channel, phase, stream=None):
+        from .capi import OscillatorState
+        s = OscillatorState(int(phase))
+        check(lib.mi_oscillator_bank_set_state(self.handle, channel, byref(s), _stream(stream)))
+
+    def get_periods(self, channel, dst, periods, skip, samples, stream=None):
+        """get_periods(dst, periods, periodsSkip, samples) of one channel into a device row; synchronous."""
+        check(lib.mi_oscillator_bank_get_periods(self.handle, channel, _opt(dst), periods, skip, samples, _stream(stream)))
+
+    def synth_rows(self):
+        """(device pointer, stride) of the oversampled rows of the last BL call."""
+        p, n = c_void_p(), ctypes.c_size_t()
+        check(lib.mi_oscillator_bank_synth_rows(self.handle, byref(p), byref(n)))
+        return p.value or 0, n.value
+
+    def close(self):
+        if self.handle:
+            lib.mi_oscillator_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class RingBank:
     """`channels` x lsp::dspu::RingBuffer on the device."""
 
