@@ -1947,6 +1947,102 @@ int mi_oscillator_bank_get_periods(mi_oscillator_bank_t *bank, uint32_t channel,
  * what went into the downsampler.  For tests that feed them to an oversampler bank of their own. */
 int mi_oscillator_bank_synth_rows(const mi_oscillator_bank_t *bank, const float **rows, size_t *stride);
 
+/* ---- noise banks (LCG white noise, maximum-length sequences) ------------------------------------------------------------------ */
+/*
+ * Both banks: process(dst, src, count, dst_stride, src_stride, op, stream) with op = MI_OSC_OVERWRITE / MI_OSC_ADD / MI_OSC_MUL as
+ * mi_oscillator_bank_process has it (process_overwrite / process_add / process_mul of every channel).  dst [channels][dst_stride]
+ * and src [channels][src_stride] are device rows; every lane reads its src values before it stores, so dst may be src with the
+ * same stride.  The state lives on the device and the kernels write it back: nothing is read back, a call can be captured.
+ * Defined where the reference is not:
+ *   - src == NULL with add or mul (a null dereference there) is MI_EINVAL;
+ *   - count == 0 succeeds and changes nothing: no state, and for MLS no pending update_settings is run either.
+ *
+ * mi_lcg_bank: `channels` x lsp::dspu::LCG (noise/LCG.h, src/main/noise/LCG.cpp) over lsp::dspu::Randomizer
+ * (src/main/util/Randomizer.cpp): four generators vLast = vMul1 * vLast + ((vMul2 * vLast) >> 16) + vAdd in uint32_t, drawn round
+ * robin from nBufID on.  The map is not affine, so a channel is four serial chains: one lane per (channel, generator) runs them in
+ * chunks and leaves the raw draws in LDS in draw order; all lanes of the workgroup turn draws into samples.  A call of `count`
+ * samples takes count draws (uniform, triangular) or 2 * count (exponential, Gaussian), and the next call goes on exactly there.
+ * Uniform and triangular samples are the reference's bits; expf, logf and cosf are the float64 function of the reference's float32
+ * argument rounded once (the reference's bits there are its C library's).
+ * Defined where the reference is not:
+ *   - a channel that was never init()ed has nBufID == size_t(-1) and the reference indexes vRandom[-1]: process is MI_ESTATE;
+ *   - a distribution above MI_LCG_GAUSSIAN is what the reference's switch makes of it (default: uniform); the setter takes it.
+ */
+typedef struct mi_lcg_bank mi_lcg_bank_t;
+enum { MI_LCG_UNIFORM, MI_LCG_EXPONENTIAL, MI_LCG_TRIANGULAR, MI_LCG_GAUSSIAN };            /* lcg_dist_t, LCG.h */
+#define MI_LCG_UNSET 0xFFFFFFFFu                                                            /* nBufID of a Randomizer before init() */
+/* The members of one Randomizer: randgen_t vRandom[4] by member, and nBufID (0 .. 3, or MI_LCG_UNSET) */
+typedef struct { uint32_t last[4], mul1[4], mul2[4], add[4]; uint32_t buf_id; } mi_lcg_state_t;
+/* Randomizer::init(seed), Randomizer.cpp:86-99, as words (host only, no device) */
+int mi_lcg_seed_words(uint32_t seed, mi_lcg_state_t *state);
+int mi_lcg_bank_create(mi_lcg_bank_t **bank, uint32_t channels);                            /* construct() */
+int mi_lcg_bank_destroy(mi_lcg_bank_t *bank);
+int mi_lcg_bank_init(mi_lcg_bank_t *bank, uint32_t channel, uint32_t seed);                 /* init(seed) */
+int mi_lcg_bank_init_time(mi_lcg_bank_t *bank, uint32_t channel);                           /* init(): the seed is the host clock */
+int mi_lcg_bank_set_distribution(mi_lcg_bank_t *bank, uint32_t channel, uint32_t distribution);
+int mi_lcg_bank_set_amplitude(mi_lcg_bank_t *bank, uint32_t channel, float amplitude);
+int mi_lcg_bank_set_offset(mi_lcg_bank_t *bank, uint32_t channel, float offset);
+/* Changed settings and states given by init / set_state go to the device first: outside a capture (MI_ESTATE inside one).  They
+ * travel with the next process() that is ISSUED: a graph captured before replays with what the device holds and does not see
+ * them until a plain process() has sent them. */
+int mi_lcg_bank_process(mi_lcg_bank_t *bank, float *dst, const float *src, size_t count, size_t dst_stride, size_t src_stride,
+                        uint32_t op, void *stream);
+/* One channel's Randomizer, read with a synchronised copy and given to the next launch: MI_ESTATE on a capturing stream.
+ * set_state takes buf_id 0 .. 3, or MI_LCG_UNSET for a channel as construct() leaves it. */
+int mi_lcg_bank_get_state(mi_lcg_bank_t *bank, uint32_t channel, mi_lcg_state_t *state, void *stream);
+int mi_lcg_bank_set_state(mi_lcg_bank_t *bank, uint32_t channel, const mi_lcg_state_t *state, void *stream);
+
+/*
+ * mi_mls_bank: `channels` x lsp::dspu::MLS (noise/MLS.h, src/main/noise/MLS.cpp) with mls_t = uint64_t, the reference's LP64 build.
+ * The register shifts right and its output is bit 0, so the update is linear over GF(2): sample i of a call is the parity of
+ * rows[i] & state with rows[i] = row 0 of the i-th power of the transition matrix M, and the state n samples on is M^n state.  The
+ * kernel runs over (tile of 1024 samples, channel); a tile reaches its state through the powers M^(1024 * 2^j) over the set bits of
+ * its index, and a launch of one wave per channel behind the tiles writes M^count state.  rows and the powers M^(2^p) depend on the
+ * register width alone: one table for all 64 widths per device, made at the first create(): nothing is built or sent per call.
+ * The host follows nState exactly (it knows count), so set_state's "unchanged: nothing happens" rule (MLS.cpp:123-130) and
+ * needs_update() are the reference's with no read-back.  A sample is fAmplitude + fOffset or -fAmplitude + fOffset: two float sums.
+ */
+typedef struct mi_mls_bank mi_mls_bank_t;
+/* The members of one MLS (MLS.h), nState as it stands after every call issued so far */
+typedef struct mi_mls_settings
+{
+    uint64_t n_bits, feedback_bit, feedback_mask, active_mask, taps_mask, output_mask, state;
+    float    amplitude, offset;
+    uint32_t sync, pad;
+} mi_mls_settings_t;
+/* construct() and update_settings(), MLS.cpp:89-103 and :153-179, on a mi_mls_settings_t (host only, no device) */
+int mi_mls_settings_init(mi_mls_settings_t *s);
+int mi_mls_settings_update(mi_mls_settings_t *s);
+/* The closed form of a register of n_bits (1 .. 64), host only: rows[1024] and powers[27][64] (either may be NULL), and M^count state */
+int mi_mls_tables(uint32_t n_bits, uint64_t *rows, uint64_t *powers);
+int mi_mls_advance(uint32_t n_bits, uint64_t state, uint64_t count, uint64_t *result);
+int mi_mls_bank_create(mi_mls_bank_t **bank, uint32_t channels);                            /* construct() */
+int mi_mls_bank_destroy(mi_mls_bank_t *bank);
+int mi_mls_bank_set_n_bits(mi_mls_bank_t *bank, uint32_t channel, size_t n_bits);           /* :114-121; clamped to 1 .. 64 at the update */
+int mi_mls_bank_set_state(mi_mls_bank_t *bank, uint32_t channel, uint64_t state);           /* :123-130 */
+int mi_mls_bank_set_amplitude(mi_mls_bank_t *bank, uint32_t channel, float amplitude);      /* :132-138 */
+int mi_mls_bank_set_offset(mi_mls_bank_t *bank, uint32_t channel, float offset);            /* :140-146 */
+int mi_mls_bank_needs_update(const mi_mls_bank_t *bank, uint32_t channel, int *yes);        /* :109-112 */
+/* update_settings() of every channel that needs it, and changed records go to the device: outside a capture (MI_ESTATE inside
+ * one; process runs it first, as progress() does) */
+int mi_mls_bank_update_settings(mi_mls_bank_t *bank, void *stream);
+int mi_mls_bank_maximum_number_of_bits(const mi_mls_bank_t *bank, size_t *bits);            /* :148-151: 64 */
+/* :199-206; 2^64 - 1 for every n_bits from 64 on (the reference shifts by n_bits there before update_settings has clamped it) */
+int mi_mls_bank_get_period(const mi_mls_bank_t *bank, uint32_t channel, uint64_t *period);
+int mi_mls_bank_process(mi_mls_bank_t *bank, float *dst, const float *src, size_t count, size_t dst_stride, size_t src_stride,
+                        uint32_t op, void *stream);
+/* What a capture of calls of `count` samples needs is there after this: the tables are (they do not depend on count), so it only
+ * checks count; kept so that every generator bank is prepared for a capture alike */
+int mi_mls_bank_reserve(mi_mls_bank_t *bank, size_t count);
+int mi_mls_bank_get_settings(const mi_mls_bank_t *bank, uint32_t channel, mi_mls_settings_t *settings);
+/* nState of a channel as the device holds it (the host's where a set_state or an update has not been launched yet), read with a
+ * synchronised copy: MI_ESTATE on a capturing stream.  get_settings gives the host's copy of the same word.  The host counts the
+ * calls it issues; replays of a captured graph move the device's word on without it, and this call brings the host's copy up to
+ * the device's again (everything issued on other streams has to be complete).  Until then set_state's no-op rule and get_settings
+ * speak of the calls that were issued, not of the replays; a set_state or set_n_bits after a capture reaches the device with the
+ * next process() that is issued, not with a replay. */
+int mi_mls_bank_get_state(mi_mls_bank_t *bank, uint32_t channel, uint64_t *state, void *stream);
+
 /*
  * Host-only introspection of the per-section device table (no GPU needed): the
  * chunk-parallel form of the TDF-II section used by the kernel.

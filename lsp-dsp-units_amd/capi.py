@@ -241,6 +241,17 @@ class OscillatorSettings(ctypes.Structure):
                 ("phase_known", c_uint32), ("phase", c_uint32), ("unset_rate_ok", c_uint32)]
 
 
+class LcgState(ctypes.Structure):
+    """mi_lcg_state_t: the members of one lsp::dspu::Randomizer."""
+    _fields_ = [("last", c_uint32 * 4), ("mul1", c_uint32 * 4), ("mul2", c_uint32 * 4), ("add", c_uint32 * 4), ("buf_id", c_uint32)]
+
+
+class MlsSettings(ctypes.Structure):
+    """mi_mls_settings_t: the members of one lsp::dspu::MLS."""
+    _fields_ = [(n, c_uint64) for n in ("n_bits", "feedback_bit", "feedback_mask", "active_mask", "taps_mask", "output_mask", "state")] + \
+               [("amplitude", c_float), ("offset", c_float), ("sync", c_uint32), ("pad", c_uint32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/mi_dspu.h must be listed here
 # (tests/test_abi.py parses the header and checks both directions).
 PROTOTYPES = {
@@ -722,6 +733,35 @@ PROTOTYPES = {
     "mi_oscillator_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(OscillatorState), c_void_p]),
     "mi_oscillator_bank_get_periods": (c_int, [c_void_p, c_uint32, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_oscillator_bank_synth_rows": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_size_t)]),
+    "mi_lcg_seed_words": (c_int, [c_uint32, POINTER(LcgState)]),
+    "mi_lcg_bank_create": (c_int, [POINTER(c_void_p), c_uint32]),
+    "mi_lcg_bank_destroy": (c_int, [c_void_p]),
+    "mi_lcg_bank_init": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_lcg_bank_init_time": (c_int, [c_void_p, c_uint32]),
+    "mi_lcg_bank_set_distribution": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_lcg_bank_set_amplitude": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_lcg_bank_set_offset": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_lcg_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_uint32, c_void_p]),
+    "mi_lcg_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(LcgState), c_void_p]),
+    "mi_lcg_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(LcgState), c_void_p]),
+    "mi_mls_settings_init": (c_int, [POINTER(MlsSettings)]),
+    "mi_mls_settings_update": (c_int, [POINTER(MlsSettings)]),
+    "mi_mls_tables": (c_int, [c_uint32, POINTER(c_uint64), POINTER(c_uint64)]),
+    "mi_mls_advance": (c_int, [c_uint32, c_uint64, c_uint64, POINTER(c_uint64)]),
+    "mi_mls_bank_create": (c_int, [POINTER(c_void_p), c_uint32]),
+    "mi_mls_bank_destroy": (c_int, [c_void_p]),
+    "mi_mls_bank_set_n_bits": (c_int, [c_void_p, c_uint32, c_size_t]),
+    "mi_mls_bank_set_state": (c_int, [c_void_p, c_uint32, c_uint64]),
+    "mi_mls_bank_set_amplitude": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_mls_bank_set_offset": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_mls_bank_needs_update": (c_int, [c_void_p, c_uint32, POINTER(c_int)]),
+    "mi_mls_bank_update_settings": (c_int, [c_void_p, c_void_p]),
+    "mi_mls_bank_maximum_number_of_bits": (c_int, [c_void_p, POINTER(c_size_t)]),
+    "mi_mls_bank_get_period": (c_int, [c_void_p, c_uint32, POINTER(c_uint64)]),
+    "mi_mls_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_uint32, c_void_p]),
+    "mi_mls_bank_reserve": (c_int, [c_void_p, c_size_t]),
+    "mi_mls_bank_get_settings": (c_int, [c_void_p, c_uint32, POINTER(MlsSettings)]),
+    "mi_mls_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(c_uint64), c_void_p]),
     "mi_delay_bank_create": (c_int, [POINTER(c_void_p), c_uint32, c_size_t]),
     "mi_delay_bank_destroy": (c_int, [c_void_p]),
     "mi_delay_bank_set_delay": (c_int, [c_void_p, c_uint32, c_size_t]),

@@ -768,6 +768,134 @@ class OscillatorBank:
             pass
 
 
+class LCGBank:
+    """`channels` x lsp::dspu::LCG (mi_lcg_bank_*): white noise of four distributions; the Randomizers live on the device."""
+    OVERWRITE, ADD, MUL = 0, 1, 2
+    UNIFORM, EXPONENTIAL, TRIANGULAR, GAUSSIAN = 0, 1, 2, 3
+    UNSET = 0xFFFFFFFF
+
+    def __init__(self, channels):
+        h = c_void_p()
+        check(lib.mi_lcg_bank_create(byref(h), channels))
+        self.handle, self.channels = h, channels
+
+    def init(self, channel, seed=None):
+        """init(seed); without a seed the argument-less init(): the host clock."""
+        if seed is None:
+            check(lib.mi_lcg_bank_init_time(self.handle, channel))
+        else:
+            check(lib.mi_lcg_bank_init(self.handle, channel, int(seed) & 0xFFFFFFFF))
+
+    def set_distribution(self, channel, distribution):
+        check(lib.mi_lcg_bank_set_distribution(self.handle, channel, distribution))
+
+    def set_amplitude(self, channel, amplitude):
+        check(lib.mi_lcg_bank_set_amplitude(self.handle, channel, amplitude))
+
+    def set_offset(self, channel, offset):
+        check(lib.mi_lcg_bank_set_offset(self.handle, channel, offset))
+
+    def process(self, dst, count, src=None, op=0, dst_stride=None, src_stride=None, stream=None):
+        """process_overwrite / process_add / process_mul by `op`; dst may be src (same stride)."""
+        check(lib.mi_lcg_bank_process(self.handle, _opt(dst), _opt(src), count, count if dst_stride is None else dst_stride,
+                                      count if src_stride is None else src_stride, op, _stream(stream)))
+
+    def get_state(self, channel, stream=None):
+        from .capi import LcgState
+        s = LcgState()
+        check(lib.mi_lcg_bank_get_state(self.handle, channel, byref(s), _stream(stream)))
+        return {"last": list(s.last), "mul1": list(s.mul1), "mul2": list(s.mul2), "add": list(s.add), "buf_id": s.buf_id}
+
+    def set_state(self, channel, last, mul1, mul2, add, buf_id, stream=None):
+        from .capi import LcgState
+        s = LcgState()
+        for k in range(4):
+            s.last[k], s.mul1[k], s.mul2[k], s.add[k] = int(last[k]), int(mul1[k]), int(mul2[k]), int(add[k])
+        s.buf_id = int(buf_id) & 0xFFFFFFFF
+        check(lib.mi_lcg_bank_set_state(self.handle, channel, byref(s), _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            lib.mi_lcg_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MLSBank:
+    """`channels` x lsp::dspu::MLS (mi_mls_bank_*): maximum-length sequences of a register of 1 .. 64 bits; nState on the device."""
+    OVERWRITE, ADD, MUL = 0, 1, 2
+
+    def __init__(self, channels):
+        h = c_void_p()
+        check(lib.mi_mls_bank_create(byref(h), channels))
+        self.handle, self.channels = h, channels
+
+    def set_n_bits(self, channel, n_bits):
+        check(lib.mi_mls_bank_set_n_bits(self.handle, channel, n_bits))
+
+    def set_state(self, channel, state):
+        check(lib.mi_mls_bank_set_state(self.handle, channel, int(state) & 0xFFFFFFFFFFFFFFFF))
+
+    def set_amplitude(self, channel, amplitude):
+        check(lib.mi_mls_bank_set_amplitude(self.handle, channel, amplitude))
+
+    def set_offset(self, channel, offset):
+        check(lib.mi_mls_bank_set_offset(self.handle, channel, offset))
+
+    def needs_update(self, channel):
+        v = c_int()
+        check(lib.mi_mls_bank_needs_update(self.handle, channel, byref(v)))
+        return bool(v.value)
+
+    def update_settings(self, stream=None):
+        check(lib.mi_mls_bank_update_settings(self.handle, _stream(stream)))
+
+    def maximum_number_of_bits(self):
+        v = ctypes.c_size_t()
+        check(lib.mi_mls_bank_maximum_number_of_bits(self.handle, byref(v)))
+        return v.value
+
+    def get_period(self, channel):
+        v = ctypes.c_uint64()
+        check(lib.mi_mls_bank_get_period(self.handle, channel, byref(v)))
+        return v.value
+
+    def process(self, dst, count, src=None, op=0, dst_stride=None, src_stride=None, stream=None):
+        """process_overwrite / process_add / process_mul by `op`; dst may be src (same stride)."""
+        check(lib.mi_mls_bank_process(self.handle, _opt(dst), _opt(src), count, count if dst_stride is None else dst_stride,
+                                      count if src_stride is None else src_stride, op, _stream(stream)))
+
+    def reserve(self, count):
+        check(lib.mi_mls_bank_reserve(self.handle, count))
+
+    def get_settings(self, channel):
+        from .capi import MlsSettings
+        s = MlsSettings()
+        check(lib.mi_mls_bank_get_settings(self.handle, channel, byref(s)))
+        return s
+
+    def get_state(self, channel, stream=None):
+        v = ctypes.c_uint64()
+        check(lib.mi_mls_bank_get_state(self.handle, channel, byref(v), _stream(stream)))
+        return v.value
+
+    def close(self):
+        if self.handle:
+            lib.mi_mls_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class RingBank:
     """`channels` x lsp::dspu::RingBuffer on the device."""
 
