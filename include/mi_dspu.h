@@ -2044,6 +2044,67 @@ int mi_mls_bank_get_settings(const mi_mls_bank_t *bank, uint32_t channel, mi_mls
 int mi_mls_bank_get_state(mi_mls_bank_t *bank, uint32_t channel, uint64_t *state, void *stream);
 
 /*
+ * mi_velvet_bank: `channels` x lsp::dspu::Velvet (noise/Velvet.h, src/main/noise/Velvet.cpp): sparse-impulse noise over a
+ * Randomizer and an MLS per channel.  process() is as for the two banks above, with what Velvet itself makes of a call:
+ *   - overwrite, and add with src == NULL, are ONE segment of `count` samples (do_process(dst, count));
+ *   - add and mul with a source cut the call into segments of 256 samples (BUF_LIM_SIZE), each of which starts its window scan
+ *     anew: a call is not the sum of shorter calls;
+ *   - mul with src == NULL zero-fills dst and draws nothing: no state word changes, and a state given by init / set_state stays
+ *     pending.  (So src == NULL with add or mul is defined here and is not MI_EINVAL.)
+ * How many draws a segment takes depends on the draws (the draw that ends a segment is consumed; ARN's spike count is data
+ * dependent; the MLS advances by the number of spikes), so the host cannot follow either state: Randomizer and MLS live on the
+ * device, the kernel writes them back, nothing is read back and a call can be captured; a replay goes on from the device's state.
+ * A wave per channel runs the four generator chains in chunks into a ring of raw draws in LDS and interprets them: 60 windows
+ * (OVN, OVNA) or 64 steps (ARN) at a time, a ballot finds the draw that ends the segment, and of two windows that hit one sample
+ * the one with the higher scan index wins, as the later write does in the reference.  Every sample and every state word has the
+ * reference's bits (fAmplitude and fOffset are applied as mul_k2 and add_k2: two roundings).
+ * init(channel, randseed, mls_n_bits, mls_seed) is Velvet::init: Randomizer::init(randseed), then MLS::set_n_bits and
+ * MLS::set_state with their "equal to the current value: nothing happens" rule (MLS.cpp:114-130) against the nState that the
+ * device holds -- the pending init travels in the channel's record and the kernel applies it --, and update_settings() runs
+ * lazily before the first MLS spike (mask, a zero state becomes all ones), so bSync is part of the state that comes back.
+ * Settings and pending states travel with the next process() that is ISSUED, as for mi_lcg_bank.
+ * Defined where the reference is not:
+ *   - a channel that was never init()ed has nBufID == size_t(-1) (vRandom[-1] there): process is MI_ESTATE, for every type and
+ *     core (mul with src == NULL, which draws nothing, included: one rule);
+ *   - count == 0 succeeds and changes nothing;
+ *   - count > 2^24 is MI_EINVAL: beyond it float(idx) is no longer exact and the reference's output degenerates;
+ *   - a window width that is not finite is MI_EINVAL at the setter (a NaN compares false in lsp_max; an infinite width makes
+ *     0 * inf, whose conversion to size_t is undefined);
+ *   - a float-to-index conversion whose value is out of range (or NaN) saturates, which ends the segment;
+ *   - a velvet type outside the enum is the reference's default: branch (zero fill, then amplitude and offset), a core outside
+ *     the enum is its default: too (the LCG core); the setters take them.
+ */
+typedef struct mi_velvet_bank mi_velvet_bank_t;
+enum { MI_VN_CORE_MLS, MI_VN_CORE_LCG };                                                    /* vn_core_t, Velvet.h */
+enum { MI_VN_VELVET_OVN, MI_VN_VELVET_OVNA, MI_VN_VELVET_ARN, MI_VN_VELVET_TRN };           /* vn_velvet_type_t */
+#define MI_VN_MAX_COUNT ((size_t)1 << 24)
+/* sRandomizer and sMLS of one Velvet.  mls.amplitude and mls.offset are 1 and 0, as construct() and both init() leave them */
+typedef struct { mi_lcg_state_t rand; uint32_t pad; mi_mls_settings_t mls; } mi_velvet_state_t;
+int mi_velvet_bank_create(mi_velvet_bank_t **bank, uint32_t channels);                      /* construct() */
+int mi_velvet_bank_destroy(mi_velvet_bank_t *bank);
+/* mls_n_bits is Velvet::init's uint8_t mlsnbits: its low 8 bits count */
+int mi_velvet_bank_init(mi_velvet_bank_t *bank, uint32_t channel, uint32_t randseed, uint32_t mls_n_bits, uint64_t mls_seed);
+int mi_velvet_bank_init_time(mi_velvet_bank_t *bank, uint32_t channel);     /* init(): the seed is the host clock; the MLS keeps what it has */
+int mi_velvet_bank_set_core_type(mi_velvet_bank_t *bank, uint32_t channel, uint32_t core);
+int mi_velvet_bank_set_velvet_type(mi_velvet_bank_t *bank, uint32_t channel, uint32_t type);
+int mi_velvet_bank_set_velvet_window_width(mi_velvet_bank_t *bank, uint32_t channel, float width);     /* clamped up to 2.0f */
+int mi_velvet_bank_set_delta_value(mi_velvet_bank_t *bank, uint32_t channel, float delta);             /* clamped to 0 .. 1 */
+int mi_velvet_bank_set_crush_probability(mi_velvet_bank_t *bank, uint32_t channel, float prob);        /* clamped to 0 .. 1 */
+int mi_velvet_bank_set_amplitude(mi_velvet_bank_t *bank, uint32_t channel, float amplitude);
+int mi_velvet_bank_set_offset(mi_velvet_bank_t *bank, uint32_t channel, float offset);
+int mi_velvet_bank_set_crush(mi_velvet_bank_t *bank, uint32_t channel, int crush);
+int mi_velvet_bank_process(mi_velvet_bank_t *bank, float *dst, const float *src, size_t count, size_t dst_stride, size_t src_stride,
+                           uint32_t op, void *stream);
+/* Nothing of the bank depends on count (the MLS tables are the device's): checks count, as mi_mls_bank_reserve does */
+int mi_velvet_bank_reserve(mi_velvet_bank_t *bank, size_t count);
+/* One channel's Randomizer and MLS as the device holds them (with a pending init or set_state applied), read with a synchronised
+ * copy and given to the next launch: MI_ESTATE on a capturing stream.  set_state takes rand.buf_id 0 .. 3 or MI_LCG_UNSET and the
+ * MLS members as they stand: n_bits, state and sync are the state, the masks follow feedback_bit (the width of the last
+ * update_settings() - 1; all masks 0: never updated). */
+int mi_velvet_bank_get_state(mi_velvet_bank_t *bank, uint32_t channel, mi_velvet_state_t *state, void *stream);
+int mi_velvet_bank_set_state(mi_velvet_bank_t *bank, uint32_t channel, const mi_velvet_state_t *state, void *stream);
+
+/*
  * Host-only introspection of the per-section device table (no GPU needed): the
  * chunk-parallel form of the TDF-II section used by the kernel.
  * variant 0 = 16-sample chunks (calls longer than 2048 samples), 1 = 8-sample

@@ -252,6 +252,11 @@ class MlsSettings(ctypes.Structure):
                [("amplitude", c_float), ("offset", c_float), ("sync", c_uint32), ("pad", c_uint32)]
 
 
+class VelvetState(ctypes.Structure):
+    """mi_velvet_state_t: sRandomizer and sMLS of one lsp::dspu::Velvet."""
+    _fields_ = [("rand", LcgState), ("pad", c_uint32), ("mls", MlsSettings)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/mi_dspu.h must be listed here
 # (tests/test_abi.py parses the header and checks both directions).
 PROTOTYPES = {
@@ -733,6 +738,22 @@ PROTOTYPES = {
     "mi_oscillator_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(OscillatorState), c_void_p]),
     "mi_oscillator_bank_get_periods": (c_int, [c_void_p, c_uint32, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_oscillator_bank_synth_rows": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_size_t)]),
+    "mi_velvet_bank_create": (c_int, [POINTER(c_void_p), c_uint32]),
+    "mi_velvet_bank_destroy": (c_int, [c_void_p]),
+    "mi_velvet_bank_init": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32, c_uint64]),
+    "mi_velvet_bank_init_time": (c_int, [c_void_p, c_uint32]),
+    "mi_velvet_bank_set_core_type": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_velvet_bank_set_velvet_type": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_velvet_bank_set_velvet_window_width": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_velvet_bank_set_delta_value": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_velvet_bank_set_crush_probability": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_velvet_bank_set_amplitude": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_velvet_bank_set_offset": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_velvet_bank_set_crush": (c_int, [c_void_p, c_uint32, c_int]),
+    "mi_velvet_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_uint32, c_void_p]),
+    "mi_velvet_bank_reserve": (c_int, [c_void_p, c_size_t]),
+    "mi_velvet_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(VelvetState), c_void_p]),
+    "mi_velvet_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(VelvetState), c_void_p]),
     "mi_lcg_seed_words": (c_int, [c_uint32, POINTER(LcgState)]),
     "mi_lcg_bank_create": (c_int, [POINTER(c_void_p), c_uint32]),
     "mi_lcg_bank_destroy": (c_int, [c_void_p]),

@@ -273,8 +273,12 @@ namespace
             params[ch].known = 0;
         }
     }
+} // namespace
 
-    // the tables of all 64 register widths on the current device: made at the first call, kept for the life of the process
+namespace mi_mls
+{
+    // the tables of all 64 register widths on the current device: made at the first call, kept for the life of the process (the
+    // velvet bank, csrc/velvet.hip, uses them too)
     int device_tables(const uint64_t **tables)
     {
         static std::mutex lock;
@@ -300,7 +304,8 @@ namespace
         *tables = of_device[dev];
         return MI_OK;
     }
-} // namespace
+} // namespace mi_mls
+using mi_mls::device_tables;
 
 struct mi_lcg_bank : mi_bank::tables<lcg_params, lcg_state>
 {

@@ -70,6 +70,8 @@ namespace lsp
                 void process_overwrite(float *dst, size_t count);
 
                 void dump(IStateDumper *v) const;
+
+            friend class Velvet;
         };
     }
 }

@@ -65,6 +65,7 @@ namespace lsp
                 void dump(IStateDumper *v) const;
 
             friend class LCG;
+            friend class Velvet;
         };
     }
 }

@@ -826,6 +826,81 @@ class LCGBank:
             pass
 
 
+class VelvetBank:
+    """`channels` x lsp::dspu::Velvet (mi_velvet_bank_*): sparse-impulse noise; Randomizer and MLS of a channel live on the device."""
+    OVERWRITE, ADD, MUL = 0, 1, 2
+    CORE_MLS, CORE_LCG = 0, 1
+    OVN, OVNA, ARN, TRN = 0, 1, 2, 3
+    UNSET = 0xFFFFFFFF
+    MAX_COUNT = 1 << 24
+
+    def __init__(self, channels):
+        h = c_void_p()
+        check(lib.mi_velvet_bank_create(byref(h), channels))
+        self.handle, self.channels = h, channels
+
+    def init(self, channel, randseed=None, mls_n_bits=64, mls_seed=0):
+        """init(randseed, mlsnbits, mlsseed); without a seed the argument-less init(): the host clock, and the MLS keeps what it has."""
+        if randseed is None:
+            check(lib.mi_velvet_bank_init_time(self.handle, channel))
+        else:
+            check(lib.mi_velvet_bank_init(self.handle, channel, int(randseed) & 0xFFFFFFFF, int(mls_n_bits) & 0xFF,
+                                          int(mls_seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def set_core_type(self, channel, core):
+        check(lib.mi_velvet_bank_set_core_type(self.handle, channel, core))
+
+    def set_velvet_type(self, channel, type_):
+        check(lib.mi_velvet_bank_set_velvet_type(self.handle, channel, type_))
+
+    def set_velvet_window_width(self, channel, width):
+        check(lib.mi_velvet_bank_set_velvet_window_width(self.handle, channel, width))
+
+    def set_delta_value(self, channel, delta):
+        check(lib.mi_velvet_bank_set_delta_value(self.handle, channel, delta))
+
+    def set_crush_probability(self, channel, prob):
+        check(lib.mi_velvet_bank_set_crush_probability(self.handle, channel, prob))
+
+    def set_amplitude(self, channel, amplitude):
+        check(lib.mi_velvet_bank_set_amplitude(self.handle, channel, amplitude))
+
+    def set_offset(self, channel, offset):
+        check(lib.mi_velvet_bank_set_offset(self.handle, channel, offset))
+
+    def set_crush(self, channel, crush):
+        check(lib.mi_velvet_bank_set_crush(self.handle, channel, int(bool(crush))))
+
+    def process(self, dst, count, src=None, op=0, dst_stride=None, src_stride=None, stream=None):
+        """process_overwrite / process_add / process_mul by `op`; src may be None with add (one segment) and mul (zero fill)."""
+        check(lib.mi_velvet_bank_process(self.handle, _opt(dst), _opt(src), count, count if dst_stride is None else dst_stride,
+                                         count if src_stride is None else src_stride, op, _stream(stream)))
+
+    def reserve(self, count):
+        check(lib.mi_velvet_bank_reserve(self.handle, count))
+
+    def get_state(self, channel, stream=None):
+        """The channel's VelvetState (capi): .rand as LcgState, .mls as MlsSettings."""
+        from .capi import VelvetState
+        s = VelvetState()
+        check(lib.mi_velvet_bank_get_state(self.handle, channel, byref(s), _stream(stream)))
+        return s
+
+    def set_state(self, channel, state, stream=None):
+        check(lib.mi_velvet_bank_set_state(self.handle, channel, byref(state), _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            lib.mi_velvet_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class MLSBank:
     """`channels` x lsp::dspu::MLS (mi_mls_bank_*): maximum-length sequences of a register of 1 .. 64 bits; nState on the device."""
     OVERWRITE, ADD, MUL = 0, 1, 2
