@@ -1991,6 +1991,16 @@ int mi_lcg_bank_process(mi_lcg_bank_t *bank, float *dst, const float *src, size_
  * set_state takes buf_id 0 .. 3, or MI_LCG_UNSET for a channel as construct() leaves it. */
 int mi_lcg_bank_get_state(mi_lcg_bank_t *bank, uint32_t channel, mi_lcg_state_t *state, void *stream);
 int mi_lcg_bank_set_state(mi_lcg_bank_t *bank, uint32_t channel, const mi_lcg_state_t *state, void *stream);
+/* As mi_biquad_bank_set_row_enabled: a channel that is switched off is what a caller gets by not calling process() on that object.
+ * Its row is not written, its Randomizer does not move, and a state given by init / set_state stays pending until the row next
+ * runs; it need not have been init()ed.  Every channel is on after create(); a bank with no channel on launches nothing.  The
+ * same for mi_mls_bank (a pending update_settings() waits too: needs_update, get_state and get_settings stay exact) and
+ * mi_velvet_bank. */
+int mi_lcg_bank_set_row_enabled(mi_lcg_bank_t *bank, uint32_t channel, int enabled);
+/* What the next process() would send to the device first -- changed settings, given states; for mi_mls_bank the update_settings()
+ * of the channels that are switched on -- goes now: outside a capture.  A process() after it can be captured.  The same for
+ * mi_mls_bank, mi_velvet_bank and mi_spectral_tilt_bank. */
+int mi_lcg_bank_commit(mi_lcg_bank_t *bank, void *stream);
 
 /*
  * mi_mls_bank: `channels` x lsp::dspu::MLS (noise/MLS.h, src/main/noise/MLS.cpp) with mls_t = uint64_t, the reference's LP64 build.
@@ -2042,6 +2052,8 @@ int mi_mls_bank_get_settings(const mi_mls_bank_t *bank, uint32_t channel, mi_mls
  * speak of the calls that were issued, not of the replays; a set_state or set_n_bits after a capture reaches the device with the
  * next process() that is issued, not with a replay. */
 int mi_mls_bank_get_state(mi_mls_bank_t *bank, uint32_t channel, uint64_t *state, void *stream);
+int mi_mls_bank_set_row_enabled(mi_mls_bank_t *bank, uint32_t channel, int enabled);        /* see mi_lcg_bank_set_row_enabled */
+int mi_mls_bank_commit(mi_mls_bank_t *bank, void *stream);                                  /* see mi_lcg_bank_commit */
 
 /*
  * mi_velvet_bank: `channels` x lsp::dspu::Velvet (noise/Velvet.h, src/main/noise/Velvet.cpp): sparse-impulse noise over a
@@ -2103,6 +2115,200 @@ int mi_velvet_bank_reserve(mi_velvet_bank_t *bank, size_t count);
  * update_settings() - 1; all masks 0: never updated). */
 int mi_velvet_bank_get_state(mi_velvet_bank_t *bank, uint32_t channel, mi_velvet_state_t *state, void *stream);
 int mi_velvet_bank_set_state(mi_velvet_bank_t *bank, uint32_t channel, const mi_velvet_state_t *state, void *stream);
+int mi_velvet_bank_set_row_enabled(mi_velvet_bank_t *bank, uint32_t channel, int enabled);  /* see mi_lcg_bank_set_row_enabled */
+int mi_velvet_bank_commit(mi_velvet_bank_t *bank, void *stream);                            /* see mi_lcg_bank_commit */
+/* An overwrite cut into segments of 256 samples (BUF_LIM_SIZE), each of which starts its window scan anew: what a caller's loop
+ * of process_overwrite(tmp, <= 256) over a longer row makes (NoiseGenerator's process_add / process_mul with a source do this,
+ * Generator.cpp), in one launch.  Everything else is as for mi_velvet_bank_process with MI_OSC_OVERWRITE. */
+int mi_velvet_bank_process_segmented(mi_velvet_bank_t *bank, float *dst, size_t count, size_t dst_stride, void *stream);
+
+/* ---- spectral tilt bank and noise generator bank (coloured noise) ------------------------------------------------------------ */
+/*
+ * mi_spectral_tilt_bank: `channels` x lsp::dspu::SpectralTilt (filters/SpectralTilt.h, src/main/filters/SpectralTilt.cpp): a
+ * magnitude response that goes like f^slope between two frequencies, made of `order` exponentially spaced bilinear pole / zero
+ * pairs joined two by two into up to 64 biquads.  The design is the host's: mi_spectral_tilt_settings_t holds the members of one
+ * SpectralTilt and the sections of its sFilter, and mi_spectral_tilt_settings_update is update_settings() line for line, with the
+ * reference's operand types (what it evaluates in double is evaluated in double), quirks included:
+ *   - an odd order is raised to the next even one, then clamped to 128;
+ *   - set_frequency_range() swaps its arguments when upper > lower -- the wrong way round --, and update_settings() then falls
+ *     back to 0.1 Hz .. 20 kHz; a frequency at or above Nyquist overwrites the member with its default;
+ *   - MI_STLT_SLOPE_UNIT_NONE or a slope of zero sets bBypass and leaves the sections of the last design where they are: the
+ *     freq_chart of a bypassed tilt reports that stale cascade;
+ *   - every new design clears the filter memory (sFilter.end(true));
+ *   - order 0 designs no section (the spacing ratio is powf(u / l, 1 / float(2^64 - 1))): process copies.
+ * dsp::bilinear_transform_x1 is lsp-dsp-lib's; the formulas of Filter::bilinear_transform (Filter.cpp:2225-2262) in float stand
+ * for it, as in mi_dynfilter_*.
+ * The cascade runs on a mi_biquad_bank of 64 sections that the bank owns: exact or fast as that bank (the process-wide default at
+ * create(), mi_spectral_tilt_bank_set_exact).  process(dst, src, count, dst_stride, src_stride, op, stream) is the reference's three
+ * entries, whose second operand is dst itself:
+ *   MI_OSC_OVERWRITE  dst = filter(src); src == NULL: zero fill; a bypassed channel: copy
+ *   MI_OSC_ADD        dst = dst + filter(src); src == NULL: nothing; a bypassed channel: dst += src
+ *   MI_OSC_MUL        dst = dst * filter(src); src == NULL: zero fill; a bypassed channel: dst *= src
+ * dst may be src (same stride).  Add and mul filter into scratch rows of the bank (reserve(count) makes them, outside a capture)
+ * and a second launch combines.  Bypassed and filtering channels run side by side.  update_settings() of the channels that are
+ * switched on opens every process (count == 0 succeeds and does nothing at all); new sections and modes go to the device outside a
+ * capture only: call mi_spectral_tilt_bank_update_settings first.
+ */
+#define MI_STLT_MAX_SECTIONS 64u
+enum { MI_STLT_SLOPE_UNIT_NEPER_PER_NEPER, MI_STLT_SLOPE_UNIT_DB_PER_OCTAVE, MI_STLT_SLOPE_UNIT_DB_PER_DECADE, MI_STLT_SLOPE_UNIT_NONE,
+       MI_STLT_SLOPE_UNIT_MAX };                                                            /* stlt_slope_unit_t */
+enum { MI_STLT_NORM_AT_DC, MI_STLT_NORM_AT_20_HZ, MI_STLT_NORM_AT_1_KHZ, MI_STLT_NORM_AT_20_KHZ, MI_STLT_NORM_AT_NYQUIST, MI_STLT_NORM_AUTO,
+       MI_STLT_NORM_NONE, MI_STLT_NORM_MAX };                                               /* stlt_norm_t */
+typedef struct mi_spectral_tilt_settings
+{
+    uint64_t        order;                                  /* nOrder */
+    uint64_t        sample_rate;                            /* nSampleRate; 2^64 - 1 (size_t(-1)) after construct() */
+    uint32_t        slope_unit, norm;                       /* enSlopeUnit, enNorm */
+    float           slope_val, slope_nep_nep;               /* fSlopeVal, fSlopeNepNep */
+    float           lower_frequency, upper_frequency;
+    uint32_t        bypass, sync;                           /* bBypass, bSync */
+    uint32_t        n_sections, pad;                        /* sFilter: the sections of the last design */
+    mi_biquad_x1_t  sections[MI_STLT_MAX_SECTIONS];
+} mi_spectral_tilt_settings_t;
+/* construct(), the setters and update_settings() on a mi_spectral_tilt_settings_t (host only, no device).  *designed (may be
+ * NULL) is set when the sections were made anew: whoever runs them clears the filter memory.  freq_chart: both forms by the
+ * pointers given (re and im, or c with re and im interleaved, or both); it does not run update first. */
+int mi_spectral_tilt_settings_init(mi_spectral_tilt_settings_t *s);
+int mi_spectral_tilt_settings_set_order(mi_spectral_tilt_settings_t *s, uint64_t order);
+int mi_spectral_tilt_settings_set_slope(mi_spectral_tilt_settings_t *s, float slope, uint32_t unit);
+int mi_spectral_tilt_settings_set_norm(mi_spectral_tilt_settings_t *s, uint32_t norm);
+int mi_spectral_tilt_settings_set_lower_frequency(mi_spectral_tilt_settings_t *s, float lower);
+int mi_spectral_tilt_settings_set_upper_frequency(mi_spectral_tilt_settings_t *s, float upper);
+int mi_spectral_tilt_settings_set_frequency_range(mi_spectral_tilt_settings_t *s, float lower, float upper);
+int mi_spectral_tilt_settings_set_sample_rate(mi_spectral_tilt_settings_t *s, uint64_t sample_rate);
+int mi_spectral_tilt_settings_update(mi_spectral_tilt_settings_t *s, int *designed);
+int mi_spectral_tilt_settings_freq_chart(const mi_spectral_tilt_settings_t *s, float *re, float *im, float *c, const float *f, size_t count);
+/* digital_biquad_gain() and normalise_digital_biquad() of one section with the members of *s (sample rate, norm, slope) */
+int mi_spectral_tilt_settings_section_gain(const mi_spectral_tilt_settings_t *s, const mi_biquad_x1_t *section, float frequency, float *gain);
+int mi_spectral_tilt_settings_normalise_section(const mi_spectral_tilt_settings_t *s, mi_biquad_x1_t *section);
+
+typedef struct mi_spectral_tilt_bank mi_spectral_tilt_bank_t;
+int mi_spectral_tilt_bank_create(mi_spectral_tilt_bank_t **bank, uint32_t channels);        /* construct() and init(); 1 .. 65535 channels */
+int mi_spectral_tilt_bank_destroy(mi_spectral_tilt_bank_t *bank);
+int mi_spectral_tilt_bank_set_order(mi_spectral_tilt_bank_t *bank, uint32_t channel, size_t order);
+int mi_spectral_tilt_bank_set_slope(mi_spectral_tilt_bank_t *bank, uint32_t channel, float slope, uint32_t unit);
+int mi_spectral_tilt_bank_set_norm(mi_spectral_tilt_bank_t *bank, uint32_t channel, uint32_t norm);
+int mi_spectral_tilt_bank_set_lower_frequency(mi_spectral_tilt_bank_t *bank, uint32_t channel, float lower);
+int mi_spectral_tilt_bank_set_upper_frequency(mi_spectral_tilt_bank_t *bank, uint32_t channel, float upper);
+int mi_spectral_tilt_bank_set_frequency_range(mi_spectral_tilt_bank_t *bank, uint32_t channel, float lower, float upper);
+int mi_spectral_tilt_bank_set_sample_rate(mi_spectral_tilt_bank_t *bank, uint32_t channel, size_t sample_rate);
+/* As mi_biquad_bank_set_row_enabled: a channel that is switched off is an object nobody calls: row, filter memory and a pending
+ * update_settings() stay.  A bank with no channel on launches nothing. */
+int mi_spectral_tilt_bank_set_row_enabled(mi_spectral_tilt_bank_t *bank, uint32_t channel, int enabled);
+int mi_spectral_tilt_bank_set_exact(mi_spectral_tilt_bank_t *bank, int on);                 /* mi_biquad_bank_set_exact of the cascade */
+/* update_settings() of EVERY channel; new sections and modes go to the device: outside a capture */
+int mi_spectral_tilt_bank_update_settings(mi_spectral_tilt_bank_t *bank, void *stream);
+/* ... and of the channels that are switched on only: what the next process() would do first (see mi_lcg_bank_commit) */
+int mi_spectral_tilt_bank_commit(mi_spectral_tilt_bank_t *bank, void *stream);
+int mi_spectral_tilt_bank_reserve(mi_spectral_tilt_bank_t *bank, size_t count, void *stream);
+int mi_spectral_tilt_bank_process(mi_spectral_tilt_bank_t *bank, float *dst, const float *src, size_t count, size_t dst_stride,
+                                  size_t src_stride, uint32_t op, void *stream);
+/* The sections as the last update_settings() of the channel left them (chains may be NULL: the count alone) */
+int mi_spectral_tilt_bank_get_chains(const mi_spectral_tilt_bank_t *bank, uint32_t channel, mi_biquad_x1_t *chains, uint32_t *count);
+int mi_spectral_tilt_bank_get_settings(const mi_spectral_tilt_bank_t *bank, uint32_t channel, mi_spectral_tilt_settings_t *settings);
+/* freq_chart() in both forms, on the host in float as complex_transfer_calc has it; update_settings() of the channel runs first,
+ * as in the reference, and a new design reaches the device with the next process() or update_settings() */
+int mi_spectral_tilt_bank_freq_chart(mi_spectral_tilt_bank_t *bank, uint32_t channel, float *re, float *im, const float *f, size_t count);
+int mi_spectral_tilt_bank_freq_chart_packed(mi_spectral_tilt_bank_t *bank, uint32_t channel, float *c, const float *f, size_t count);
+/* FilterBank::reset() of one channel's sFilter; channel = UINT32_MAX for all (not in the reference's class; for hosts that seek) */
+int mi_spectral_tilt_bank_reset(mi_spectral_tilt_bank_t *bank, uint32_t channel, void *stream);
+/* One channel's filter memory, [MI_STLT_MAX_SECTIONS][2] floats {d0, d1}: synchronised copies, MI_ESTATE on a capturing stream.
+ * The biquad bank's accessors move the whole bank's memory, so each call costs [channels][64][2] floats through the host (and
+ * set_state twice that): meant for single channels and tests, not for saving a large bank channel by channel.  The same holds for
+ * mi_noise_generator_bank_get_state / set_state, which go through these. */
+int mi_spectral_tilt_bank_get_state(mi_spectral_tilt_bank_t *bank, uint32_t channel, float *memory, void *stream);
+int mi_spectral_tilt_bank_set_state(mi_spectral_tilt_bank_t *bank, uint32_t channel, const float *memory, void *stream);
+
+/*
+ * mi_noise_generator_bank: `channels` x lsp::dspu::NoiseGenerator (noise/Generator.h, src/main/noise/Generator.cpp): an MLS, an
+ * LCG and a Velvet source behind one interface, coloured by a SpectralTilt.  The bank owns a mi_mls_bank, a mi_lcg_bank, a
+ * mi_velvet_bank and a mi_spectral_tilt_bank, each `channels` wide, and scratch rows.  Per call the channels are sorted by their
+ * generator: exactly those rows are switched on in each source bank, and only source banks with a row are launched; the tilt bank
+ * runs the coloured rows in place, white rows are switched off there.  The idle sources of a channel keep their state.
+ *   overwrite, and add with src == NULL   the sources write dst as one segment of count, the tilt colours dst in place: a white
+ *                                         overwrite costs exactly the source bank's launch
+ *   add, mul with a source                the reference draws into a temporary in chunks of <= 256, which LCG, MLS and the filter
+ *                                         cannot tell from one call and Velvet can (every chunk restarts its window scan): the
+ *                                         sources overwrite the scratch rows (Velvet: mi_velvet_bank_process_segmented), the tilt
+ *                                         colours them in place, and one launch forms dst = src op scratch.  dst may be src.
+ *   mul with src == NULL                  zero fill; nothing drawn, nothing filtered; update_settings() still runs
+ * update_settings() is the reference's: the UPD_* bits say what is applied again, amplitude and offset go to all three sources
+ * whenever anything is pending, set_generator raises nothing, the velvet core is MI_VN_CORE_LCG, the window width is
+ * sample_rate * width (seconds_to_samples), the colour filter runs from 10 Hz to 0.9 * 0.5 * sample_rate with MI_STLT_NORM_AUTO and
+ * its own update_settings() runs only when a coloured row is processed (or charted).
+ * Defined where the reference is not, or refused:
+ *   - process before init() of every channel is MI_ESTATE (the Randomizers index vRandom[-1] there);
+ *   - a coloured channel with sample rate 0 is MI_ESTATE at process (the reference designs NaN coefficients);
+ *   - count above MI_VN_MAX_COUNT is MI_EINVAL; count == 0 succeeds and changes nothing;
+ *   - a generator or colour outside its enum takes the default: branch (LCG; white);
+ *   - a velvet window width that is not finite is MI_EINVAL at the setter.
+ */
+typedef struct mi_noise_generator_bank mi_noise_generator_bank_t;
+enum { MI_NG_GEN_MLS, MI_NG_GEN_LCG, MI_NG_GEN_VELVET };                                    /* ng_generator_t */
+enum { MI_NG_COLOR_WHITE, MI_NG_COLOR_PINK, MI_NG_COLOR_RED, MI_NG_COLOR_BLUE, MI_NG_COLOR_VIOLET, MI_NG_COLOR_ARBITRARY };    /* ng_color_t */
+enum { MI_NG_UPD_MLS = 1, MI_NG_UPD_LCG = 2, MI_NG_UPD_VELVET = 4, MI_NG_UPD_COLOR = 8, MI_NG_UPD_OTHER = 16, MI_NG_UPD_ALL = 31 };
+/* The members of one NoiseGenerator beside its four units */
+typedef struct mi_noise_generator_settings
+{
+    uint64_t mls_seed, velvet_mls_seed, color_order, sample_rate, update;   /* sMLSParams.nSeed, sVelvetParams.nMLSseed, sColorParams.nOrder, nSampleRate, nUpdate */
+    uint32_t mls_n_bits, lcg_seed, lcg_distribution;
+    uint32_t velvet_rand_seed, velvet_mls_n_bits, velvet_core, velvet_type, velvet_crush;
+    float    velvet_window_width_s, velvet_arn_delta, velvet_crush_prob;
+    uint32_t color, color_slope_unit;
+    float    color_slope;
+    uint32_t generator, inited;                                             /* enGenerator; init() has run */
+    float    amplitude, offset;
+} mi_noise_generator_settings_t;
+/* The state of one NoiseGenerator's four units */
+typedef struct mi_noise_generator_state
+{
+    mi_lcg_state_t      lcg;
+    uint32_t            pad;
+    uint64_t            mls_state, mls_n_bits;              /* sMLS: nState and nBits */
+    mi_velvet_state_t   velvet;
+    float               filter[MI_STLT_MAX_SECTIONS * 2];   /* sColorFilter's memory */
+} mi_noise_generator_state_t;
+int mi_noise_generator_bank_create(mi_noise_generator_bank_t **bank, uint32_t channels);    /* construct() */
+int mi_noise_generator_bank_destroy(mi_noise_generator_bank_t *bank);
+/* init(mls_n_bits, mls_seed, lcg_seed, velvet_rand_seed, velvet_mls_n_bits, velvet_mls_seed); the bit counts are uint8_t there */
+int mi_noise_generator_bank_init(mi_noise_generator_bank_t *bank, uint32_t channel, uint32_t mls_n_bits, uint64_t mls_seed, uint32_t lcg_seed,
+                                 uint32_t velvet_rand_seed, uint32_t velvet_mls_n_bits, uint64_t velvet_mls_seed);
+int mi_noise_generator_bank_init_auto(mi_noise_generator_bank_t *bank, uint32_t channel);   /* init(): time seeds, MLS of 64 bits */
+int mi_noise_generator_bank_set_sample_rate(mi_noise_generator_bank_t *bank, uint32_t channel, size_t sample_rate);
+int mi_noise_generator_bank_set_mls_n_bits(mi_noise_generator_bank_t *bank, uint32_t channel, uint32_t n_bits);
+int mi_noise_generator_bank_set_mls_seed(mi_noise_generator_bank_t *bank, uint32_t channel, uint64_t seed);
+int mi_noise_generator_bank_set_lcg_distribution(mi_noise_generator_bank_t *bank, uint32_t channel, uint32_t distribution);
+int mi_noise_generator_bank_set_velvet_type(mi_noise_generator_bank_t *bank, uint32_t channel, uint32_t type);
+int mi_noise_generator_bank_set_velvet_window_width(mi_noise_generator_bank_t *bank, uint32_t channel, float seconds);
+int mi_noise_generator_bank_set_velvet_arn_delta(mi_noise_generator_bank_t *bank, uint32_t channel, float delta);
+int mi_noise_generator_bank_set_velvet_crush(mi_noise_generator_bank_t *bank, uint32_t channel, int crush);
+int mi_noise_generator_bank_set_velvet_crushing_probability(mi_noise_generator_bank_t *bank, uint32_t channel, float prob);
+int mi_noise_generator_bank_set_generator(mi_noise_generator_bank_t *bank, uint32_t channel, uint32_t generator);
+int mi_noise_generator_bank_set_noise_color(mi_noise_generator_bank_t *bank, uint32_t channel, uint32_t color);
+int mi_noise_generator_bank_set_coloring_order(mi_noise_generator_bank_t *bank, uint32_t channel, size_t order);
+int mi_noise_generator_bank_set_color_slope(mi_noise_generator_bank_t *bank, uint32_t channel, float slope, uint32_t unit);
+int mi_noise_generator_bank_set_amplitude(mi_noise_generator_bank_t *bank, uint32_t channel, float amplitude);
+int mi_noise_generator_bank_set_offset(mi_noise_generator_bank_t *bank, uint32_t channel, float offset);
+int mi_noise_generator_bank_set_exact(mi_noise_generator_bank_t *bank, int on);             /* the colour filter's arithmetic */
+/* NoiseGenerator::update_settings() of every channel (host only: it calls the units' setters), the rows sorted by generator and
+ * colour, and then what the units' next launches would send first goes to the device (mi_*_bank_commit): outside a capture.  The
+ * units' OWN update_settings() run for the rows that are switched on only -- an idle MLS and the colour filter of a white channel
+ * keep theirs pending, as in the reference, where nobody calls them.  After it (and reserve(count) for add and mul with a source)
+ * process can be captured. */
+int mi_noise_generator_bank_update_settings(mi_noise_generator_bank_t *bank, void *stream);
+int mi_noise_generator_bank_reserve(mi_noise_generator_bank_t *bank, size_t count, void *stream);
+int mi_noise_generator_bank_process(mi_noise_generator_bank_t *bank, float *dst, const float *src, size_t count, size_t dst_stride,
+                                    size_t src_stride, uint32_t op, void *stream);
+/* A white channel: re = 1, im = 0; a coloured one: the colour filter's chart (NoiseGenerator::freq_chart does not run the
+ * generator's own update_settings(), and neither do these) */
+int mi_noise_generator_bank_freq_chart(mi_noise_generator_bank_t *bank, uint32_t channel, float *re, float *im, const float *f, size_t count);
+int mi_noise_generator_bank_freq_chart_packed(mi_noise_generator_bank_t *bank, uint32_t channel, float *c, const float *f, size_t count);
+int mi_noise_generator_bank_get_settings(const mi_noise_generator_bank_t *bank, uint32_t channel, mi_noise_generator_settings_t *settings);
+int mi_noise_generator_bank_get_tilt_settings(const mi_noise_generator_bank_t *bank, uint32_t channel, mi_spectral_tilt_settings_t *settings);
+/* The four units' states with synchronised copies: MI_ESTATE on a capturing stream.  set_state gives the Randomizers and the
+ * filter memory as they stand and the MLS through set_n_bits / set_state (their "unchanged: nothing happens" rule holds). */
+int mi_noise_generator_bank_get_state(mi_noise_generator_bank_t *bank, uint32_t channel, mi_noise_generator_state_t *state, void *stream);
+int mi_noise_generator_bank_set_state(mi_noise_generator_bank_t *bank, uint32_t channel, const mi_noise_generator_state_t *state, void *stream);
 
 /*
  * Host-only introspection of the per-section device table (no GPU needed): the

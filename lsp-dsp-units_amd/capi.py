@@ -257,6 +257,29 @@ class VelvetState(ctypes.Structure):
     _fields_ = [("rand", LcgState), ("pad", c_uint32), ("mls", MlsSettings)]
 
 
+class SpectralTiltSettings(ctypes.Structure):
+    """mi_spectral_tilt_settings_t: the members of one lsp::dspu::SpectralTilt and the sections of its sFilter."""
+    _fields_ = [("order", c_uint64), ("sample_rate", c_uint64), ("slope_unit", c_uint32), ("norm", c_uint32),
+                ("slope_val", c_float), ("slope_nep_nep", c_float), ("lower_frequency", c_float), ("upper_frequency", c_float),
+                ("bypass", c_uint32), ("sync", c_uint32), ("n_sections", c_uint32), ("pad", c_uint32), ("sections", BiquadX1 * 64)]
+
+
+class NoiseGeneratorSettings(ctypes.Structure):
+    """mi_noise_generator_settings_t: the members of one lsp::dspu::NoiseGenerator beside its four units."""
+    _fields_ = [(n, c_uint64) for n in ("mls_seed", "velvet_mls_seed", "color_order", "sample_rate", "update")] + \
+               [(n, c_uint32) for n in ("mls_n_bits", "lcg_seed", "lcg_distribution", "velvet_rand_seed", "velvet_mls_n_bits", "velvet_core",
+                                        "velvet_type", "velvet_crush")] + \
+               [(n, c_float) for n in ("velvet_window_width_s", "velvet_arn_delta", "velvet_crush_prob")] + \
+               [("color", c_uint32), ("color_slope_unit", c_uint32), ("color_slope", c_float), ("generator", c_uint32), ("inited", c_uint32),
+                ("amplitude", c_float), ("offset", c_float)]
+
+
+class NoiseGeneratorState(ctypes.Structure):
+    """mi_noise_generator_state_t: the states of one NoiseGenerator's four units."""
+    _fields_ = [("lcg", LcgState), ("pad", c_uint32), ("mls_state", c_uint64), ("mls_n_bits", c_uint64), ("velvet", VelvetState),
+                ("filter", c_float * 128)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/mi_dspu.h must be listed here
 # (tests/test_abi.py parses the header and checks both directions).
 PROTOTYPES = {
@@ -754,6 +777,9 @@ PROTOTYPES = {
     "mi_velvet_bank_reserve": (c_int, [c_void_p, c_size_t]),
     "mi_velvet_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(VelvetState), c_void_p]),
     "mi_velvet_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(VelvetState), c_void_p]),
+    "mi_velvet_bank_set_row_enabled": (c_int, [c_void_p, c_uint32, c_int]),
+    "mi_velvet_bank_commit": (c_int, [c_void_p, c_void_p]),
+    "mi_velvet_bank_process_segmented": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
     "mi_lcg_seed_words": (c_int, [c_uint32, POINTER(LcgState)]),
     "mi_lcg_bank_create": (c_int, [POINTER(c_void_p), c_uint32]),
     "mi_lcg_bank_destroy": (c_int, [c_void_p]),
@@ -765,6 +791,8 @@ PROTOTYPES = {
     "mi_lcg_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_uint32, c_void_p]),
     "mi_lcg_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(LcgState), c_void_p]),
     "mi_lcg_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(LcgState), c_void_p]),
+    "mi_lcg_bank_set_row_enabled": (c_int, [c_void_p, c_uint32, c_int]),
+    "mi_lcg_bank_commit": (c_int, [c_void_p, c_void_p]),
     "mi_mls_settings_init": (c_int, [POINTER(MlsSettings)]),
     "mi_mls_settings_update": (c_int, [POINTER(MlsSettings)]),
     "mi_mls_tables": (c_int, [c_uint32, POINTER(c_uint64), POINTER(c_uint64)]),
@@ -783,6 +811,71 @@ PROTOTYPES = {
     "mi_mls_bank_reserve": (c_int, [c_void_p, c_size_t]),
     "mi_mls_bank_get_settings": (c_int, [c_void_p, c_uint32, POINTER(MlsSettings)]),
     "mi_mls_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(c_uint64), c_void_p]),
+    "mi_mls_bank_set_row_enabled": (c_int, [c_void_p, c_uint32, c_int]),
+    "mi_mls_bank_commit": (c_int, [c_void_p, c_void_p]),
+    "mi_spectral_tilt_settings_init": (c_int, [POINTER(SpectralTiltSettings)]),
+    "mi_spectral_tilt_settings_set_order": (c_int, [POINTER(SpectralTiltSettings), c_uint64]),
+    "mi_spectral_tilt_settings_set_slope": (c_int, [POINTER(SpectralTiltSettings), c_float, c_uint32]),
+    "mi_spectral_tilt_settings_set_norm": (c_int, [POINTER(SpectralTiltSettings), c_uint32]),
+    "mi_spectral_tilt_settings_set_lower_frequency": (c_int, [POINTER(SpectralTiltSettings), c_float]),
+    "mi_spectral_tilt_settings_set_upper_frequency": (c_int, [POINTER(SpectralTiltSettings), c_float]),
+    "mi_spectral_tilt_settings_set_frequency_range": (c_int, [POINTER(SpectralTiltSettings), c_float, c_float]),
+    "mi_spectral_tilt_settings_set_sample_rate": (c_int, [POINTER(SpectralTiltSettings), c_uint64]),
+    "mi_spectral_tilt_settings_update": (c_int, [POINTER(SpectralTiltSettings), POINTER(c_int)]),
+    "mi_spectral_tilt_settings_freq_chart": (c_int, [POINTER(SpectralTiltSettings), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "mi_spectral_tilt_settings_section_gain": (c_int, [POINTER(SpectralTiltSettings), POINTER(BiquadX1), c_float, POINTER(c_float)]),
+    "mi_spectral_tilt_settings_normalise_section": (c_int, [POINTER(SpectralTiltSettings), POINTER(BiquadX1)]),
+    "mi_spectral_tilt_bank_create": (c_int, [POINTER(c_void_p), c_uint32]),
+    "mi_spectral_tilt_bank_destroy": (c_int, [c_void_p]),
+    "mi_spectral_tilt_bank_set_order": (c_int, [c_void_p, c_uint32, c_size_t]),
+    "mi_spectral_tilt_bank_set_slope": (c_int, [c_void_p, c_uint32, c_float, c_uint32]),
+    "mi_spectral_tilt_bank_set_norm": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_spectral_tilt_bank_set_lower_frequency": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_spectral_tilt_bank_set_upper_frequency": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_spectral_tilt_bank_set_frequency_range": (c_int, [c_void_p, c_uint32, c_float, c_float]),
+    "mi_spectral_tilt_bank_set_sample_rate": (c_int, [c_void_p, c_uint32, c_size_t]),
+    "mi_spectral_tilt_bank_set_row_enabled": (c_int, [c_void_p, c_uint32, c_int]),
+    "mi_spectral_tilt_bank_set_exact": (c_int, [c_void_p, c_int]),
+    "mi_spectral_tilt_bank_update_settings": (c_int, [c_void_p, c_void_p]),
+    "mi_spectral_tilt_bank_commit": (c_int, [c_void_p, c_void_p]),
+    "mi_spectral_tilt_bank_reserve": (c_int, [c_void_p, c_size_t, c_void_p]),
+    "mi_spectral_tilt_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_uint32, c_void_p]),
+    "mi_spectral_tilt_bank_get_chains": (c_int, [c_void_p, c_uint32, POINTER(BiquadX1), POINTER(c_uint32)]),
+    "mi_spectral_tilt_bank_get_settings": (c_int, [c_void_p, c_uint32, POINTER(SpectralTiltSettings)]),
+    "mi_spectral_tilt_bank_freq_chart": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "mi_spectral_tilt_bank_freq_chart_packed": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p, c_size_t]),
+    "mi_spectral_tilt_bank_reset": (c_int, [c_void_p, c_uint32, c_void_p]),
+    "mi_spectral_tilt_bank_get_state": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p]),
+    "mi_spectral_tilt_bank_set_state": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p]),
+    "mi_noise_generator_bank_create": (c_int, [POINTER(c_void_p), c_uint32]),
+    "mi_noise_generator_bank_destroy": (c_int, [c_void_p]),
+    "mi_noise_generator_bank_init": (c_int, [c_void_p, c_uint32, c_uint32, c_uint64, c_uint32, c_uint32, c_uint32, c_uint64]),
+    "mi_noise_generator_bank_init_auto": (c_int, [c_void_p, c_uint32]),
+    "mi_noise_generator_bank_set_sample_rate": (c_int, [c_void_p, c_uint32, c_size_t]),
+    "mi_noise_generator_bank_set_mls_n_bits": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_noise_generator_bank_set_mls_seed": (c_int, [c_void_p, c_uint32, c_uint64]),
+    "mi_noise_generator_bank_set_lcg_distribution": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_noise_generator_bank_set_velvet_type": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_noise_generator_bank_set_velvet_window_width": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_noise_generator_bank_set_velvet_arn_delta": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_noise_generator_bank_set_velvet_crush": (c_int, [c_void_p, c_uint32, c_int]),
+    "mi_noise_generator_bank_set_velvet_crushing_probability": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_noise_generator_bank_set_generator": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_noise_generator_bank_set_noise_color": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_noise_generator_bank_set_coloring_order": (c_int, [c_void_p, c_uint32, c_size_t]),
+    "mi_noise_generator_bank_set_color_slope": (c_int, [c_void_p, c_uint32, c_float, c_uint32]),
+    "mi_noise_generator_bank_set_amplitude": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_noise_generator_bank_set_offset": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_noise_generator_bank_set_exact": (c_int, [c_void_p, c_int]),
+    "mi_noise_generator_bank_update_settings": (c_int, [c_void_p, c_void_p]),
+    "mi_noise_generator_bank_reserve": (c_int, [c_void_p, c_size_t, c_void_p]),
+    "mi_noise_generator_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_uint32, c_void_p]),
+    "mi_noise_generator_bank_freq_chart": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "mi_noise_generator_bank_freq_chart_packed": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p, c_size_t]),
+    "mi_noise_generator_bank_get_settings": (c_int, [c_void_p, c_uint32, POINTER(NoiseGeneratorSettings)]),
+    "mi_noise_generator_bank_get_tilt_settings": (c_int, [c_void_p, c_uint32, POINTER(SpectralTiltSettings)]),
+    "mi_noise_generator_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(NoiseGeneratorState), c_void_p]),
+    "mi_noise_generator_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(NoiseGeneratorState), c_void_p]),
     "mi_delay_bank_create": (c_int, [POINTER(c_void_p), c_uint32, c_size_t]),
     "mi_delay_bank_destroy": (c_int, [c_void_p]),
     "mi_delay_bank_set_delay": (c_int, [c_void_p, c_uint32, c_size_t]),

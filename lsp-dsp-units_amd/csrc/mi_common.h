@@ -130,6 +130,14 @@ namespace mi
     // blocks of the next launch when `left` are left: a run of K blocks is K + 1 units of work for the eight waves of
     // conv_frames_wave_kernel's workgroups, so a full launch takes 127 (128 units: sixteen rounds and no seventeenth for one wave)
     inline size_t conv_frames_chunk(size_t left) { return (left <= CONV_FRAMES_MAX) ? left : CONV_FRAMES_MAX - 1; }
+
+    // spectral_tilt.hip, for the noise generator bank too: dst = a OP b over `channels` rows of `count` samples (count != 0) in one
+    // launch; b is `filtered`, or `bypassed` where d_mode[ch] says so (channels whose mode is off are left out; d_mode == NULL: every
+    // channel takes `filtered`).  And a bank's scratch rows [channels][*stride], grown to hold `count` samples outside a capture.
+    int         rows_combine(float *dst, const float *a, const float *filtered, const float *bypassed, size_t dst_stride, size_t a_stride,
+                             size_t filtered_stride, size_t bypassed_stride, size_t count, uint32_t op, const uint32_t *d_mode,
+                             uint32_t channels, hipStream_t st);
+    int         scratch_reserve(const char *bank, float **d_scratch, size_t *stride, uint32_t channels, size_t count, hipStream_t st);
 } // namespace mi
 
 #if defined(__HIPCC__)

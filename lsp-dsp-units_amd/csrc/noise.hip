@@ -53,7 +53,8 @@ namespace
         uint32_t last[4], buf_id, known;                        // known: vLast and nBufID are these, not the device's
         uint32_t dist;
         float    amplitude, offset;
-        uint32_t pad[3];
+        uint32_t enabled;                                       // 0: the row is not written and vLast, nBufID and known stay
+        uint32_t pad[2];
     };
     struct lcg_state { uint32_t last[4], buf_id, pad[3]; };
     static_assert(sizeof(lcg_params) == 96 && sizeof(lcg_state) == 32, "16-byte multiples");
@@ -63,7 +64,8 @@ namespace
         uint64_t state;                                         // nState where known
         uint32_t known, table;                                  // table: the register width - 1
         float    high, low;                                     // fAmplitude + fOffset, -fAmplitude + fOffset
-        uint32_t pad[2];
+        uint32_t enabled;                                       // 0: the row is not written and nState and known stay
+        uint32_t pad;
     };
     struct mls_state { uint64_t state; };
     static_assert(sizeof(mls_params) == 32, "16-byte multiple");
@@ -147,11 +149,18 @@ namespace
 
         // wave 0, the producer's lane: channel ch0 + lane / 4, generator lane % 4
         const uint32_t pch = ch0 + (lane >> 2), g = lane & 3u;
-        const bool producer = wave == 0 && lane < 4 * LCG_GROUP && pch < channels;
+        // a channel that is switched off: its producer lanes and its transform wave do nothing and still reach every barrier; a
+        // workgroup with no channel switched on leaves as one (the four words are the same in every lane)
+        bool any = false;
+        for (uint32_t k = 0; k < LCG_GROUP; ++k)
+            any |= ch0 + k < channels && params[ch0 + k].enabled != 0;
+        if (!any)
+            return;
+        const bool producer = wave == 0 && lane < 4 * LCG_GROUP && pch < channels && params[pch].enabled != 0;
         uint32_t last = 0, mul1 = 0, mul2 = 0, add = 0, buf = 0, per = 1;
         // waves 1 .. LCG_GROUP, the transform: channel ch0 + wave - 1, uniform in the wave
         const uint32_t tch = ch0 + wave - 1;
-        const bool transform = wave != 0 && tch < channels;
+        const bool transform = wave != 0 && tch < channels && params[tch].enabled != 0;
         uint32_t dist = 0;
         float A = 0.0f, off = 0.0f;
         if (producer)
@@ -235,6 +244,8 @@ namespace
     {
         const uint32_t ch = blockIdx.y, lane = threadIdx.x & 63u;
         const mls_params P = params[ch];
+        if (!P.enabled)                                         // the whole workgroup: nobody is left waiting at a ballot
+            return;
         const uint64_t kept = state[ch].state;                  // read whether needed or not: beside the record, not behind it
         const uint64_t *table = tables + size_t(P.table) * MLS_TABLE_WORDS;
         // the lane's rows are those of its place in a tile, the same for every tile; M^1024 takes a tile's state to the next one's
@@ -265,6 +276,8 @@ namespace
     {
         const uint32_t ch = blockIdx.x, lane = threadIdx.x;
         const mls_params P = params[ch];
+        if (!P.enabled)
+            return;
         const uint64_t kept = state[ch].state;
         const uint64_t s = mi_mls::jump<COUNT_BITS>(tables + size_t(P.table) * MLS_TABLE_WORDS, P.known ? P.state : kept, count, 0, lane);
         if (lane == 0)
@@ -312,6 +325,7 @@ struct mi_lcg_bank : mi_bank::tables<lcg_params, lcg_state>
     std::vector<uint8_t> inited;                                // init() or set_state() has given the channel a nBufID
     uint32_t             uninited = 0;                          // channels without one
     bool                 any_known = false;                     // a record carries a state that no launch has taken yet
+    uint32_t             disabled = 0;                          // channels that are switched off
 };
 
 struct mi_mls_bank : mi_bank::tables<mls_params, mls_state>
@@ -322,6 +336,7 @@ struct mi_mls_bank : mi_bank::tables<mls_params, mls_state>
     const uint64_t         *d_tables = nullptr;                 // the device's, not the bank's
     bool                    touched = true;                     // a setter ran since the records were last made
     bool                    any_known = true;                   // a record carries a state that no launch has taken yet
+    uint32_t                disabled = 0;                       // channels that are switched off
 };
 
 namespace
@@ -371,7 +386,9 @@ namespace
         b->base[ch] = b->issued;
     }
 
-    int mls_update(mi_mls_bank *b, hipStream_t st)
+    // update_settings() of every channel, or (running: process() opens with it) of those that are switched on: nobody calls it
+    // on an object that is left out, whose bSync and amplitude wait for the call that takes it in again
+    int mls_update(mi_mls_bank *b, hipStream_t st, bool running = false)
     {
         if (!b->touched)                                        // a steady stream of calls: nothing to look at per channel
             return mi_bank::upload(*b, "mi_mls_bank", st);
@@ -380,6 +397,12 @@ namespace
         {
             mi_mls_settings_t &c = b->cfg[ch];
             mls_params p = b->params[ch];
+            if (running && !p.enabled)                          // what waits on it keeps the bank out of the steady path, nothing else does
+            {
+                const float high = c.amplitude + c.offset, low = -c.amplitude + c.offset;
+                b->touched |= c.sync != 0 || memcmp(&high, &p.high, sizeof(float)) != 0 || memcmp(&low, &p.low, sizeof(float)) != 0;
+                continue;
+            }
             if (c.sync)
             {
                 resolve(b, ch);
@@ -410,6 +433,7 @@ int mi_lcg_bank_create(mi_lcg_bank_t **bank, uint32_t channels)
     b->uninited = channels;
     lcg_params p = lcg_params();
     p.buf_id = MI_LCG_UNSET, p.dist = MI_LCG_UNIFORM, p.amplitude = 1.0f;       // construct(): Randomizer.cpp:69-80, LCG.cpp:38-43
+    p.enabled = 1;
     lcg_state s = lcg_state();
     s.buf_id = MI_LCG_UNSET;
     r = mi_bank::alloc(*b, "mi_lcg_bank_create", p, s);
@@ -494,7 +518,9 @@ int mi_lcg_bank_process(mi_lcg_bank_t *b, float *dst, const float *src, size_t c
     if (r != MI_OK || nothing)
         return r;
     for (uint32_t ch = 0; b->uninited != 0 && ch < b->channels; ++ch)
-        MI_REQUIRE(b->inited[ch], MI_ESTATE, "mi_lcg_bank_process: channel %u was never init()ed", ch);
+        MI_REQUIRE(b->inited[ch] || !b->params[ch].enabled, MI_ESTATE, "mi_lcg_bank_process: channel %u was never init()ed", ch);
+    if (b->disabled == b->channels)                             // nobody's process() is called
+        return MI_OK;
     hipStream_t st = mi::as_stream(stream);
     r = mi_bank::upload(*b, "mi_lcg_bank", st);
     if (r != MI_OK)
@@ -503,10 +529,29 @@ int mi_lcg_bank_process(mi_lcg_bank_t *b, float *dst, const float *src, size_t c
     const bool vec = rows_aligned(dst, src, dst_stride, src_stride, b->channels);
     NOISE_LAUNCH(lcg_kernel, LCG_BLOCK, op, vec, grid, st, dst, src, dst_stride, src_stride, uint32_t(count), b->d_params, b->d_state, b->channels);
     MI_HIP_CHECK(hipGetLastError());
+    bool left = false;
     for (uint32_t ch = 0; b->any_known && ch < b->channels; ++ch)  // as the kernel leaves the records
-        b->params[ch].known = 0;
-    b->any_known = false;
+        if (b->params[ch].enabled)
+            b->params[ch].known = 0;
+        else
+            left |= b->params[ch].known != 0;
+    b->any_known = left;
     return MI_OK;
+}
+
+int mi_lcg_bank_set_row_enabled(mi_lcg_bank_t *b, uint32_t channel, int enabled)
+{
+    LCG_CHANNEL("set_row_enabled");
+    const uint32_t on = enabled != 0;
+    if (p.enabled != on)
+        b->disabled += p.enabled - on, p.enabled = on, b->up.touch(channel);
+    return MI_OK;
+}
+
+int mi_lcg_bank_commit(mi_lcg_bank_t *b, void *stream)
+{
+    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_lcg_bank_commit: NULL bank");
+    return mi_bank::upload(*b, "mi_lcg_bank", mi::as_stream(stream));
 }
 
 int mi_lcg_bank_get_state(mi_lcg_bank_t *b, uint32_t channel, mi_lcg_state_t *state, void *stream)
@@ -560,7 +605,7 @@ int mi_mls_bank_create(mi_mls_bank_t **bank, uint32_t channels)
     b->cfg.assign(channels, fresh);
     b->base.assign(channels, 0);
     mls_params p = mls_params();
-    p.known = 1, p.table = MLS_MAX_BITS - 1, p.high = 1.0f, p.low = -1.0f;
+    p.known = 1, p.table = MLS_MAX_BITS - 1, p.high = 1.0f, p.low = -1.0f, p.enabled = 1;
     r = mi_bank::alloc(*b, "mi_mls_bank_create", p, mls_state{ 0 });
     if (r == MI_OK)
         r = device_tables(&b->d_tables);
@@ -627,6 +672,12 @@ int mi_mls_bank_update_settings(mi_mls_bank_t *b, void *stream)
     return mls_update(b, mi::as_stream(stream));
 }
 
+int mi_mls_bank_commit(mi_mls_bank_t *b, void *stream)
+{
+    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_mls_bank_commit: NULL bank");
+    return mls_update(b, mi::as_stream(stream), true);
+}
+
 int mi_mls_bank_maximum_number_of_bits(const mi_mls_bank_t *b, size_t *bits)
 {
     MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_mls_bank_maximum_number_of_bits: NULL bank");
@@ -652,7 +703,9 @@ int mi_mls_bank_process(mi_mls_bank_t *b, float *dst, const float *src, size_t c
     if (r != MI_OK || nothing)
         return r;
     hipStream_t st = mi::as_stream(stream);
-    r = mls_update(b, st);                                      // progress() opens with it, :211
+    if (b->disabled == b->channels)                             // nobody's process() is called
+        return MI_OK;
+    r = mls_update(b, st, true);                                // progress() opens with it, :211
     if (r != MI_OK)
         return r;
     const dim3 grid(uint32_t((count + MLS_TILE * MLS_SPAN - 1) / (MLS_TILE * MLS_SPAN)), b->channels);
@@ -661,10 +714,28 @@ int mi_mls_bank_process(mi_mls_bank_t *b, float *dst, const float *src, size_t c
     MI_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(mls_advance_kernel, dim3(b->channels), dim3(64), 0, st, b->d_params, b->d_state, uint32_t(count), b->d_tables);
     MI_HIP_CHECK(hipGetLastError());
+    bool left = false;
     for (uint32_t ch = 0; b->any_known && ch < b->channels; ++ch)  // as the advance kernel leaves the records
-        b->params[ch].known = 0;
-    b->any_known = false;
-    b->issued += count;                                         // every channel's nState is count samples on
+        if (b->params[ch].enabled)
+            b->params[ch].known = 0;
+        else
+            left |= b->params[ch].known != 0;
+    b->any_known = left;
+    b->issued += count;                                         // every channel's nState is count samples on ...
+    for (uint32_t ch = 0; b->disabled != 0 && ch < b->channels; ++ch)
+        if (!b->params[ch].enabled)
+            b->base[ch] += count;                               // ... but for those that stood still
+    return MI_OK;
+}
+
+int mi_mls_bank_set_row_enabled(mi_mls_bank_t *b, uint32_t channel, int enabled)
+{
+    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_mls_bank_set_row_enabled: NULL bank");
+    MI_REQUIRE(channel < b->channels, MI_EINVAL, "mi_mls_bank_set_row_enabled: channel %u out of range", channel);
+    mls_params &p = b->params[channel];
+    const uint32_t on = enabled != 0;
+    if (p.enabled != on)
+        b->disabled += p.enabled - on, p.enabled = on, b->up.touch(channel), b->touched = true;
     return MI_OK;
 }
 

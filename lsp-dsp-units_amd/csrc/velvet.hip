@@ -62,7 +62,8 @@ namespace
         uint32_t upd_bits, forced;                              // ... and forced: two pending inits differed, bSync whatever the device holds
         uint32_t core, type, crush;
         float    width, delta, prob, amplitude, offset;
-        uint32_t pad[2];
+        uint32_t enabled;                                       // 0: the row is not written, the state and what is pending stay
+        uint32_t pad;
     };
     struct velvet_state
     {
@@ -133,6 +134,8 @@ namespace
         __shared__ __attribute__((aligned(16))) float tile[VN_SEG];
         const uint32_t lane = threadIdx.x, ch = blockIdx.x, g = lane & 3u;
         const velvet_params P = params[ch];
+        if (!P.enabled)                                         // the workgroup is this one wave
+            return;
         const velvet_state S = state[ch];
         const uint32_t type = P.type, crush = P.crush;
         const float W = P.width, A = P.amplitude, off = P.offset, prob = P.prob;
@@ -385,6 +388,7 @@ struct mi_velvet_bank : mi_bank::tables<velvet_params, velvet_state>
     std::vector<uint8_t> inited;                                // init() or set_state() has given the channel a nBufID
     uint32_t             uninited = 0;                          // channels without one
     bool                 any_known = false;                     // a record carries a state that no launch has taken yet
+    uint32_t             disabled = 0;                          // channels that are switched off
     const uint64_t      *d_tables = nullptr;                    // the device's MLS tables, not the bank's
 };
 
@@ -454,7 +458,7 @@ int mi_velvet_bank_create(mi_velvet_bank_t **bank, uint32_t channels)
     velvet_params p = velvet_params();                          // construct(), Velvet.cpp:48-63
     p.buf_id = MI_LCG_UNSET, p.mls_known = MLS_KEEP;
     p.core = MI_VN_CORE_MLS, p.type = MI_VN_VELVET_OVN, p.crush = 0, p.prob = 0.5f;
-    p.width = 10.0f, p.delta = 0.5f, p.amplitude = 1.0f, p.offset = 0.0f;
+    p.width = 10.0f, p.delta = 0.5f, p.amplitude = 1.0f, p.offset = 0.0f, p.enabled = 1;
     velvet_state s = velvet_state();                            // Randomizer.cpp:69-80, MLS.cpp:89-103
     s.buf_id = MI_LCG_UNSET, s.sync = 1, s.n_bits = mi_mls::MLS_MAX_BITS;
     r = mi_bank::alloc(*b, "mi_velvet_bank_create", p, s);
@@ -559,43 +563,84 @@ int mi_velvet_bank_set_crush(mi_velvet_bank_t *b, uint32_t channel, int crush)
     return MI_OK;
 }
 
-int mi_velvet_bank_process(mi_velvet_bank_t *b, float *dst, const float *src, size_t count, size_t dst_stride, size_t src_stride, uint32_t op,
-                           void *stream)
+// segmented: an overwrite cut into segments of BUF_LIM_SIZE, as a caller's loop of process_overwrite(tmp, <= 256) makes it
+static int velvet_process(const char *entry, mi_velvet_bank *b, float *dst, const float *src, size_t count, size_t dst_stride, size_t src_stride,
+                          uint32_t op, bool segmented, void *stream)
 {
-    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_velvet_bank_process: NULL bank");
-    MI_REQUIRE(op <= MI_OSC_MUL, MI_EINVAL, "mi_velvet_bank_process: no operation %u", op);
+    MI_REQUIRE(b != nullptr, MI_ESTATE, "%s: NULL bank", entry);
+    MI_REQUIRE(op <= MI_OSC_MUL, MI_EINVAL, "%s: no operation %u", entry, op);
     if (op == MI_OSC_OVERWRITE)
         src = nullptr;
     if (count == 0)
         return MI_OK;
-    int r = mi_bank::check_rows("mi_velvet_bank_process", b->channels, count, COUNT_LIMIT,
+    int r = mi_bank::check_rows(entry, b->channels, count, COUNT_LIMIT,
                                 { { dst, dst_stride, count, mi_bank::REQUIRED | mi_bank::OUTPUT }, { src, src_stride, count, 0 } });
     if (r != MI_OK)
         return r;
     for (uint32_t ch = 0; b->uninited != 0 && ch < b->channels; ++ch)
-        MI_REQUIRE(b->inited[ch], MI_ESTATE, "mi_velvet_bank_process: channel %u was never init()ed", ch);
+        MI_REQUIRE(b->inited[ch] || !b->params[ch].enabled, MI_ESTATE, "%s: channel %u was never init()ed", entry, ch);
+    if (b->disabled == b->channels)                         // nobody's process() is called
+        return MI_OK;
     hipStream_t st = mi::as_stream(stream);
-    if (src == nullptr && op == MI_OSC_MUL)                     // noise * 0: fill_zero and not a draw, :290-295
+    if (src == nullptr && op == MI_OSC_MUL)                 // noise * 0: fill_zero and not a draw, :290-295
     {
-        if (b->channels == 1)                                   // one row: its stride says nothing
+        if (b->channels == 1)                               // one row: its stride says nothing
             MI_HIP_CHECK(hipMemsetAsync(dst, 0, count * sizeof(float), st));
-        else
+        else if (b->disabled == 0)
             MI_HIP_CHECK(hipMemset2DAsync(dst, dst_stride * sizeof(float), 0, count * sizeof(float), b->channels, st));
+        else
+            for (uint32_t ch = 0; ch < b->channels; ++ch)
+                if (b->params[ch].enabled)
+                    MI_HIP_CHECK(hipMemsetAsync(dst + size_t(ch) * dst_stride, 0, count * sizeof(float), st));
         return MI_OK;
     }
     r = mi_bank::upload(*b, "mi_velvet_bank", st);
     if (r != MI_OK)
         return r;
     // with a source the call is cut into segments of BUF_LIM_SIZE; without one (overwrite, add to nothing) it is one segment
-    const uint32_t mode = (src == nullptr) ? uint32_t(MI_OSC_OVERWRITE) : op, seg = (src == nullptr) ? uint32_t(count) : VN_SEG;
+    const uint32_t mode = (src == nullptr) ? uint32_t(MI_OSC_OVERWRITE) : op;
+    const uint32_t seg = (src == nullptr && !segmented) ? uint32_t(count) : VN_SEG;
     const bool vec = mi::aligned16(dst, dst_stride, b->channels) && (src == nullptr || mi::aligned16(src, src_stride, b->channels));
     const dim3 grid(b->channels);
     VELVET_LAUNCH(mode, vec, grid, st, dst, src, dst_stride, src_stride, uint32_t(count), seg, b->d_params, b->d_state, b->d_tables);
     MI_HIP_CHECK(hipGetLastError());
+    bool left = false;
     for (uint32_t ch = 0; b->any_known && ch < b->channels; ++ch)  // as the kernel leaves the records
-        b->params[ch].rand_known = 0, b->params[ch].mls_known = MLS_KEEP;
-    b->any_known = false;
+    {
+        velvet_params &p = b->params[ch];
+        if (p.enabled)
+            p.rand_known = 0, p.mls_known = MLS_KEEP;
+        else
+            left |= p.rand_known != 0 || p.mls_known != MLS_KEEP;
+    }
+    b->any_known = left;
     return MI_OK;
+}
+
+int mi_velvet_bank_process(mi_velvet_bank_t *b, float *dst, const float *src, size_t count, size_t dst_stride, size_t src_stride, uint32_t op,
+                           void *stream)
+{
+    return velvet_process("mi_velvet_bank_process", b, dst, src, count, dst_stride, src_stride, op, false, stream);
+}
+
+int mi_velvet_bank_process_segmented(mi_velvet_bank_t *b, float *dst, size_t count, size_t dst_stride, void *stream)
+{
+    return velvet_process("mi_velvet_bank_process_segmented", b, dst, nullptr, count, dst_stride, 0, MI_OSC_OVERWRITE, true, stream);
+}
+
+int mi_velvet_bank_set_row_enabled(mi_velvet_bank_t *b, uint32_t channel, int enabled)
+{
+    VELVET_CHANNEL("set_row_enabled");
+    const uint32_t on = enabled != 0;
+    if (p.enabled != on)
+        b->disabled += p.enabled - on, p.enabled = on, b->up.touch(channel);
+    return MI_OK;
+}
+
+int mi_velvet_bank_commit(mi_velvet_bank_t *b, void *stream)
+{
+    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_velvet_bank_commit: NULL bank");
+    return mi_bank::upload(*b, "mi_velvet_bank", mi::as_stream(stream));
 }
 
 int mi_velvet_bank_reserve(mi_velvet_bank_t *b, size_t count)

@@ -800,6 +800,10 @@ class LCGBank:
         check(lib.mi_lcg_bank_process(self.handle, _opt(dst), _opt(src), count, count if dst_stride is None else dst_stride,
                                       count if src_stride is None else src_stride, op, _stream(stream)))
 
+    def set_row_enabled(self, channel, enabled=True):
+        """A channel that is switched off is skipped by process(): row not written, state and pending state kept."""
+        check(lib.mi_lcg_bank_set_row_enabled(self.handle, channel, 1 if enabled else 0))
+
     def get_state(self, channel, stream=None):
         from .capi import LcgState
         s = LcgState()
@@ -876,6 +880,14 @@ class VelvetBank:
         check(lib.mi_velvet_bank_process(self.handle, _opt(dst), _opt(src), count, count if dst_stride is None else dst_stride,
                                          count if src_stride is None else src_stride, op, _stream(stream)))
 
+    def process_segmented(self, dst, count, dst_stride=None, stream=None):
+        """An overwrite in segments of 256 samples: a loop of process_overwrite(tmp, <= 256) in one launch."""
+        check(lib.mi_velvet_bank_process_segmented(self.handle, _opt(dst), count, count if dst_stride is None else dst_stride, _stream(stream)))
+
+    def set_row_enabled(self, channel, enabled=True):
+        """A channel that is switched off is skipped by process(): row not written, state and pending state kept."""
+        check(lib.mi_velvet_bank_set_row_enabled(self.handle, channel, 1 if enabled else 0))
+
     def reserve(self, count):
         check(lib.mi_velvet_bank_reserve(self.handle, count))
 
@@ -945,6 +957,10 @@ class MLSBank:
         check(lib.mi_mls_bank_process(self.handle, _opt(dst), _opt(src), count, count if dst_stride is None else dst_stride,
                                       count if src_stride is None else src_stride, op, _stream(stream)))
 
+    def set_row_enabled(self, channel, enabled=True):
+        """A channel that is switched off is skipped by process(): row not written, nState and a pending update kept."""
+        check(lib.mi_mls_bank_set_row_enabled(self.handle, channel, 1 if enabled else 0))
+
     def reserve(self, count):
         check(lib.mi_mls_bank_reserve(self.handle, count))
 
@@ -962,6 +978,211 @@ class MLSBank:
     def close(self):
         if self.handle:
             lib.mi_mls_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _chart(call, f, packed):
+    """freq_chart in either form on host arrays: complex64 [len(f)]."""
+    f = np.ascontiguousarray(f, dtype=np.float32)
+    if packed:
+        c = np.empty(2 * f.size, np.float32)
+        call(True, c.ctypes.data_as(c_void_p), None, f.ctypes.data_as(c_void_p), f.size)
+        return c[0::2] + 1j * c[1::2]
+    re, im = np.empty(f.size, np.float32), np.empty(f.size, np.float32)
+    call(False, re.ctypes.data_as(c_void_p), im.ctypes.data_as(c_void_p), f.ctypes.data_as(c_void_p), f.size)
+    return re + 1j * im
+
+
+class SpectralTiltBank:
+    """`channels` x lsp::dspu::SpectralTilt (mi_spectral_tilt_bank_*): a pole / zero cascade of up to 64 biquads that tilts the spectrum."""
+    OVERWRITE, ADD, MUL = 0, 1, 2
+    NEPER_PER_NEPER, DB_PER_OCTAVE, DB_PER_DECADE, UNIT_NONE = 0, 1, 2, 3
+    NORM_AT_DC, NORM_AT_20_HZ, NORM_AT_1_KHZ, NORM_AT_20_KHZ, NORM_AT_NYQUIST, NORM_AUTO, NORM_NONE = range(7)
+    MAX_SECTIONS = 64
+
+    def __init__(self, channels):
+        h = c_void_p()
+        check(lib.mi_spectral_tilt_bank_create(byref(h), channels))
+        self.handle, self.channels = h, channels
+
+    def set_order(self, channel, order):
+        check(lib.mi_spectral_tilt_bank_set_order(self.handle, channel, order))
+
+    def set_slope(self, channel, slope, unit=0):
+        check(lib.mi_spectral_tilt_bank_set_slope(self.handle, channel, slope, unit))
+
+    def set_norm(self, channel, norm):
+        check(lib.mi_spectral_tilt_bank_set_norm(self.handle, channel, norm))
+
+    def set_lower_frequency(self, channel, lower):
+        check(lib.mi_spectral_tilt_bank_set_lower_frequency(self.handle, channel, lower))
+
+    def set_upper_frequency(self, channel, upper):
+        check(lib.mi_spectral_tilt_bank_set_upper_frequency(self.handle, channel, upper))
+
+    def set_frequency_range(self, channel, lower, upper):
+        check(lib.mi_spectral_tilt_bank_set_frequency_range(self.handle, channel, lower, upper))
+
+    def set_sample_rate(self, channel, sample_rate):
+        check(lib.mi_spectral_tilt_bank_set_sample_rate(self.handle, channel, sample_rate))
+
+    def set_row_enabled(self, channel, enabled=True):
+        check(lib.mi_spectral_tilt_bank_set_row_enabled(self.handle, channel, 1 if enabled else 0))
+
+    def set_exact(self, on=True):
+        check(lib.mi_spectral_tilt_bank_set_exact(self.handle, 1 if on else 0))
+
+    def update_settings(self, stream=None):
+        check(lib.mi_spectral_tilt_bank_update_settings(self.handle, _stream(stream)))
+
+    def commit(self, stream=None):
+        check(lib.mi_spectral_tilt_bank_commit(self.handle, _stream(stream)))
+
+    def reserve(self, count, stream=None):
+        check(lib.mi_spectral_tilt_bank_reserve(self.handle, count, _stream(stream)))
+
+    def process(self, dst, count, src=None, op=0, dst_stride=None, src_stride=None, stream=None):
+        """process_overwrite / process_add / process_mul by `op`: dst = filter(src), dst += filter(src), dst *= filter(src)."""
+        check(lib.mi_spectral_tilt_bank_process(self.handle, _opt(dst), _opt(src), count, count if dst_stride is None else dst_stride,
+                                                count if src_stride is None else src_stride, op, _stream(stream)))
+
+    def get_chains(self, channel):
+        """(n, 5) float32 {b0, b1, b2, a1, a2}: the sections as the channel's last update_settings() left them."""
+        arr, n = (BiquadX1 * self.MAX_SECTIONS)(), c_uint32()
+        check(lib.mi_spectral_tilt_bank_get_chains(self.handle, channel, arr, byref(n)))
+        return np.frombuffer(arr, np.float32).reshape(self.MAX_SECTIONS, 8)[:n.value, :5].copy()
+
+    def get_settings(self, channel):
+        from .capi import SpectralTiltSettings
+        s = SpectralTiltSettings()
+        check(lib.mi_spectral_tilt_bank_get_settings(self.handle, channel, byref(s)))
+        return s
+
+    def freq_chart(self, channel, f, packed=False):
+        def call(p, a, b, fp, n):
+            if p:
+                check(lib.mi_spectral_tilt_bank_freq_chart_packed(self.handle, channel, a, fp, n))
+            else:
+                check(lib.mi_spectral_tilt_bank_freq_chart(self.handle, channel, a, b, fp, n))
+        return _chart(call, f, packed)
+
+    def reset(self, channel=None, stream=None):
+        check(lib.mi_spectral_tilt_bank_reset(self.handle, 0xFFFFFFFF if channel is None else channel, _stream(stream)))
+
+    def get_state(self, channel, stream=None):
+        st = np.empty((self.MAX_SECTIONS, 2), np.float32)
+        check(lib.mi_spectral_tilt_bank_get_state(self.handle, channel, st.ctypes.data_as(c_void_p), _stream(stream)))
+        return st
+
+    def set_state(self, channel, state, stream=None):
+        st = np.ascontiguousarray(state, dtype=np.float32)
+        assert st.shape == (self.MAX_SECTIONS, 2)
+        check(lib.mi_spectral_tilt_bank_set_state(self.handle, channel, st.ctypes.data_as(c_void_p), _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            lib.mi_spectral_tilt_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NoiseGeneratorBank:
+    """`channels` x lsp::dspu::NoiseGenerator (mi_noise_generator_bank_*): MLS, LCG and Velvet noise behind one interface, coloured
+    by a SpectralTilt."""
+    OVERWRITE, ADD, MUL = 0, 1, 2
+    GEN_MLS, GEN_LCG, GEN_VELVET = 0, 1, 2
+    WHITE, PINK, RED, BLUE, VIOLET, ARBITRARY = range(6)
+
+    def __init__(self, channels):
+        h = c_void_p()
+        check(lib.mi_noise_generator_bank_create(byref(h), channels))
+        self.handle, self.channels = h, channels
+
+    def init(self, channel, mls_n_bits=None, mls_seed=0, lcg_seed=0, velvet_rand_seed=0, velvet_mls_n_bits=0, velvet_mls_seed=0):
+        """init(...) with its six arguments; without any the argument-less init(): time seeds, an MLS of 64 bits."""
+        if mls_n_bits is None:
+            check(lib.mi_noise_generator_bank_init_auto(self.handle, channel))
+        else:
+            check(lib.mi_noise_generator_bank_init(self.handle, channel, int(mls_n_bits) & 0xFF, int(mls_seed) & 0xFFFFFFFFFFFFFFFF,
+                                                   int(lcg_seed) & 0xFFFFFFFF, int(velvet_rand_seed) & 0xFFFFFFFF,
+                                                   int(velvet_mls_n_bits) & 0xFF, int(velvet_mls_seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def _set(self, name, channel, *args):
+        check(getattr(lib, "mi_noise_generator_bank_set_" + name)(self.handle, channel, *args))
+
+    def set_sample_rate(self, channel, sr): self._set("sample_rate", channel, sr)
+    def set_mls_n_bits(self, channel, n): self._set("mls_n_bits", channel, int(n) & 0xFF)
+    def set_mls_seed(self, channel, seed): self._set("mls_seed", channel, int(seed) & 0xFFFFFFFFFFFFFFFF)
+    def set_lcg_distribution(self, channel, dist): self._set("lcg_distribution", channel, dist)
+    def set_velvet_type(self, channel, type_): self._set("velvet_type", channel, type_)
+    def set_velvet_window_width(self, channel, seconds): self._set("velvet_window_width", channel, seconds)
+    def set_velvet_arn_delta(self, channel, delta): self._set("velvet_arn_delta", channel, delta)
+    def set_velvet_crush(self, channel, crush): self._set("velvet_crush", channel, int(bool(crush)))
+    def set_velvet_crushing_probability(self, channel, prob): self._set("velvet_crushing_probability", channel, prob)
+    def set_generator(self, channel, generator): self._set("generator", channel, generator)
+    def set_noise_color(self, channel, color): self._set("noise_color", channel, color)
+    def set_coloring_order(self, channel, order): self._set("coloring_order", channel, order)
+    def set_color_slope(self, channel, slope, unit=0): self._set("color_slope", channel, slope, unit)
+    def set_amplitude(self, channel, amplitude): self._set("amplitude", channel, amplitude)
+    def set_offset(self, channel, offset): self._set("offset", channel, offset)
+
+    def set_exact(self, on=True):
+        check(lib.mi_noise_generator_bank_set_exact(self.handle, 1 if on else 0))
+
+    def update_settings(self, stream=None):
+        check(lib.mi_noise_generator_bank_update_settings(self.handle, _stream(stream)))
+
+    def reserve(self, count, stream=None):
+        check(lib.mi_noise_generator_bank_reserve(self.handle, count, _stream(stream)))
+
+    def process(self, dst, count, src=None, op=0, dst_stride=None, src_stride=None, stream=None):
+        """process_overwrite / process_add / process_mul by `op`; src may be None with add (as overwrite) and mul (zero fill)."""
+        check(lib.mi_noise_generator_bank_process(self.handle, _opt(dst), _opt(src), count, count if dst_stride is None else dst_stride,
+                                                  count if src_stride is None else src_stride, op, _stream(stream)))
+
+    def freq_chart(self, channel, f, packed=False):
+        def call(p, a, b, fp, n):
+            if p:
+                check(lib.mi_noise_generator_bank_freq_chart_packed(self.handle, channel, a, fp, n))
+            else:
+                check(lib.mi_noise_generator_bank_freq_chart(self.handle, channel, a, b, fp, n))
+        return _chart(call, f, packed)
+
+    def get_settings(self, channel):
+        from .capi import NoiseGeneratorSettings
+        s = NoiseGeneratorSettings()
+        check(lib.mi_noise_generator_bank_get_settings(self.handle, channel, byref(s)))
+        return s
+
+    def get_tilt_settings(self, channel):
+        from .capi import SpectralTiltSettings
+        s = SpectralTiltSettings()
+        check(lib.mi_noise_generator_bank_get_tilt_settings(self.handle, channel, byref(s)))
+        return s
+
+    def get_state(self, channel, stream=None):
+        from .capi import NoiseGeneratorState
+        s = NoiseGeneratorState()
+        check(lib.mi_noise_generator_bank_get_state(self.handle, channel, byref(s), _stream(stream)))
+        return s
+
+    def set_state(self, channel, state, stream=None):
+        check(lib.mi_noise_generator_bank_set_state(self.handle, channel, byref(state), _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            lib.mi_noise_generator_bank_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
