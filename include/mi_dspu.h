@@ -1556,6 +1556,103 @@ int mi_surge_bank_process(mi_surge_bank_t *bank, float *out, const float *in, si
 int mi_surge_bank_process_mul(mi_surge_bank_t *bank, float *out, const float *in, size_t count, size_t out_stride,
                               size_t in_stride, void *stream);
 
+/* ---- depopper bank: RMS-gated fades with look-ahead --------------------------------------------------------------------------- */
+/*
+ * mi_depopper_bank: `channels` x lsp::dspu::Depopper (util/Depopper.h, src/main/util/Depopper.cpp), every channel with settings of
+ * its own.  Per sample: the sliding RMS of the input over nRmsLen samples (env); a four-state automaton on it (closed, fade,
+ * opened, wait) with a fade-in threshold and a fade-out threshold; and a look-ahead gain buffer into which a fade-out is patched
+ * backwards, so the gain leaves nLookCount = (fade-out samples) + nRmsLen samples late.  fRms, nState, nCounter, nDelay, nRmsOff,
+ * nLookOff and both buffers live on the device: process() reads nothing back and can be captured into a graph.  env, gain and the
+ * state are the reference's bit for bit in float32 (NaN and Inf samples behave as there, subnormals are kept); the two fade
+ * curves are tabulated on the host with the C library's sinf and expf, the device evaluates no transcendental.  The output does
+ * not depend on how a stream is cut into calls.  Rows: [channels][stride].
+ *
+ * Refused with MI_EINVAL and a message by update_settings(), process(), get_state() and set_state() -- where the reference reads
+ * or writes outside its buffers, divides by zero or converts an undefined float to an integer:
+ *   - a channel that was never init()ed;
+ *   - nRmsLen == 0 (an RMS length of less than one sample: the default);
+ *   - a fade-out time above max_fade or below 0;
+ *   - a time or delay that is not a number or at least 2^30 samples; init() maxima that are negative, not a number or at least
+ *     2^24 samples (init() itself refuses these);
+ * and, the bank's own bound, a fade-in of more than 2^20 samples (one table entry per sample).  An RMS length outside
+ * [0, max_rms] is clamped, as the reference clamps it.  A refused bank stays refused until a setter has mended the channel.
+ */
+typedef struct mi_depopper_bank mi_depopper_bank_t;
+enum { MI_DEPOPPER_LINEAR = 0, MI_DEPOPPER_CUBIC = 1, MI_DEPOPPER_SINE = 2, MI_DEPOPPER_GAUSSIAN = 3, MI_DEPOPPER_PARABOLIC = 4 };  /* depopper_mode_t */
+enum { MI_DEPOPPER_CLOSED = 0, MI_DEPOPPER_FADE = 1, MI_DEPOPPER_OPENED = 2, MI_DEPOPPER_WAIT = 3 };          /* Depopper::state_t */
+/* Depopper::fade_t: enMode, fThresh, fTime, fDelay, nSamples, nDelay, fPoly */
+typedef struct { uint32_t mode; float threshold, time, delay; int64_t samples, delay_samples; float poly[4]; } mi_depopper_fade_t;
+/* sFadeIn, sFadeOut, nSampleRate, fLookMax, fRmsMax, fRmsLength, fRmsNorm, nLookMin, nLookMax, nLookCount, nRmsMin, nRmsMax,
+ * nRmsLen as the last update_settings() left them, and bReconfigure */
+typedef struct
+{
+    mi_depopper_fade_t fade_in, fade_out;
+    uint64_t sample_rate;
+    float look_max, rms_max, rms_length, rms_norm;
+    int64_t look_min_off, look_max_off, look_count, rms_min_off, rms_max_off, rms_len;
+    uint32_t reconfigure;
+} mi_depopper_params_t;
+typedef struct { float rms; uint32_t state; int64_t counter, delay, rms_off, look_off; } mi_depopper_state_t;  /* fRms, nState, nCounter, nDelay, nRmsOff, nLookOff */
+/* init() and reconfigure() of one depopper without a bank or a device: the settings are read from *settings as they stand, not
+ * through the setters (sample_rate, look_max, rms_max, rms_length -- clamped to [0, rms_max] -- and of both fades mode, threshold,
+ * time, delay), *designed receives them with the designed values, the tables (HOST memory, each may be NULL) at most their
+ * capacity of entries.  MI_EINVAL where the bank would refuse the settings; designed->reconfigure then says what was written: 0,
+ * the designed values as the reference computes them (nRmsLen == 0, a fade-out time outside [0, max_fade], a fade-in too long for
+ * the bank); 1, nothing, because the reference's own conversions are undefined (times that are no numbers, bad maxima or modes). */
+int mi_depopper_compute_params(const mi_depopper_params_t *settings, mi_depopper_params_t *designed, float *table_in, size_t in_capacity,
+                               float *table_out, size_t out_capacity);
+/* init() alone: *extents receives sample_rate, look_max, rms_max and the four offsets nLookMin, nLookMax, nRmsMin, nRmsMax of
+ * these maxima (times in milliseconds); everything else in it is the constructor's.  MI_EINVAL for maxima that init() refuses. */
+int mi_depopper_compute_extents(uint64_t sample_rate, float max_fade, float max_rms, mi_depopper_params_t *extents);
+/* A threshold on the envelope taken to the domain of squares, as the device compares it: *square receives the smallest q >= 0
+ * with sqrtf(q) >= threshold, so that  sqrtf(q) < threshold  is  q < *square  for every q >= 0 and for NaN (-Inf for a threshold
+ * that is not above 0, NaN for NaN: neither compare ever holds). */
+int mi_depopper_square_threshold(float threshold, float *square);
+int mi_depopper_bank_create(mi_depopper_bank_t **bank, uint32_t channels);                 /* construct(): no buffers yet */
+int mi_depopper_bank_destroy(mi_depopper_bank_t *bank);
+/* init(srate, max_fade, max_rms) of one channel (times in milliseconds): nothing happens where the three are what they were;
+ * otherwise the next update_settings() makes the channel's buffers, zeroes them and sets nState, nRmsOff and nLookOff. */
+int mi_depopper_bank_init(mi_depopper_bank_t *bank, uint32_t channel, uint64_t sample_rate, float max_fade, float max_rms);
+/* The setters (times in milliseconds), line for line the reference's: each compares the new value with the (clamped) old one,
+ * stores it unclamped and asks for a reconfiguration where they differ; *old (may be NULL) receives what the reference returns.
+ * A changed setting acts with the next process() that is issued.  The reference declares a tenth setter, set_release(), and
+ * defines it nowhere: there is nothing to restate. */
+int mi_depopper_bank_set_fade_in_mode(mi_depopper_bank_t *bank, uint32_t channel, uint32_t mode, uint32_t *old);
+int mi_depopper_bank_set_fade_out_mode(mi_depopper_bank_t *bank, uint32_t channel, uint32_t mode, uint32_t *old);
+int mi_depopper_bank_set_fade_in_time(mi_depopper_bank_t *bank, uint32_t channel, float value, float *old);
+int mi_depopper_bank_set_fade_out_time(mi_depopper_bank_t *bank, uint32_t channel, float value, float *old);
+int mi_depopper_bank_set_fade_in_threshold(mi_depopper_bank_t *bank, uint32_t channel, float value, float *old);
+int mi_depopper_bank_set_fade_out_threshold(mi_depopper_bank_t *bank, uint32_t channel, float value, float *old);
+int mi_depopper_bank_set_fade_in_delay(mi_depopper_bank_t *bank, uint32_t channel, float value, float *old);
+int mi_depopper_bank_set_fade_out_delay(mi_depopper_bank_t *bank, uint32_t channel, float value, float *old);
+int mi_depopper_bank_set_rms_length(mi_depopper_bank_t *bank, uint32_t channel, float value, float *old);
+/* init() and every setter's field of one channel as they stand in *settings (read as compute_params reads them; the RMS length
+ * is clamped): what a caller that keeps the reference's fields itself hands over.  A reconfiguration is asked for where a field
+ * differs from the channel's, or where settings->reconfigure is not 0. */
+int mi_depopper_bank_set_settings(mi_depopper_bank_t *bank, uint32_t channel, const mi_depopper_params_t *settings);
+/* reconfigure() of every channel that asks for it: the designer, the tables and the settings to the device, fRms re-summed over
+ * the new nRmsLen (and the call waits for the copies).  Every process entry runs it first.  On a stream being captured pending
+ * work is refused (MI_ESTATE): call it before the capture.  Where one channel's settings are refused no channel is touched:
+ * get_params(), get_fade_table() and latency() go on reporting what the device runs, with reconfigure still 1. */
+int mi_depopper_bank_update_settings(mi_depopper_bank_t *bank, void *stream);
+/* The designed values (HOST memory).  The fade tables, crossfade(fade, x) for x = 0 .. nSamples - 1 (fade_out 0: sFadeIn, 1:
+ * sFadeOut): *count receives the length, table (HOST memory, may be NULL) at most `capacity` entries.  latency(): sFadeOut.nSamples. */
+int mi_depopper_bank_get_params(const mi_depopper_bank_t *bank, uint32_t channel, mi_depopper_params_t *params);
+int mi_depopper_bank_get_fade_table(const mi_depopper_bank_t *bank, uint32_t channel, uint32_t fade_out, float *table, size_t capacity,
+                                    size_t *count);
+int mi_depopper_bank_latency(const mi_depopper_bank_t *bank, uint32_t channel, int64_t *samples);
+/* The state after what is pending and enqueued (HOST memory; waits for the stream; not on a stream being captured: MI_ESTATE).
+ * rms_buf / gain_buf (HOST memory, each may be NULL): the logical contents of the buffers, the last nRmsMin squares and the last
+ * nLookMin gains, oldest first.  set_state refuses a state above 3, a counter below 0, counters of 2^30 and more and offsets
+ * outside [nRmsMin, nRmsMax] / [nLookMin, nLookMax] (MI_EINVAL). */
+int mi_depopper_bank_get_state(mi_depopper_bank_t *bank, uint32_t channel, mi_depopper_state_t *state, float *rms_buf, float *gain_buf,
+                               void *stream);
+int mi_depopper_bank_set_state(mi_depopper_bank_t *bank, uint32_t channel, const mi_depopper_state_t *state, const float *rms_buf,
+                               const float *gain_buf, void *stream);
+/* process(env, gain, src, count): env may be NULL; env or gain may be src (same stride); env and gain are different buffers. */
+int mi_depopper_bank_process(mi_depopper_bank_t *bank, float *env, float *gain, const float *src, size_t count, size_t env_stride,
+                             size_t gain_stride, size_t src_stride, void *stream);
+
 /* ---- bypass and crossfade banks: click-free switching ------------------------------------------------------------------------ */
 /*
  * mi_bypass_bank: `channels` x lsp::dspu::Bypass (ctl/Bypass.h, src/main/ctl/Bypass.cpp).  The gain runs from 0 (dry) to 1 (wet)

@@ -204,6 +204,26 @@ class SurgeState(ctypes.Structure):
     _fields_ = [("gain", c_float), ("transition_time", c_uint32), ("shutdown_time", c_uint32), ("on", c_uint32)]
 
 
+class DepopperFade(ctypes.Structure):
+    """mi_depopper_fade_t: enMode, fThresh, fTime, fDelay, nSamples, nDelay, fPoly."""
+    _fields_ = [("mode", c_uint32), ("threshold", c_float), ("time", c_float), ("delay", c_float), ("samples", ctypes.c_int64),
+                ("delay_samples", ctypes.c_int64), ("poly", c_float * 4)]
+
+
+class DepopperParams(ctypes.Structure):
+    """mi_depopper_params_t: both fades, the rate, the maxima, the RMS length and norm, the look and RMS extents, bReconfigure."""
+    _fields_ = [("fade_in", DepopperFade), ("fade_out", DepopperFade), ("sample_rate", ctypes.c_uint64), ("look_max", c_float),
+                ("rms_max", c_float), ("rms_length", c_float), ("rms_norm", c_float), ("look_min_off", ctypes.c_int64),
+                ("look_max_off", ctypes.c_int64), ("look_count", ctypes.c_int64), ("rms_min_off", ctypes.c_int64),
+                ("rms_max_off", ctypes.c_int64), ("rms_len", ctypes.c_int64), ("reconfigure", c_uint32)]
+
+
+class DepopperState(ctypes.Structure):
+    """mi_depopper_state_t: fRms, nState, nCounter, nDelay, nRmsOff, nLookOff."""
+    _fields_ = [("rms", c_float), ("state", c_uint32), ("counter", ctypes.c_int64), ("delay", ctypes.c_int64),
+                ("rms_off", ctypes.c_int64), ("look_off", ctypes.c_int64)]
+
+
 class BypassState(ctypes.Structure):
     """mi_bypass_state_t: nState (0 on, 1 active, 2 off), fDelta, fGain."""
     _fields_ = [("state", c_uint32), ("delta", c_float), ("gain", c_float)]
@@ -654,6 +674,29 @@ PROTOTYPES = {
     "mi_surge_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(SurgeState), c_void_p]),
     "mi_surge_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_surge_bank_process_mul": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_depopper_compute_params": (c_int, [POINTER(DepopperParams), POINTER(DepopperParams), c_void_p, c_size_t, c_void_p, c_size_t]),
+    "mi_depopper_compute_extents": (c_int, [ctypes.c_uint64, c_float, c_float, POINTER(DepopperParams)]),
+    "mi_depopper_square_threshold": (c_int, [c_float, POINTER(c_float)]),
+    "mi_depopper_bank_create": (c_int, [POINTER(c_void_p), c_uint32]),
+    "mi_depopper_bank_destroy": (c_int, [c_void_p]),
+    "mi_depopper_bank_init": (c_int, [c_void_p, c_uint32, ctypes.c_uint64, c_float, c_float]),
+    "mi_depopper_bank_set_fade_in_mode": (c_int, [c_void_p, c_uint32, c_uint32, POINTER(c_uint32)]),
+    "mi_depopper_bank_set_fade_out_mode": (c_int, [c_void_p, c_uint32, c_uint32, POINTER(c_uint32)]),
+    "mi_depopper_bank_set_fade_in_time": (c_int, [c_void_p, c_uint32, c_float, POINTER(c_float)]),
+    "mi_depopper_bank_set_fade_out_time": (c_int, [c_void_p, c_uint32, c_float, POINTER(c_float)]),
+    "mi_depopper_bank_set_fade_in_threshold": (c_int, [c_void_p, c_uint32, c_float, POINTER(c_float)]),
+    "mi_depopper_bank_set_fade_out_threshold": (c_int, [c_void_p, c_uint32, c_float, POINTER(c_float)]),
+    "mi_depopper_bank_set_fade_in_delay": (c_int, [c_void_p, c_uint32, c_float, POINTER(c_float)]),
+    "mi_depopper_bank_set_fade_out_delay": (c_int, [c_void_p, c_uint32, c_float, POINTER(c_float)]),
+    "mi_depopper_bank_set_rms_length": (c_int, [c_void_p, c_uint32, c_float, POINTER(c_float)]),
+    "mi_depopper_bank_set_settings": (c_int, [c_void_p, c_uint32, POINTER(DepopperParams)]),
+    "mi_depopper_bank_update_settings": (c_int, [c_void_p, c_void_p]),
+    "mi_depopper_bank_get_params": (c_int, [c_void_p, c_uint32, POINTER(DepopperParams)]),
+    "mi_depopper_bank_get_fade_table": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_size_t, POINTER(c_size_t)]),
+    "mi_depopper_bank_latency": (c_int, [c_void_p, c_uint32, POINTER(ctypes.c_int64)]),
+    "mi_depopper_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(DepopperState), c_void_p, c_void_p, c_void_p]),
+    "mi_depopper_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(DepopperState), c_void_p, c_void_p, c_void_p]),
+    "mi_depopper_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_bypass_bank_create": (c_int, [POINTER(c_void_p), c_uint32]),
     "mi_bypass_bank_destroy": (c_int, [c_void_p]),
     "mi_bypass_bank_init": (c_int, [c_void_p, c_uint32, c_int, c_float]),

@@ -2476,6 +2476,130 @@ class SurgeProtectorBank:
             pass
 
 
+class DepopperBank:
+    """`channels` x lsp::dspu::Depopper (mi_depopper_bank_*): the RMS envelope of a row and a gain that fades in when the signal
+    appears and -- ahead of time, by the look-ahead -- out before it vanishes."""
+    MODES = {"linear": 0, "cubic": 1, "sine": 2, "gaussian": 3, "parabolic": 4}
+
+    def __init__(self, channels):
+        h = c_void_p()
+        check(lib.mi_depopper_bank_create(byref(h), channels))
+        self.handle, self.channels = h, channels
+
+    def init(self, channel, sample_rate, max_fade, max_rms):
+        check(lib.mi_depopper_bank_init(self.handle, channel, sample_rate, float(max_fade), float(max_rms)))
+
+    def _set_mode(self, fn, channel, mode):
+        old = c_uint32()
+        check(fn(self.handle, channel, self.MODES.get(mode, mode), byref(old)))
+        return old.value
+
+    def _set_float(self, fn, channel, value):
+        old = c_float()
+        check(fn(self.handle, channel, float(value), byref(old)))
+        return np.float32(old.value)
+
+    def set_fade_in_mode(self, channel, mode):
+        return self._set_mode(lib.mi_depopper_bank_set_fade_in_mode, channel, mode)
+
+    def set_fade_out_mode(self, channel, mode):
+        return self._set_mode(lib.mi_depopper_bank_set_fade_out_mode, channel, mode)
+
+    def set_fade_in_time(self, channel, time):
+        return self._set_float(lib.mi_depopper_bank_set_fade_in_time, channel, time)
+
+    def set_fade_out_time(self, channel, time):
+        return self._set_float(lib.mi_depopper_bank_set_fade_out_time, channel, time)
+
+    def set_fade_in_threshold(self, channel, threshold):
+        return self._set_float(lib.mi_depopper_bank_set_fade_in_threshold, channel, threshold)
+
+    def set_fade_out_threshold(self, channel, threshold):
+        return self._set_float(lib.mi_depopper_bank_set_fade_out_threshold, channel, threshold)
+
+    def set_fade_in_delay(self, channel, delay):
+        return self._set_float(lib.mi_depopper_bank_set_fade_in_delay, channel, delay)
+
+    def set_fade_out_delay(self, channel, delay):
+        return self._set_float(lib.mi_depopper_bank_set_fade_out_delay, channel, delay)
+
+    def set_rms_length(self, channel, length):
+        return self._set_float(lib.mi_depopper_bank_set_rms_length, channel, length)
+
+    def update_settings(self, stream=None):
+        check(lib.mi_depopper_bank_update_settings(self.handle, _stream(stream)))
+
+    @staticmethod
+    def _fade(f):
+        return {"mode": f.mode, "threshold": np.float32(f.threshold), "time": np.float32(f.time), "delay": np.float32(f.delay),
+                "samples": f.samples, "delay_samples": f.delay_samples, "poly": np.array(list(f.poly), np.float32)}
+
+    def get_params(self, channel):
+        """The reference's designed fields as the last update_settings() left them."""
+        from .capi import DepopperParams
+        p = DepopperParams()
+        check(lib.mi_depopper_bank_get_params(self.handle, channel, byref(p)))
+        return {"fade_in": self._fade(p.fade_in), "fade_out": self._fade(p.fade_out), "sample_rate": p.sample_rate,
+                "look_max": np.float32(p.look_max), "rms_max": np.float32(p.rms_max), "rms_length": np.float32(p.rms_length),
+                "rms_norm": np.float32(p.rms_norm), "look_min_off": p.look_min_off, "look_max_off": p.look_max_off,
+                "look_count": p.look_count, "rms_min_off": p.rms_min_off, "rms_max_off": p.rms_max_off, "rms_len": p.rms_len,
+                "reconfigure": p.reconfigure}
+
+    def get_fade_table(self, channel, fade_out):
+        """crossfade(sFadeOut if fade_out else sFadeIn, x) for x = 0 .. nSamples - 1, as the device reads it."""
+        n = ctypes.c_size_t()
+        check(lib.mi_depopper_bank_get_fade_table(self.handle, channel, int(bool(fade_out)), None, 0, byref(n)))
+        t = np.zeros(n.value, np.float32)
+        check(lib.mi_depopper_bank_get_fade_table(self.handle, channel, int(bool(fade_out)), c_void_p(t.ctypes.data), t.size, byref(n)))
+        return t
+
+    def latency(self, channel):
+        n = ctypes.c_int64()
+        check(lib.mi_depopper_bank_latency(self.handle, channel, byref(n)))
+        return n.value
+
+    def get_state(self, channel, buffers=False, stream=None):
+        """fRms, nState, nCounter, nDelay, nRmsOff, nLookOff; with buffers also the last nRmsMin squares and nLookMin gains."""
+        from .capi import DepopperState
+        s = DepopperState()
+        rms = gain = None
+        if buffers:
+            p = self.get_params(channel)
+            rms, gain = np.zeros(p["rms_min_off"], np.float32), np.zeros(p["look_min_off"], np.float32)
+        check(lib.mi_depopper_bank_get_state(self.handle, channel, byref(s), c_void_p(rms.ctypes.data) if buffers else None,
+                                             c_void_p(gain.ctypes.data) if buffers else None, _stream(stream)))
+        out = {"rms": np.float32(s.rms), "state": s.state, "counter": s.counter, "delay": s.delay, "rms_off": s.rms_off,
+               "look_off": s.look_off}
+        if buffers:
+            out["rms_buf"], out["gain_buf"] = rms, gain
+        return out
+
+    def set_state(self, channel, rms, state, counter, delay, rms_off, look_off, rms_buf=None, gain_buf=None, stream=None):
+        from .capi import DepopperState
+        s = DepopperState(float(rms), state, counter, delay, rms_off, look_off)
+        rb = None if rms_buf is None else np.ascontiguousarray(rms_buf, np.float32)
+        gb = None if gain_buf is None else np.ascontiguousarray(gain_buf, np.float32)
+        check(lib.mi_depopper_bank_set_state(self.handle, channel, byref(s), None if rb is None else c_void_p(rb.ctypes.data),
+                                             None if gb is None else c_void_p(gb.ctypes.data), _stream(stream)))
+
+    def process(self, env, gain, src, count, env_stride=None, gain_stride=None, src_stride=None, stream=None):
+        """process(env, gain, src, count): env may be None; env or gain may be src."""
+        check(lib.mi_depopper_bank_process(self.handle, _opt(env), _opt(gain), _opt(src), count,
+                                           count if env_stride is None else env_stride, count if gain_stride is None else gain_stride,
+                                           count if src_stride is None else src_stride, _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            lib.mi_depopper_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _word_and_floats(struct, word, a, b):
     """A state struct of one uint32 and two float32 with the floats' bits as given (a NaN keeps its payload)."""
     return struct.from_buffer_copy(np.uint32(word).tobytes() + np.float32(a).tobytes() + np.float32(b).tobytes())
