@@ -1350,6 +1350,8 @@ int mi_simple_autogain_bank_process(mi_simple_autogain_bank_t *bank, float *dst,
  * once, the square root is correctly rounded); the sums of the refresh are taken serially, oldest sample first (DESIGN.md
  * section 4).  Ring, fRmsValue, nRefresh and the ring position live on the device; the bank has no host positions, so its
  * process calls can be captured into a graph and replayed.  Inputs are finite: NaN is out of scope.  Subnormals are kept.
+ * The magnitude of a negative zero is +0 (fabsf), where the class's scalar text, (s < 0.0f) ? -s : s (:435), keeps -0: in PEAK
+ * mode the output's sign bit differs there.  lsp-dsp-lib's abs1 / abs2 are not in the reference tree, so this is unpinned.
  * Rows of the sample buffers: [channels][stride].
  */
 typedef struct mi_sidechain_bank mi_sidechain_bank_t;
@@ -1369,7 +1371,8 @@ int mi_sidechain_bank_create(mi_sidechain_bank_t **bank, uint32_t channels, uint
 int mi_sidechain_bank_destroy(mi_sidechain_bank_t *bank);
 /* The setters of one channel with the reference's rules (:88-117, Sidechain.h:146-175): set_sample_rate re-makes the ring
  * (zeroed, position 0) and raises UPDATE and CLEAR; set_reactivity ignores an unchanged value and values outside
- * [0, max_reactivity] and raises UPDATE (which forces a refresh at the next sample); set_stereo_mode raises CLEAR when the
+ * [0, max_reactivity] and raises UPDATE (which forces a refresh at the next sample); set_sample_rate also takes the channel
+ * back to the stereo mode STEREO, as the reference's assignment to nFlags does (:91); set_stereo_mode raises CLEAR when the
  * mode changes; set_mode zeroes fRmsValue WITHOUT a refresh when the mode changes; set_source and set_gain just set.
  * Nothing reaches the device before update_settings().  A source above AMAX, a mode above UNIFORM and a stereo mode above
  * MIDSIDE are MI_EINVAL. */
@@ -1389,7 +1392,8 @@ int mi_sidechain_bank_clear(mi_sidechain_bank_t *bank, uint32_t channel);
 int mi_sidechain_bank_update_settings(mi_sidechain_bank_t *bank, void *stream);
 /* The channel's parameters as the last update_settings() left them, flags with what is pending now (HOST memory); fRmsValue,
  * nRefresh and the ring position (RawRingBuffer::position()) as the work enqueued on `stream` leaves them (HOST memory, each
- * may be NULL; waits for the stream) */
+ * may be NULL; waits for the stream).  The position is 0 only before the first sample of a ring: after samples it lies in
+ * (0, capacity], AT the capacity where a call ended at the ring's end (RawRingBuffer.cpp:106-125) */
 int mi_sidechain_bank_get_params(const mi_sidechain_bank_t *bank, uint32_t channel, mi_sidechain_params_t *params);
 int mi_sidechain_bank_get_state(mi_sidechain_bank_t *bank, uint32_t channel, float *rms_value, uint32_t *refresh, uint32_t *position,
                                 void *stream);

@@ -69,19 +69,23 @@ size_t RawRingBuffer::write(const float *src, size_t count)
 
 void RawRingBuffer::write(float data)
 {
-    pData[nHead] = data;
+    pData[(nHead < nCapacity) ? nHead : 0] = data;              // see push(float)
 }
 
 size_t RawRingBuffer::push(const float *data, size_t count)
 {
     count = write(data, count);
-    if (nCapacity > 0)
-        nHead = (nHead + count) % nCapacity;
+    // RawRingBuffer.cpp:110-122: the position wraps only where nHead + count > nCapacity, so a block that ends at the ring's end
+    // leaves it AT the capacity (head() == end()), and the next block starts over from there
+    nHead = (nHead + count > nCapacity) ? nHead + count - nCapacity : nHead + count;
     return count;
 }
 
 void RawRingBuffer::push(float data)
 {
+    // a position at the capacity (see above) is the ring's start: the reference writes pData[nCapacity] there (:127-131)
+    if (nHead >= nCapacity)
+        nHead = 0;
     pData[nHead] = data;
     nHead = (nHead + 1) % nCapacity;
 }

@@ -298,8 +298,13 @@ void Sidechain::process(float *out, const float **in, size_t samples)      // :4
     p->known = true;
     fRmsValue = p->rms;
     nRefresh = p->refresh;
-    sBuffer.reset();
-    sBuffer.advance(p->head);
+    sBuffer.reset();                                            // position() = p->head, which is the capacity after a block that
+    if (p->head > 0)                                            // ended at the ring's end (RawRingBuffer.cpp:118-122): advance()
+    {                                                           // alone would take it to 0.  The sample that this push
+        const float nothing = 0.0f;                             // writes means nothing: the ring's samples live on the device
+        sBuffer.advance(p->head - 1);
+        sBuffer.push(&nothing, 1);
+    }
 }
 
 float Sidechain::process(const float *in)                       // one sample through the block path (see the header)

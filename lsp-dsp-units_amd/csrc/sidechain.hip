@@ -312,7 +312,9 @@ namespace
         {
             // nRefresh after `count` samples (count > 0): it is taken modulo REFRESH_RATE only when a sample follows (:455-459)
             const uint32_t refresh = (R0 + count - 1) % REFRESH_RATE + 1;
-            const uint32_t head = uint32_t((uint64_t(head0) + count) % cap);
+            // RawRingBuffer::push wraps only where nHead + count > nCapacity (RawRingBuffer.cpp:110-122): a block that ends at the
+            // ring's end leaves the position AT the capacity, so after count > 0 samples it lies in (0, capacity]
+            const uint32_t head = uint32_t((uint64_t(head0) + count - 1) % cap) + 1;
             state[ch] = device_state{ rms, refresh, head, 0 };
         }
     }
@@ -538,7 +540,8 @@ namespace mi
             r = sc_update(b, st);
         if (r != MI_OK)
             return r;
-        const device_state s = { rms_value, (refresh < REFRESH_RATE) ? refresh : REFRESH_RATE, position % b->params[channel].capacity, 0 };
+        const device_state s = { rms_value, (refresh < REFRESH_RATE) ? refresh : REFRESH_RATE,
+                                 (position <= b->params[channel].capacity) ? position : position % b->params[channel].capacity, 0 };
         if (zero_ring)
             MI_HIP_CHECK(hipMemsetAsync(b->d_ring + size_t(channel) * b->ring_stride, 0, b->ring_stride * sizeof(float), st));
         return mi::write_state(b->d_state + channel, s, st);
@@ -593,7 +596,7 @@ int mi_sidechain_bank_set_sample_rate(mi_sidechain_bank_t *b, uint32_t channel, 
     const uint32_t cap = ring_capacity(sample_rate, b->max_reactivity);
     MI_REQUIRE(cap > 0, MI_EINVAL, "mi_sidechain_bank_set_sample_rate: %g ms at %u Hz are too long", double(b->max_reactivity), sample_rate);
     c.sample_rate = sample_rate;
-    c.flags = (c.flags & MI_SCF_MIDSIDE) | MI_SCF_UPDATE | MI_SCF_CLEAR;
+    c.flags = MI_SCF_UPDATE | MI_SCF_CLEAR;                     // :91 assigns: the mid-side flag goes too
     b->params[channel].capacity = cap;
     b->pend[channel] |= P_RING;
     b->work = true;

@@ -38,7 +38,10 @@ namespace lsp
                 // at the head, without moving it: min(count, size()) samples, wrapping at the end; returns what was written
                 size_t              write(const float *src, size_t count);
                 void                write(float data);
-                // the same, and the head moves behind what was written
+                // the same, and the head moves behind what was written.  As in the reference (RawRingBuffer.cpp:106-125) the block
+                // form wraps the position only where it would pass the end: a block that ends AT the ring's end leaves
+                // position() == size() and head() == end(), and the next block starts over from begin().  The single-sample
+                // forms take such a position as 0 (the reference writes one sample past its storage there)
                 size_t              push(const float *data, size_t count);
                 void                push(float data);
                 // `count` samples from `offset` samples behind the head on (oldest first), wrapping; returns what was read

@@ -6,10 +6,16 @@
 // input; not for in == NULL).  Inputs are finite: NaN is out of scope.
 //
 // The single-sample process(const float *) is a call of ONE sample through the block path.  The reference's own text for it
-// (Sidechain.cpp:556-624) differs from its block overload in three places, and these are NOT reproduced:
+// (Sidechain.cpp:556-624) differs from its block overload in four places, and these are NOT reproduced:
 //   * it counts the sample before it looks at nRefresh (++nRefresh >= REFRESH_RATE), so its refresh comes one sample earlier;
 //   * it divides by float(nReactivity) (rms / float(nReactivity)) where the block overload multiplies by 1.0f / nReactivity;
+//   * it sums from the left, (fRmsValue + new) - last (:600, :613), where the block overload adds the difference,
+//     rms += new - last (:499, :528);
 //   * in stereo mode it has no equalizer for LEFT and RIGHT (:388-393).
+//
+// The magnitude of a negative zero is +0 here (fabsf); the reference's scalar text, (s < 0.0f) ? -s : s (Sidechain.cpp:435),
+// keeps -0, which in PEAK mode reaches the output's sign bit.  What lsp-dsp-lib's abs1 / abs2 give in the block overload is
+// not in the reference tree, so this is unpinned, and it is a deviation from the scalar text.
 //
 // As the reference: set_mode() zeroes fRmsValue without a refresh, so until the next refresh (at most 0x2000 samples) the
 // running sum of the RMS and UNIFORM detectors may be negative and the output sits on the clamp; clear() and

@@ -1,6 +1,7 @@
 // STAND-IN for lsp-dsp-lib's <lsp-plug.in/dsp/dsp.h>, which the reference tree does not carry.  Only what Compressor,
 // Expander, Gate, DynamicProcessor and Limiter take from it: dsp::copy, the knee structs, the eight array gain primitives, and
-// Limiter.cpp's buffer primitives (at the end of this file; AutoGain and SimpleAutoGain take nothing).
+// Limiter.cpp's buffer primitives (AutoGain and SimpleAutoGain take nothing), and what Sidechain.cpp and RawRingBuffer.cpp take
+// (at the end of this file).
 //
 // The primitives are plain loops of the formula that each class states in full in its own scalar overload
 // (Compressor::reduction(float) / curve(float), Expander::amplification(float) / curve(float), Gate::amplification(float, bool)
@@ -204,6 +205,133 @@ namespace lsp
                 if (src[i] > src[idx])
                     idx = i;
             return idx;
+        }
+
+        // ---- Sidechain.cpp's and RawRingBuffer.cpp's primitives ---------------------------------------------------------------
+        // Each is the plain loop of what the class's scalar preprocess(float *, const float *) states (Sidechain.cpp:335-437);
+        // tests/golden/make_sidechain_vectors.py asserts, on every recorded sample, that the array path returns the bits of
+        // that scalar overload.
+        inline void fill(float *dst, float value, size_t count)
+        {
+            for (size_t i = 0; i < count; ++i)
+                dst[i] = value;
+        }
+
+        inline void abs1(float *dst, size_t count)                                  // :435 (s < 0.0f) ? -s : s
+        {
+            for (size_t i = 0; i < count; ++i)
+                dst[i] = (dst[i] < 0.0f) ? -dst[i] : dst[i];
+        }
+
+        inline void abs2(float *dst, const float *src, size_t count)
+        {
+            for (size_t i = 0; i < count; ++i)
+                dst[i] = (src[i] < 0.0f) ? -src[i] : src[i];
+        }
+
+        inline void lr_to_mid(float *m, const float *l, const float *r, size_t count)      // :395
+        {
+            for (size_t i = 0; i < count; ++i)
+                m[i] = (l[i] + r[i]) * 0.5f;
+        }
+
+        inline void lr_to_side(float *s, const float *l, const float *r, size_t count)     // :400
+        {
+            for (size_t i = 0; i < count; ++i)
+                s[i] = (l[i] - r[i]) * 0.5f;
+        }
+
+        inline void ms_to_left(float *l, const float *m, const float *s, size_t count)     // :346
+        {
+            for (size_t i = 0; i < count; ++i)
+                l[i] = m[i] + s[i];
+        }
+
+        inline void ms_to_right(float *r, const float *m, const float *s, size_t count)    // :351
+        {
+            for (size_t i = 0; i < count; ++i)
+                r[i] = m[i] - s[i];
+        }
+
+        inline float shim_smin(float a, float b)    { return (fabsf(a) < fabsf(b)) ? a : b; }      // :405, :368
+        inline float shim_smax(float a, float b)    { return (fabsf(b) < fabsf(a)) ? a : b; }      // :410, :375
+        inline float shim_abs(float s)              { return (s < 0.0f) ? -s : s; }                // :435
+
+        inline void psmin3(float *dst, const float *a, const float *b, size_t count)
+        {
+            for (size_t i = 0; i < count; ++i)
+                dst[i] = shim_smin(a[i], b[i]);
+        }
+
+        inline void psmax3(float *dst, const float *a, const float *b, size_t count)
+        {
+            for (size_t i = 0; i < count; ++i)
+                dst[i] = shim_smax(a[i], b[i]);
+        }
+
+        inline void pamin3(float *dst, const float *a, const float *b, size_t count)
+        {
+            for (size_t i = 0; i < count; ++i)
+                dst[i] = shim_abs(shim_smin(a[i], b[i]));
+        }
+
+        inline void pamax3(float *dst, const float *a, const float *b, size_t count)
+        {
+            for (size_t i = 0; i < count; ++i)
+                dst[i] = shim_abs(shim_smax(a[i], b[i]));
+        }
+
+        inline void ms_pamin3(float *dst, const float *m, const float *s, size_t count)    // :366-368
+        {
+            for (size_t i = 0; i < count; ++i)
+                dst[i] = shim_abs(shim_smin(m[i] + s[i], m[i] - s[i]));
+        }
+
+        inline void ms_pamax3(float *dst, const float *m, const float *s, size_t count)    // :373-375
+        {
+            for (size_t i = 0; i < count; ++i)
+                dst[i] = shim_abs(shim_smax(m[i] + s[i], m[i] - s[i]));
+        }
+
+        // Sidechain.cpp:231, :241 call these on the mid and side rows, ahead of a pre-equalizer only.  No recorded case has a
+        // pre-equalizer, so they are never run; they are here for the class to compile and link.
+        inline void lr_psmin3(float *dst, const float *l, const float *r, size_t count)
+        {
+            for (size_t i = 0; i < count; ++i)
+                dst[i] = shim_smin((l[i] + r[i]) * 0.5f, (l[i] - r[i]) * 0.5f);
+        }
+
+        inline void lr_psmax3(float *dst, const float *l, const float *r, size_t count)
+        {
+            for (size_t i = 0; i < count; ++i)
+                dst[i] = shim_smax((l[i] + r[i]) * 0.5f, (l[i] - r[i]) * 0.5f);
+        }
+
+        // UNPINNED, a stand-in by this project's reading.  :158-161, :171-174 h_abs_sum / h_sqr_sum(src, count): a serial
+        // float32 sum from 0, oldest sample first, each term and each partial sum rounded on its own.  lsp-dsp-lib's SIMD
+        // variants add in another order; nothing here pins which.  The stereo meters' and the Depopper's vectors use the same.
+        inline float h_abs_sum(const float *src, size_t count)
+        {
+            float sum = 0.0f;
+            for (size_t i = 0; i < count; ++i)
+                sum += fabsf(src[i]);
+            return sum;
+        }
+
+        inline float h_sqr_sum(const float *src, size_t count)
+        {
+            float sum = 0.0f;
+            for (size_t i = 0; i < count; ++i)
+                sum += src[i] * src[i];
+            return sum;
+        }
+
+        // UNPINNED, a stand-in by this project's reading.  :539 ssqrt1(out, to_do), "saturated" square root: sqrtf of the
+        // value clamped at 0, as the single-sample overload states it (:614, (rms < 0.0f) ? 0.0f : sqrtf(...)).
+        inline void ssqrt1(float *dst, size_t count)
+        {
+            for (size_t i = 0; i < count; ++i)
+                dst[i] = (dst[i] > 0.0f) ? sqrtf(dst[i]) : 0.0f;
         }
     }
 }

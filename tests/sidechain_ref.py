@@ -70,6 +70,7 @@ class Sidechains:
         self.head = np.zeros(self.C, np.int64)
         self.rms = np.zeros(self.C, f32)
         self.refresh = np.zeros(self.C, np.int64)
+        self.fresh = np.ones(self.C, bool)      # nothing was pushed into the ring yet: the only time its position is 0
         self.refreshes = []                     # (channel, samples seen by it in this object, wrapped) of every window refresh
 
     def set_params(self, params):
@@ -130,6 +131,8 @@ class Sidechains:
             sig = self.premix(in0, in1)
         x = (np.abs(sig) * self.gain[:, None]).astype(f32)
         n = x.shape[1]
+        if n > 0:
+            self.fresh[:] = False
         out, trace = np.empty((C, n), f32), np.empty((C, n), f32)
         rows = np.arange(C)
         is_rms, is_uni, is_lpf, is_peak = (self.mode == m for m in (SCM_RMS, SCM_UNIFORM, SCM_LPF, SCM_PEAK))
@@ -161,4 +164,7 @@ class Sidechains:
         return out, trace
 
     def state(self):
-        return {"rms": self.rms.copy(), "refresh": self.refresh.astype(np.uint32), "head": self.head.astype(np.uint32)}
+        """head is RawRingBuffer::position(): push() of a block that ends at the ring's end leaves it AT the capacity
+        (RawRingBuffer.cpp:118-122: it wraps only where nHead + count > nCapacity), and the next push starts over from there."""
+        head = np.where((self.head == 0) & ~self.fresh, self.cap, self.head)
+        return {"rms": self.rms.copy(), "refresh": self.refresh.astype(np.uint32), "head": head.astype(np.uint32)}

@@ -285,6 +285,15 @@ int main()
     rb.advance(2);
     rb.clear();
     printf(" %zu %g\n", rb.position(), *rb.begin());
+    // a block that ends at the ring's end leaves the position AT the capacity; a single sample then goes to the start
+    printf("ring_end %zu", rb.push(a, 4));
+    rb.push(b, 1);
+    printf(" %zu %td", rb.position(), rb.head() - rb.begin());
+    rb.push(8.0f);
+    printf(" %zu %g", rb.position(), *rb.begin());
+    rb.advance(3);
+    rb.push(b, 3);                                              // 1 + 3 + 3 = 7 > 5: wraps to 2
+    printf(" %zu\n", rb.position());
     names rn;
     rb.dump(&rn);
     printf("ring_dump");
@@ -355,6 +364,7 @@ def test_raw_ring_buffer_known_answers(probe):
     assert probe["ring_single"] == ["3", "8", "9", "1"]                                # push(8) at [2]; write(9) at [3]; advance(3): 6 % 5
     # write of 7 keeps 5: 1..4 at [1..4], 5 at [0]; the head stays at 1
     assert probe["ring_long"] == ["5", "1", "5", "1", "2", "3", "4", "2.5", "1", "0", "0", "0"]
+    assert probe["ring_end"] == ["4", "5", "5", "1", "8", "2"]
     assert probe["ring_gone"] == ["0", "1"]
 
 
