@@ -2411,6 +2411,111 @@ int mi_noise_generator_bank_get_tilt_settings(const mi_noise_generator_bank_t *b
 int mi_noise_generator_bank_get_state(mi_noise_generator_bank_t *bank, uint32_t channel, mi_noise_generator_state_t *state, void *stream);
 int mi_noise_generator_bank_set_state(mi_noise_generator_bank_t *bank, uint32_t channel, const mi_noise_generator_state_t *state, void *stream);
 
+/* ---- ADSR envelope bank (attack, hold, decay, break, slope, sustain, release curves) ------------------------------------------- */
+/*
+ * mi_adsr_bank: `channels` x lsp::dspu::ADSREnvelope (util/ADSREnvelope.h, src/main/util/ADSREnvelope.cpp).  The unit has no
+ * stream state: a sample is a function of one time value and the channel's designed record (four curves of a function tag and the
+ * six floats of gen_params_t, fHoldTime, fBreakLevel, fSustainLevel, nFlags), so one kernel over (chunk of the row, channel)
+ * serves the five array entry points, writes nothing but dst, and every call can be captured.  Float arithmetic in the
+ * reference's order with no contraction; expf in an EXP segment is the float64 exp of the float32 argument rounded once.
+ *
+ *   process          dst[i] = do_process(src[i])               :334-340   (t <= 0, t >= 1: +0; a NaN t reaches the release curve)
+ *   process_mul      dst[i] *= do_process(src[i])              :342-348
+ *   generate         dst[i] = the curve at t_i                 :385-433   t_0 = start, t_i = start + float(i) * step
+ *   generate_mul     src == NULL: dst[i] *= the curve at t_i   :435-483   (hold leaves dst[i]; before attack and after release
+ *                    src != NULL: dst[i] = src[i] * the curve  :485-533    store 0.0f in every flavour)
+ *
+ * The reference's generate loops only move forward through the stages 0 before attack, 1 attack, 2 hold, 3 decay, 4 slope,
+ * 5 sustain, 6 release, 7 after; in closed form sample i is at stage max(floor, stage(t_i)) with floor = stage(start) for a
+ * negative step and 0 otherwise, and a NaN t is at stage 7.  start and step are host arrays of one float per channel; they reach
+ * the device as arguments of a small launch on the call's stream ahead of the kernel, so a captured call replays the values of
+ * capture time.  A bank's calls belong on one stream at a time.
+ * Defined where the reference is not:
+ *   - a NaN given to a setter (lsp_limit lets it through) is MI_EINVAL and nothing changes;
+ *   - a function outside MI_ADSR_NONE .. MI_ADSR_EXP runs as MI_ADSR_NONE (the reference's default: label);
+ *   - count == 0 succeeds and launches nothing; dst and src may be the same rows with the same stride, and must not overlap otherwise.
+ */
+typedef struct mi_adsr_bank mi_adsr_bank_t;
+enum { MI_ADSR_NONE, MI_ADSR_LINE, MI_ADSR_LINE2, MI_ADSR_CUBIC, MI_ADSR_QUADRO, MI_ADSR_EXP };         /* function_t, .h:41-49 */
+enum { MI_ADSR_ATTACK, MI_ADSR_DECAY, MI_ADSR_SLOPE, MI_ADSR_RELEASE, MI_ADSR_PARTS };                /* part_t, .h:59-67 */
+enum { MI_ADSR_USE_HOLD = 1, MI_ADSR_USE_BREAK = 2, MI_ADSR_RECONFIGURE = 4 };                      /* flags_t, .h:52-57 */
+/* curve_t without pGenerator.  params by function: NONE { fT, fK, fB }; LINE, LINE2 { fT2, fK1, fB1, fK2, fB2 }; CUBIC, QUADRO
+ * { fT0, fK[5] }; EXP { fT0, fKT, fA[2], fB[2] } */
+typedef struct { float time, curve; uint32_t function; float params[6]; } mi_adsr_curve_t;
+typedef struct mi_adsr_settings
+{
+    mi_adsr_curve_t curve[MI_ADSR_PARTS];
+    float           hold_time, break_level, sustain_level;
+    uint32_t        flags;
+} mi_adsr_settings_t;
+/* The setters of .h:161-188 by number: a is the value (a time, a curve, a level, a function, or != 0 for enabled); the combined
+ * setters take (time, curve, function) or (time or level, enabled) in a, b, c */
+enum
+{
+    MI_ADSR_SET_ATTACK_TIME, MI_ADSR_SET_HOLD_TIME, MI_ADSR_SET_DECAY_TIME, MI_ADSR_SET_SLOPE_TIME, MI_ADSR_SET_RELEASE_TIME,
+    MI_ADSR_SET_ATTACK_CURVE, MI_ADSR_SET_DECAY_CURVE, MI_ADSR_SET_SLOPE_CURVE, MI_ADSR_SET_RELEASE_CURVE,
+    MI_ADSR_SET_ATTACK_FUNCTION, MI_ADSR_SET_DECAY_FUNCTION, MI_ADSR_SET_SLOPE_FUNCTION, MI_ADSR_SET_RELEASE_FUNCTION,
+    MI_ADSR_SET_BREAK_LEVEL, MI_ADSR_SET_SUSTAIN_LEVEL, MI_ADSR_SET_HOLD_ENABLED, MI_ADSR_SET_BREAK_ENABLED,
+    MI_ADSR_SET_ATTACK, MI_ADSR_SET_HOLD, MI_ADSR_SET_DECAY, MI_ADSR_SET_BREAK, MI_ADSR_SET_SLOPE, MI_ADSR_SET_RELEASE
+};
+/* construct(), the setters and update_settings() (:40-293) on a mi_adsr_settings_t, and do_process(t) of a designed one with the
+ * device's expf rule: host only, no device */
+int mi_adsr_settings_init(mi_adsr_settings_t *s);
+int mi_adsr_settings_set(mi_adsr_settings_t *s, uint32_t setter, double a, double b, double c);
+int mi_adsr_settings_update(mi_adsr_settings_t *s);
+int mi_adsr_settings_process(const mi_adsr_settings_t *s, float t, float *value);
+/* interpolation::hermite_cubic and hermite_quadro (src/main/misc/interpolation.cpp:112-177): p[4] and p[5] */
+int mi_interpolation_hermite_cubic(float *p, float x0, float y0, float k0, float x1, float y1, float k1);
+int mi_interpolation_hermite_quadro(float *p, float x0, float y0, float k0, float x1, float y1, float k1, float x2, float y2);
+
+int mi_adsr_bank_create(mi_adsr_bank_t **bank, uint32_t channels);                          /* construct() of every channel */
+int mi_adsr_bank_destroy(mi_adsr_bank_t *bank);
+/* One setter of one channel (MI_ADSR_SET_*, as mi_adsr_settings_set), and by name */
+int mi_adsr_bank_set(mi_adsr_bank_t *bank, uint32_t channel, uint32_t setter, double a, double b, double c);
+int mi_adsr_bank_set_attack_time(mi_adsr_bank_t *bank, uint32_t channel, float value);
+int mi_adsr_bank_set_hold_time(mi_adsr_bank_t *bank, uint32_t channel, float value);
+int mi_adsr_bank_set_decay_time(mi_adsr_bank_t *bank, uint32_t channel, float value);
+int mi_adsr_bank_set_slope_time(mi_adsr_bank_t *bank, uint32_t channel, float value);
+int mi_adsr_bank_set_release_time(mi_adsr_bank_t *bank, uint32_t channel, float value);     /* set_relese_time, .h:165 */
+int mi_adsr_bank_set_attack_curve(mi_adsr_bank_t *bank, uint32_t channel, float value);
+int mi_adsr_bank_set_decay_curve(mi_adsr_bank_t *bank, uint32_t channel, float value);
+int mi_adsr_bank_set_slope_curve(mi_adsr_bank_t *bank, uint32_t channel, float value);
+int mi_adsr_bank_set_release_curve(mi_adsr_bank_t *bank, uint32_t channel, float value);
+int mi_adsr_bank_set_attack_function(mi_adsr_bank_t *bank, uint32_t channel, uint32_t function);
+int mi_adsr_bank_set_decay_function(mi_adsr_bank_t *bank, uint32_t channel, uint32_t function);
+int mi_adsr_bank_set_slope_function(mi_adsr_bank_t *bank, uint32_t channel, uint32_t function);
+int mi_adsr_bank_set_release_function(mi_adsr_bank_t *bank, uint32_t channel, uint32_t function);
+int mi_adsr_bank_set_break_level(mi_adsr_bank_t *bank, uint32_t channel, float value);
+int mi_adsr_bank_set_sustain_level(mi_adsr_bank_t *bank, uint32_t channel, float value);
+int mi_adsr_bank_set_hold_enabled(mi_adsr_bank_t *bank, uint32_t channel, int enabled);
+int mi_adsr_bank_set_break_enabled(mi_adsr_bank_t *bank, uint32_t channel, int enabled);
+int mi_adsr_bank_set_attack(mi_adsr_bank_t *bank, uint32_t channel, float time, float curve, uint32_t function);
+int mi_adsr_bank_set_hold(mi_adsr_bank_t *bank, uint32_t channel, float time, int enabled);
+int mi_adsr_bank_set_decay(mi_adsr_bank_t *bank, uint32_t channel, float time, float curve, uint32_t function);
+int mi_adsr_bank_set_break(mi_adsr_bank_t *bank, uint32_t channel, float level, int enabled);
+int mi_adsr_bank_set_slope(mi_adsr_bank_t *bank, uint32_t channel, float time, float curve, uint32_t function);
+int mi_adsr_bank_set_release(mi_adsr_bank_t *bank, uint32_t channel, float time, float curve, uint32_t function);
+/* A channel's settings as they stand (the C++ class designs elsewhere and sets them): a NaN member is MI_EINVAL */
+int mi_adsr_bank_set_settings(mi_adsr_bank_t *bank, uint32_t channel, const mi_adsr_settings_t *settings);
+int mi_adsr_bank_get_settings(const mi_adsr_bank_t *bank, uint32_t channel, mi_adsr_settings_t *settings);
+int mi_adsr_bank_needs_update(const mi_adsr_bank_t *bank, uint32_t channel, int *yes);      /* nFlags & F_RECONFIGURE */
+/* update_settings() of every channel that needs it, and changed records go to the device: outside a capture (MI_ESTATE inside
+ * one).  The five operations run it first, as the reference's do. */
+int mi_adsr_bank_update_settings(mi_adsr_bank_t *bank, void *stream);
+/* A channel that is switched off is an object nobody calls: its row is neither read nor written.  Every channel is on after
+ * create(); a bank with no channel on launches nothing. */
+int mi_adsr_bank_set_row_enabled(mi_adsr_bank_t *bank, uint32_t channel, int enabled);
+/* dst [channels][dst_stride] and src [channels][src_stride] are device rows; start and step are host arrays [channels].
+ * generate_mul: src == NULL is the in-place flavour (src_stride is not looked at). */
+int mi_adsr_bank_process(mi_adsr_bank_t *bank, float *dst, const float *src, size_t count, size_t dst_stride, size_t src_stride,
+                         void *stream);
+int mi_adsr_bank_process_mul(mi_adsr_bank_t *bank, float *dst, const float *src, size_t count, size_t dst_stride, size_t src_stride,
+                             void *stream);
+int mi_adsr_bank_generate(mi_adsr_bank_t *bank, float *dst, const float *start, const float *step, size_t count, size_t dst_stride,
+                          void *stream);
+int mi_adsr_bank_generate_mul(mi_adsr_bank_t *bank, float *dst, const float *src, const float *start, const float *step, size_t count,
+                              size_t dst_stride, size_t src_stride, void *stream);
+
 /*
  * Host-only introspection of the per-section device table (no GPU needed): the
  * chunk-parallel form of the TDF-II section used by the kernel.

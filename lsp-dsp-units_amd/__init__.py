@@ -12,7 +12,7 @@ Import with ``importlib.import_module("lsp-dsp-units_amd")`` (the directory
 name carries the reference's name and is not a Python identifier).
 """
 from .capi import LIB_PATH, MiError, check, lib          # noqa: F401
-from .units import (AnalyzerBank, AutoGainBank, BiquadBank, BypassBank, Comm, CompressorBank, ConvolverBank, CorrelometerBank, CrossfadeBank, CrossoverBank, DelayBank, DepopperBank, DeviceBuffer, DynFilterBank, DynamicDelayBank, DynamicProcessorBank, EqualizerBank,  # noqa: F401
+from .units import (ADSREnvelopeBank, AnalyzerBank, AutoGainBank, BiquadBank, BypassBank, Comm, CompressorBank, ConvolverBank, CorrelometerBank, CrossfadeBank, CrossoverBank, DelayBank, DepopperBank, DeviceBuffer, DynFilterBank, DynamicDelayBank, DynamicProcessorBank, EqualizerBank,  # noqa: F401
                     ExpanderBank, GateBank, ILUFSBank, LCGBank, LimiterBank, LoudnessBank, MLSBank, NoiseGeneratorBank, OscillatorBank, OversamplerBank, PanometerBank,
                     PeakMeterBank, RingBank, SidechainBank, SimpleAutoGainBank,
                     SpectralBank, SpectralTiltBank, SurgeProtectorBank, SplitterBank, TruePeakBank, VelvetBank, crossover_fft_mask,

@@ -261,6 +261,16 @@ class OscillatorSettings(ctypes.Structure):
                 ("phase_known", c_uint32), ("phase", c_uint32), ("unset_rate_ok", c_uint32)]
 
 
+class AdsrCurve(ctypes.Structure):
+    """mi_adsr_curve_t: fTime, fCurve, enFunction and the six floats of gen_params_t."""
+    _fields_ = [("time", c_float), ("curve", c_float), ("function", c_uint32), ("params", c_float * 6)]
+
+
+class AdsrSettings(ctypes.Structure):
+    """mi_adsr_settings_t: the members of one lsp::dspu::ADSREnvelope."""
+    _fields_ = [("curve", AdsrCurve * 4), ("hold_time", c_float), ("break_level", c_float), ("sustain_level", c_float), ("flags", c_uint32)]
+
+
 class LcgState(ctypes.Structure):
     """mi_lcg_state_t: the members of one lsp::dspu::Randomizer."""
     _fields_ = [("last", c_uint32 * 4), ("mul1", c_uint32 * 4), ("mul2", c_uint32 * 4), ("add", c_uint32 * 4), ("buf_id", c_uint32)]
@@ -768,6 +778,47 @@ PROTOTYPES = {
     "mi_dyndelay_bank_write_line": (c_int, [c_void_p, c_uint32, c_void_p, c_size_t, c_size_t, c_void_p]),
     "mi_dyndelay_bank_count_steps": (c_int, [c_void_p, c_int, c_void_p]),
     "mi_dyndelay_bank_steps": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), c_void_p]),
+    "mi_adsr_settings_init": (c_int, [POINTER(AdsrSettings)]),
+    "mi_adsr_settings_set": (c_int, [POINTER(AdsrSettings), c_uint32, c_double, c_double, c_double]),
+    "mi_adsr_settings_update": (c_int, [POINTER(AdsrSettings)]),
+    "mi_adsr_settings_process": (c_int, [POINTER(AdsrSettings), c_float, POINTER(c_float)]),
+    "mi_interpolation_hermite_cubic": (c_int, [c_void_p] + [c_float] * 6),
+    "mi_interpolation_hermite_quadro": (c_int, [c_void_p] + [c_float] * 8),
+    "mi_adsr_bank_create": (c_int, [POINTER(c_void_p), c_uint32]),
+    "mi_adsr_bank_destroy": (c_int, [c_void_p]),
+    "mi_adsr_bank_set": (c_int, [c_void_p, c_uint32, c_uint32, c_double, c_double, c_double]),
+    "mi_adsr_bank_set_attack_time": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_adsr_bank_set_hold_time": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_adsr_bank_set_decay_time": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_adsr_bank_set_slope_time": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_adsr_bank_set_release_time": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_adsr_bank_set_attack_curve": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_adsr_bank_set_decay_curve": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_adsr_bank_set_slope_curve": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_adsr_bank_set_release_curve": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_adsr_bank_set_break_level": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_adsr_bank_set_sustain_level": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_adsr_bank_set_attack_function": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_adsr_bank_set_decay_function": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_adsr_bank_set_slope_function": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_adsr_bank_set_release_function": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_adsr_bank_set_hold_enabled": (c_int, [c_void_p, c_uint32, c_int]),
+    "mi_adsr_bank_set_break_enabled": (c_int, [c_void_p, c_uint32, c_int]),
+    "mi_adsr_bank_set_attack": (c_int, [c_void_p, c_uint32, c_float, c_float, c_uint32]),
+    "mi_adsr_bank_set_decay": (c_int, [c_void_p, c_uint32, c_float, c_float, c_uint32]),
+    "mi_adsr_bank_set_slope": (c_int, [c_void_p, c_uint32, c_float, c_float, c_uint32]),
+    "mi_adsr_bank_set_release": (c_int, [c_void_p, c_uint32, c_float, c_float, c_uint32]),
+    "mi_adsr_bank_set_hold": (c_int, [c_void_p, c_uint32, c_float, c_int]),
+    "mi_adsr_bank_set_break": (c_int, [c_void_p, c_uint32, c_float, c_int]),
+    "mi_adsr_bank_set_settings": (c_int, [c_void_p, c_uint32, POINTER(AdsrSettings)]),
+    "mi_adsr_bank_get_settings": (c_int, [c_void_p, c_uint32, POINTER(AdsrSettings)]),
+    "mi_adsr_bank_needs_update": (c_int, [c_void_p, c_uint32, POINTER(c_int)]),
+    "mi_adsr_bank_update_settings": (c_int, [c_void_p, c_void_p]),
+    "mi_adsr_bank_set_row_enabled": (c_int, [c_void_p, c_uint32, c_int]),
+    "mi_adsr_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_adsr_bank_process_mul": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_adsr_bank_generate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
+    "mi_adsr_bank_generate_mul": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_oscillator_settings_init": (c_int, [POINTER(OscillatorSettings)]),
     "mi_oscillator_settings_set": (c_int, [POINTER(OscillatorSettings), c_uint32, c_double, c_double]),
     "mi_oscillator_settings_update": (c_int, [POINTER(OscillatorSettings)]),

@@ -768,6 +768,90 @@ class OscillatorBank:
             pass
 
 
+class ADSREnvelopeBank:
+    """`channels` x lsp::dspu::ADSREnvelope (mi_adsr_bank_*): envelope curves over rows of time values, or generated from a start
+    and a step per channel.  The unit has no state; every call can be captured (generate* replay the start and step of capture time)."""
+    NONE, LINE, LINE2, CUBIC, QUADRO, EXP = range(6)
+    SETTERS = ("attack_time", "hold_time", "decay_time", "slope_time", "release_time", "attack_curve", "decay_curve", "slope_curve",
+               "release_curve", "attack_function", "decay_function", "slope_function", "release_function", "break_level",
+               "sustain_level", "hold_enabled", "break_enabled", "attack", "hold", "decay", "break", "slope", "release")
+
+    def __init__(self, channels):
+        h = c_void_p()
+        check(lib.mi_adsr_bank_create(byref(h), channels))
+        self.handle, self.channels = h, channels
+
+    def set(self, channel, setter, a=0.0, b=0.0, c=0.0):
+        """One setter by its MI_ADSR_SET_* number."""
+        check(lib.mi_adsr_bank_set(self.handle, channel, setter, float(a), float(b), float(c)))
+
+    def __getattr__(self, name):
+        # set_<name>(channel, value...): the reference's setters, each one its own C entry
+        if name.startswith("set_") and name[4:] in self.SETTERS:
+            fn = getattr(lib, "mi_adsr_bank_" + name)
+            return lambda channel, *values: check(fn(self.handle, channel, *values))
+        raise AttributeError(name)
+
+    def needs_update(self, channel):
+        v = c_int()
+        check(lib.mi_adsr_bank_needs_update(self.handle, channel, byref(v)))
+        return bool(v.value)
+
+    def update_settings(self, stream=None):
+        check(lib.mi_adsr_bank_update_settings(self.handle, _stream(stream)))
+
+    def get_settings(self, channel):
+        from .capi import AdsrSettings
+        s = AdsrSettings()
+        check(lib.mi_adsr_bank_get_settings(self.handle, channel, byref(s)))
+        return s
+
+    def set_settings(self, channel, settings):
+        check(lib.mi_adsr_bank_set_settings(self.handle, channel, byref(settings)))
+
+    def set_row_enabled(self, channel, enabled=True):
+        check(lib.mi_adsr_bank_set_row_enabled(self.handle, channel, 1 if enabled else 0))
+
+    def _pairs(self, start, step):
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(start, np.float32), (self.channels,)))
+        b = np.ascontiguousarray(np.broadcast_to(np.asarray(step, np.float32), (self.channels,)))
+        return a, b
+
+    def process(self, dst, src, count, dst_stride=None, src_stride=None, stream=None):
+        """dst[i] = do_process(src[i]); dst may be src (same stride)."""
+        check(lib.mi_adsr_bank_process(self.handle, _opt(dst), _opt(src), count, count if dst_stride is None else dst_stride,
+                                       count if src_stride is None else src_stride, _stream(stream)))
+
+    def process_mul(self, dst, src, count, dst_stride=None, src_stride=None, stream=None):
+        """dst[i] *= do_process(src[i])."""
+        check(lib.mi_adsr_bank_process_mul(self.handle, _opt(dst), _opt(src), count, count if dst_stride is None else dst_stride,
+                                           count if src_stride is None else src_stride, _stream(stream)))
+
+    def generate(self, dst, start, step, count, dst_stride=None, stream=None):
+        """The curve at t_i = start + i * step, one start and step per channel (a scalar serves all)."""
+        a, b = self._pairs(start, step)
+        check(lib.mi_adsr_bank_generate(self.handle, _opt(dst), a.ctypes.data_as(c_void_p), b.ctypes.data_as(c_void_p), count,
+                                        count if dst_stride is None else dst_stride, _stream(stream)))
+
+    def generate_mul(self, dst, start, step, count, src=None, dst_stride=None, src_stride=None, stream=None):
+        """dst[i] *= the curve (src None) or dst[i] = src[i] * the curve; hold leaves or copies the sample, outside [0, 1] stores 0."""
+        a, b = self._pairs(start, step)
+        check(lib.mi_adsr_bank_generate_mul(self.handle, _opt(dst), _opt(src), a.ctypes.data_as(c_void_p), b.ctypes.data_as(c_void_p), count,
+                                            count if dst_stride is None else dst_stride, count if src_stride is None else src_stride,
+                                            _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            lib.mi_adsr_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class LCGBank:
     """`channels` x lsp::dspu::LCG (mi_lcg_bank_*): white noise of four distributions; the Randomizers live on the device."""
     OVERWRITE, ADD, MUL = 0, 1, 2
