@@ -21,9 +21,15 @@ their followers, hold, hysteresis, update_settings and scalar gain formulas
 Three more likewise, Limiter, AutoGain and SimpleAutoGain (Makefile -> _ref/gain_ref and its
 sanitizer twin _ref/gain_ref_san, driver gain_driver.cpp; tests/golden/
 limiter_ref_vectors.npz and autogain_ref_vectors.npz, tests/test_gain_reference_*.py).
+Filter, FilterBank and DynamicFilters likewise (Makefile -> _ref/filter_ref, _ref/dynfilter_ref and
+their sanitizer twins, drivers filter_driver.cpp and dynfilter_driver.cpp, stand-ins in
+ref_overlay/filters/; tests/golden/filter_ref_*.npz and dynfilter_ref_*.npz,
+tests/test_filter_reference_*.py and tests/test_dynfilter_reference_*.py): the designer,
+Filter::limit, the bank's packing and clear / keep rules, the dynamic cascade builders.
 It does not pin lsp-dsp-lib's array primitives or their SIMD variants (dsp::max_index
-and dsp::abs_mul3 of the Limiter among them), the Sidechain's detectors, the Lanczos
-tables or the IIR streaming arithmetic.
+and dsp::abs_mul3 of the Limiter among them), the order of the Sidechain's refresh sums,
+the Lanczos tables or the arithmetic inside an IIR section (the Sidechain's detectors
+themselves have been pinned since: _ref/sidechain_ref).
 """
 from .binding import *  # noqa: F401,F403
 from . import spectral  # noqa: F401,E402

@@ -31,8 +31,9 @@
  *  (3) on the device, tests/hip/serial_biquad.hip runs this recurrence operation for operation and equals this
  *      file bit for bit (tests/test_biquad_gpu.py::test_device_twin_equals_the_oracle): the GPU's float32
  *      arithmetic is the one written here.
- * The README filter values in tests/golden/filter_anchors.json were recorded by the survey probe with stand-in
- * headers and a scalar shim: a regression check of the designer, not a pin of this arithmetic.
+ * The README filter values in tests/golden/filter_anchors.json are a regression check of the designer, not a pin of this
+ * arithmetic; they now also follow from tests/golden/filter_ref_designs.npz and filter_ref_streams.npz, recorded from the
+ * reference's own Filter and FilterBank over a stand-in that IS this recurrence (oracle/ref_overlay/filters).
  *
  * Build: see oracle/Makefile (gcc -O2 -ffp-contract=off so the rounding is the
  * same on every host).

@@ -446,14 +446,20 @@ class DynamicFilters:
         p = self.params[fid]
         t = p["nType"]
         T, B = cascades(t, p["nSlope"], p["fFreq2"], p["fQuality"], gains)
-        with np.errstate(all="ignore"):                      # kf of :223-228
-            if t <= fd.FLT_MT_AMPLIFIER:
-                kf = F(0.95)
-            elif t & 1:
-                kf = F(1.0) / np.tan(p["fFreq"] * PI / F(self.sample_rate), dtype=np.float32)
-            else:
-                kf = F(TWO_PI / F(self.sample_rate))
+        with np.errstate(all="ignore"):
+            kf = self.kf(fid)
             return bilinear(T, B, kf) if (t & 1) else matched(T, B, p["fFreq"], kf)
+
+    def kf(self, fid):
+        """What process() hands the transform (:222-226): 0.95 for the amplifiers, the bilinear factor, or 2 pi / sample rate."""
+        p = self.params[fid]
+        t = p["nType"]
+        with np.errstate(all="ignore"):
+            if t <= fd.FLT_MT_AMPLIFIER:
+                return F(0.95)
+            if t & 1:
+                return F(F(1.0) / np.tan(p["fFreq"] * PI / F(self.sample_rate), dtype=np.float32))
+            return F(TWO_PI / F(self.sample_rate))
 
     def bypassed(self, fid):
         p = self.params[fid] if fid < self.n else None

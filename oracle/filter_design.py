@@ -812,5 +812,7 @@ def freq_chart(params, sample_rate, freqs):
             mag = (F(1.0) / (gamma * gamma + delta * delta)).astype(np.float32)
             re = (mag * (alpha * gamma - beta * delta)).astype(np.float32)
             im = (mag * (alpha * delta + beta * gamma)).astype(np.float32)
-            h = (h * (re + 1j * im)).astype(np.complex64)
+            # the product as Filter.cpp:438-439 writes it, every term rounded to float on its own (a complex64 product may fuse)
+            hr, hi = h.real.astype(np.float32), h.imag.astype(np.float32)
+            h = ((hr * re - hi * im).astype(np.float32) + 1j * (hr * im + hi * re).astype(np.float32)).astype(np.complex64)
     return h, mode

@@ -8,6 +8,7 @@ import oracle
 from oracle import dynamic_filters as df
 from oracle import filter_design as fd
 from conftest import IIR_EXACT_FACTOR, IIR_REF_FACTOR, NOISE_FLOOR, TOL, record_parity
+from dynfilter_reference import check      # conftest.assert_iir_parity's rule with a coefficient allowance
 
 pytestmark = pytest.mark.gpu
 SR = 48000
@@ -24,26 +25,6 @@ def gains(rng, C, n, kind):
     else:                                                    # sample-to-sample changes
         g = np.exp(rng.uniform(-1.0, 1.0, (C, n)))
     return g.astype(np.float32)
-
-
-def check(y, ref, exact, what, coef_tol=0.0):
-    """conftest.assert_iir_parity's rule (the recursion's own float32 noise is the yardstick).
-    coef_tol: how far the coefficient sets of the device and of the oracle may differ (matched-Z types: the float
-    amplitude normalisation next to z = 1, Filter.cpp:2369-2411, turns the last bits of expf into 1e-4 of a numerator --
-    tests/test_oracle_dynamic_filters.py::test_product_builders_match_the_oracle shows the same between two host libms)."""
-    peak = max(float(np.abs(exact).max()), 1e-30)
-    noise = float(np.abs(ref - exact).max()) / peak
-    e32 = float(np.abs(y - ref).max()) / peak
-    e64 = float(np.abs(y - exact).max()) / peak
-    msg = "%s: vs oracle %.2e, vs float64 %.2e, oracle's own noise %.2e" % (what, e32, e64, noise)
-    assert np.all(np.isfinite(y)), msg
-    # the coefficients themselves come from two libms (device / numpy): one part in 1e6 of the coefficients on top of the
-    # recursion's noise
-    if noise <= NOISE_FLOOR:
-        assert e32 <= 2 * TOL + coef_tol, msg
-    else:
-        assert e64 <= max(2 * TOL, IIR_EXACT_FACTOR * noise) + coef_tol and e32 <= max(2 * TOL, IIR_REF_FACTOR * noise) + coef_tol, msg
-    return e32, noise
 
 
 @pytest.mark.parametrize("t", TYPES)
