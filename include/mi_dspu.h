@@ -2516,6 +2516,50 @@ int mi_adsr_bank_generate(mi_adsr_bank_t *bank, float *dst, const float *start, 
 int mi_adsr_bank_generate_mul(mi_adsr_bank_t *bank, float *dst, const float *src, const float *start, const float *step, size_t count,
                               size_t dst_stride, size_t src_stride, void *stream);
 
+/* ---- MeterGraph bank (a full-rate row decimated into display frames) ----------------------------------------------------------- */
+/*
+ * mi_metergraph_bank: `channels` x lsp::dspu::MeterGraph (util/MeterGraph.h, src/main/util/MeterGraph.cpp).  Every channel cuts its
+ * row into frames of `period` samples, reduces each by its method and appends the result to a ring of `frames` words on the
+ * device; ring, fCurrent, nCount and nHead are the reference's in every bit (DESIGN.md 3.30 lists the quirks that are kept).
+ *   - one process() call is one process(s, n) (gains == NULL) or process(s, gain, n) of every channel;
+ *   - create() leaves every channel as construct() does (ABS_MAXIMUM, period 1, no ring); a channel needs init() before the bank
+ *     processes: MI_ESTATE otherwise;
+ *   - the reference loops forever on a period of 0: init() and set_period() refuse it with MI_EINVAL;
+ *   - init(), the setters, fill() and clear() pend until update_settings(), which process(), process_value(), read(), level(),
+ *     get_state() and set_state() run first; with something pending that is MI_ESTATE on a stream being captured;
+ *   - process(), process_value(), read() and level() are capturable: the kernels keep the state, so a replay appends again.
+ */
+typedef struct mi_metergraph_bank mi_metergraph_bank_t;
+enum { MI_MM_ABS_MAXIMUM, MI_MM_ABS_MINIMUM, MI_MM_SIGN_MAXIMUM, MI_MM_SIGN_MINIMUM, MI_MM_PEAK };      /* meter_method_t, .h:33-63 */
+typedef struct { float current; uint32_t count; uint32_t head; } mi_metergraph_state_t;                /* fCurrent, nCount, nHead */
+typedef struct { uint32_t method, period, frames; float default_value; } mi_metergraph_params_t;       /* enMethod, nPeriod, nCapacity, fDefault */
+int mi_metergraph_bank_create(mi_metergraph_bank_t **bank, uint32_t channels, uint32_t max_frames);
+int mi_metergraph_bank_destroy(mi_metergraph_bank_t *bank);
+/* init(frames, period, default_value), :55-68: 1 <= frames <= max_frames, 1 <= period < 2^32; the ring is filled with the default */
+int mi_metergraph_bank_init(mi_metergraph_bank_t *bank, uint32_t channel, size_t frames, size_t period, float default_value);
+/* a method outside the enum runs as MI_MM_ABS_MAXIMUM (the reference's default: label) */
+int mi_metergraph_bank_set_method(mi_metergraph_bank_t *bank, uint32_t channel, uint32_t method);
+int mi_metergraph_bank_set_period(mi_metergraph_bank_t *bank, uint32_t channel, size_t period);
+int mi_metergraph_bank_set_default_value(mi_metergraph_bank_t *bank, uint32_t channel, float value);
+/* fill(level) and clear() = fill(fDefault): the ring's words and nHead = 0; fCurrent and nCount stay.  channel UINT32_MAX: all */
+int mi_metergraph_bank_fill(mi_metergraph_bank_t *bank, uint32_t channel, float level);
+int mi_metergraph_bank_clear(mi_metergraph_bank_t *bank, uint32_t channel);
+int mi_metergraph_bank_update_settings(mi_metergraph_bank_t *bank, void *stream);
+int mi_metergraph_bank_get_params(const mi_metergraph_bank_t *bank, uint32_t channel, mi_metergraph_params_t *params);
+/* ring: NULL, or a HOST array of the channel's `frames` words in storage order.  set_state: head < frames */
+int mi_metergraph_bank_get_state(mi_metergraph_bank_t *bank, uint32_t channel, mi_metergraph_state_t *state, float *ring, void *stream);
+int mi_metergraph_bank_set_state(mi_metergraph_bank_t *bank, uint32_t channel, const mi_metergraph_state_t *state, const float *ring,
+                                 void *stream);
+/* src [channels][stride] device rows, read only; gains: NULL, or a DEVICE array of `channels` floats; count < 2^31 */
+int mi_metergraph_bank_process(mi_metergraph_bank_t *bank, const float *src, const float *gains, size_t count, size_t stride,
+                               void *stream);
+/* process(sample) of every channel, :70-111: values is a device array of `channels` floats */
+int mi_metergraph_bank_process_value(mi_metergraph_bank_t *bank, const float *values, void *stream);
+/* read(dst, count), :246-258, of every channel into dst [channels][stride]: the default ahead of the frames where count exceeds
+ * the channel's frames, then the newest frames, oldest first.  level(): the newest frame, levels a device array [channels]. */
+int mi_metergraph_bank_read(mi_metergraph_bank_t *bank, float *dst, size_t count, size_t stride, void *stream);
+int mi_metergraph_bank_level(mi_metergraph_bank_t *bank, float *levels, void *stream);
+
 /*
  * Host-only introspection of the per-section device table (no GPU needed): the
  * chunk-parallel form of the TDF-II section used by the kernel.

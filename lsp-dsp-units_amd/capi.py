@@ -194,6 +194,16 @@ class PeakMeterState(ctypes.Structure):
     _fields_ = [("peak", c_float), ("counter", c_uint32)]
 
 
+class MeterGraphState(ctypes.Structure):
+    """mi_metergraph_state_t: fCurrent, nCount, and the ring's nHead."""
+    _fields_ = [("current", c_float), ("count", c_uint32), ("head", c_uint32)]
+
+
+class MeterGraphParams(ctypes.Structure):
+    """mi_metergraph_params_t: enMethod, nPeriod, the ring's nCapacity, fDefault."""
+    _fields_ = [("method", c_uint32), ("period", c_uint32), ("frames", c_uint32), ("default_value", c_float)]
+
+
 class SurgeParams(ctypes.Structure):
     """mi_surge_params_t: nTransitionMax, nShutdownMax, fOnThreshold, fOffThreshold."""
     _fields_ = [("transition_max", c_uint32), ("shutdown_max", c_uint32), ("on_threshold", c_float), ("off_threshold", c_float)]
@@ -819,6 +829,22 @@ PROTOTYPES = {
     "mi_adsr_bank_process_mul": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
     "mi_adsr_bank_generate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
     "mi_adsr_bank_generate_mul": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]),
+    "mi_metergraph_bank_create": (c_int, [POINTER(c_void_p), c_uint32, c_uint32]),
+    "mi_metergraph_bank_destroy": (c_int, [c_void_p]),
+    "mi_metergraph_bank_init": (c_int, [c_void_p, c_uint32, c_size_t, c_size_t, c_float]),
+    "mi_metergraph_bank_set_method": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_metergraph_bank_set_period": (c_int, [c_void_p, c_uint32, c_size_t]),
+    "mi_metergraph_bank_set_default_value": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_metergraph_bank_fill": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_metergraph_bank_clear": (c_int, [c_void_p, c_uint32]),
+    "mi_metergraph_bank_update_settings": (c_int, [c_void_p, c_void_p]),
+    "mi_metergraph_bank_get_params": (c_int, [c_void_p, c_uint32, POINTER(MeterGraphParams)]),
+    "mi_metergraph_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(MeterGraphState), c_void_p, c_void_p]),
+    "mi_metergraph_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(MeterGraphState), c_void_p, c_void_p]),
+    "mi_metergraph_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
+    "mi_metergraph_bank_process_value": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "mi_metergraph_bank_read": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
+    "mi_metergraph_bank_level": (c_int, [c_void_p, c_void_p, c_void_p]),
     "mi_oscillator_settings_init": (c_int, [POINTER(OscillatorSettings)]),
     "mi_oscillator_settings_set": (c_int, [POINTER(OscillatorSettings), c_uint32, c_double, c_double]),
     "mi_oscillator_settings_update": (c_int, [POINTER(OscillatorSettings)]),

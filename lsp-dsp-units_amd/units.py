@@ -2487,6 +2487,84 @@ class PeakMeterBank:
             pass
 
 
+class MeterGraphBank:
+    """`channels` x lsp::dspu::MeterGraph (mi_metergraph_bank_*): full-rate rows decimated into rings of display frames on the
+    device.  Methods: ABS_MAXIMUM .. PEAK as meter_method_t has them."""
+    ALL = 0xFFFFFFFF
+    ABS_MAXIMUM, ABS_MINIMUM, SIGN_MAXIMUM, SIGN_MINIMUM, PEAK = range(5)
+
+    def __init__(self, channels, max_frames):
+        h = c_void_p()
+        check(lib.mi_metergraph_bank_create(byref(h), channels, max_frames))
+        self.handle, self.channels, self.max_frames = h, channels, max_frames
+
+    def init(self, channel, frames, period, default_value=0.0):
+        check(lib.mi_metergraph_bank_init(self.handle, channel, frames, period, float(default_value)))
+
+    def set_method(self, channel, method):
+        check(lib.mi_metergraph_bank_set_method(self.handle, channel, method))
+
+    def set_period(self, channel, period):
+        check(lib.mi_metergraph_bank_set_period(self.handle, channel, period))
+
+    def set_default_value(self, channel, value):
+        check(lib.mi_metergraph_bank_set_default_value(self.handle, channel, float(value)))
+
+    def fill(self, level, channel=ALL):
+        check(lib.mi_metergraph_bank_fill(self.handle, channel, float(level)))
+
+    def clear(self, channel=ALL):
+        check(lib.mi_metergraph_bank_clear(self.handle, channel))
+
+    def update_settings(self, stream=None):
+        check(lib.mi_metergraph_bank_update_settings(self.handle, _stream(stream)))
+
+    def get_params(self, channel):
+        from .capi import MeterGraphParams
+        p = MeterGraphParams()
+        check(lib.mi_metergraph_bank_get_params(self.handle, channel, byref(p)))
+        return {"method": p.method, "period": p.period, "frames": p.frames, "default_value": np.float32(p.default_value)}
+
+    def get_state(self, channel, stream=None):
+        """fCurrent, nCount, nHead and the ring's words in storage order."""
+        from .capi import MeterGraphState
+        s = MeterGraphState()
+        ring = np.zeros(max(1, self.get_params(channel)["frames"]), np.float32)
+        check(lib.mi_metergraph_bank_get_state(self.handle, channel, byref(s), ring.ctypes.data_as(c_void_p), _stream(stream)))
+        return {"current": np.float32(s.current), "count": s.count, "head": s.head, "ring": ring[:self.get_params(channel)["frames"]]}
+
+    def set_state(self, channel, current, count, head, ring=None, stream=None):
+        from .capi import MeterGraphState
+        s = MeterGraphState(float(current), count, head)
+        r = None if ring is None else np.ascontiguousarray(ring, np.float32)
+        check(lib.mi_metergraph_bank_set_state(self.handle, channel, byref(s), None if r is None else r.ctypes.data_as(c_void_p), _stream(stream)))
+
+    def process(self, src, count, gains=None, stride=None, stream=None):
+        """process(s, n) of every channel, or process(s, gain, n) with gains a device array of `channels` floats."""
+        check(lib.mi_metergraph_bank_process(self.handle, _opt(src), _opt(gains), count, count if stride is None else stride, _stream(stream)))
+
+    def process_value(self, values, stream=None):
+        """process(sample) of every channel: values is a device array of `channels` floats."""
+        check(lib.mi_metergraph_bank_process_value(self.handle, _opt(values), _stream(stream)))
+
+    def read(self, dst, count, stride=None, stream=None):
+        check(lib.mi_metergraph_bank_read(self.handle, _opt(dst), count, count if stride is None else stride, _stream(stream)))
+
+    def level(self, levels, stream=None):
+        check(lib.mi_metergraph_bank_level(self.handle, _opt(levels), _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            lib.mi_metergraph_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class SurgeProtectorBank:
     """`channels` x lsp::dspu::SurgeProtector (mi_surge_bank_*): a fade-in when the level row appears, a fade-out when it stops."""
     ALL = 0xFFFFFFFF
