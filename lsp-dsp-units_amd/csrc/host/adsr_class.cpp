@@ -35,7 +35,7 @@ namespace interpolation
 namespace
 {
     struct adsr_held { uint32_t unused = 0; };                  // the unit has no state on the device
-    typedef mi_host::registry<mi_adsr_bank_t, adsr_held, mi_adsr_bank_create, mi_adsr_bank_destroy> envelopes;
+    typedef mi_host::registry<mi_host::beside<mi_adsr_bank_t, adsr_held, mi_adsr_bank_destroy> > envelopes;
 
     static_assert(sizeof(void *) != 8 || sizeof(ADSREnvelope) == 208, "sizeof(ADSREnvelope)");
 
@@ -203,18 +203,18 @@ namespace
     {
         if (count == 0 || dst == NULL)
             return true;
-        envelopes::entry *p = envelopes::of(self);
-        if (p == NULL || !p->reserve(count, 2))
+        envelopes::entry *p = envelopes::of_one(self, mi_adsr_bank_create);
+        if (p == NULL || !p->buf.reserve(count, 2))
             return false;
         if (mi_adsr_bank_set_settings(p->bank, 0, &s) != MI_OK)
             return false;
-        float *d_dst = p->d_buf, *d_src = p->d_buf + p->cap;
+        float *d_dst = p->buf.row(0), *d_src = p->buf.row(1);
         const bool reads_dst = op == OP_PROCESS_MUL || op == OP_GENERATE_MUL, reads_src = op != OP_GENERATE && op != OP_GENERATE_MUL;
         if (reads_src && src == NULL)
             return false;
-        if (reads_dst && mi_dspu_copy_h2d(d_dst, dst, count * sizeof(float), NULL) != MI_OK)
+        if (reads_dst && !p->buf.up(0, dst, count))
             return false;
-        if (reads_src && mi_dspu_copy_h2d(d_src, src, count * sizeof(float), NULL) != MI_OK)
+        if (reads_src && !p->buf.up(1, src, count))
             return false;
         int r;
         switch (op)
@@ -225,7 +225,7 @@ namespace
             case OP_GENERATE_MUL:   r = mi_adsr_bank_generate_mul(p->bank, d_dst, NULL, &start, &step, count, count, count, NULL); break;
             default:                r = mi_adsr_bank_generate_mul(p->bank, d_dst, d_src, &start, &step, count, count, count, NULL); break;
         }
-        return r == MI_OK && mi_dspu_copy_d2h(dst, d_dst, count * sizeof(float), NULL) == MI_OK && mi_dspu_stream_synchronize(NULL) == MI_OK;
+        return r == MI_OK && p->buf.down(dst, 0, count) && mi_dspu_stream_synchronize(NULL) == MI_OK;
     }
 }
 

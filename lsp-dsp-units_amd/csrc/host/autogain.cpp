@@ -21,8 +21,8 @@ namespace
     // the state as the device holds it, beside the object (beside.h)
     struct autogain_held { float gain = 1.0f, out = 1.0f; uint32_t surge = 0; };
     struct simple_held { float gain = 1.0f; };
-    typedef mi_host::registry<mi_autogain_bank_t, autogain_held, mi_autogain_bank_create, mi_autogain_bank_destroy> autogains;
-    typedef mi_host::registry<mi_simple_autogain_bank_t, simple_held, mi_simple_autogain_bank_create, mi_simple_autogain_bank_destroy> simples;
+    typedef mi_host::registry<mi_host::beside<mi_autogain_bank_t, autogain_held, mi_autogain_bank_destroy> > autogains;
+    typedef mi_host::registry<mi_host::beside<mi_simple_autogain_bank_t, simple_held, mi_simple_autogain_bank_destroy> > simples;
 
     int send_autogain_state(mi_autogain_bank_t *bank, const autogain_held &s)
     {
@@ -159,8 +159,8 @@ void AutoGain::update()                                         // :155-173
 void AutoGain::run(float *vca, const float *llong, const float *lshort, const float *lexp, float level, size_t count)
 {
     update();
-    autogains::entry *p = autogains::of(this);
-    if (p == nullptr || count == 0 || !p->reserve(count, 3))
+    autogains::entry *p = autogains::of_one(this, mi_autogain_bank_create);
+    if (p == nullptr || count == 0 || !p->buf.reserve(count, 3))
         return;
     mi_autogain_params_t q;
     q.short_kgrow = sShort.fKGrow, q.short_kfall = sShort.fKFall, q.long_kgrow = sLong.fKGrow, q.long_kfall = sLong.fKFall;
@@ -173,20 +173,19 @@ void AutoGain::run(float *vca, const float *llong, const float *lshort, const fl
     const uint32_t surge = uint32_t(nFlags) & (MI_AG_SURGE_UP | MI_AG_SURGE_DOWN);
     if (!p->hand_over_state({ fCurrGain, fOutGain, surge }, send_autogain_state))
         return;
-    float *d_long = p->d_buf, *d_short = d_long + p->cap, *d_exp = d_short + p->cap;
-    const size_t bytes = count * sizeof(float);
-    if (mi_dspu_copy_h2d(d_long, llong, bytes, nullptr) != MI_OK || mi_dspu_copy_h2d(d_short, lshort, bytes, nullptr) != MI_OK)
+    float *d_long = p->buf.row(0), *d_short = p->buf.row(1), *d_exp = p->buf.row(2);
+    if (!p->buf.up(0, llong, count) || !p->buf.up(1, lshort, count))
         return;
     if (lexp != nullptr)
     {
-        if (mi_dspu_copy_h2d(d_exp, lexp, bytes, nullptr) != MI_OK ||
+        if (!p->buf.up(2, lexp, count) ||
             mi_autogain_bank_process(p->bank, d_long, d_long, d_short, d_exp, count, count, count, count, count, nullptr) != MI_OK)
             return;
     }
-    else if (mi_dspu_copy_h2d(d_exp, &level, sizeof(float), nullptr) != MI_OK ||
+    else if (!p->buf.up(2, &level, 1) ||
              mi_autogain_bank_process_level(p->bank, d_long, d_long, d_short, d_exp, count, count, count, count, nullptr) != MI_OK)
         return;
-    if (mi_dspu_copy_d2h(vca, d_long, bytes, nullptr) != MI_OK)
+    if (!p->buf.down(vca, 0, count))
         return;
     uint32_t flags = 0;
     if (mi_autogain_bank_get_state(p->bank, 0, &p->held.gain, &p->held.out, &flags, nullptr) != MI_OK)
@@ -351,17 +350,17 @@ void SimpleAutoGain::update()                                   // :142-153
 void SimpleAutoGain::process(float *dst, const float *src, size_t count)        // :155-175
 {
     update();
-    simples::entry *p = simples::of(this);
-    if (p == nullptr || count == 0 || !p->reserve(count, 1))
+    simples::entry *p = simples::of_one(this, mi_simple_autogain_bank_create);
+    if (p == nullptr || count == 0 || !p->buf.reserve(count, 1))
         return;
     const mi_simple_autogain_params_t q = { fKGrow, fKFall, fThreshold, fMinGain, fMaxGain };
     if (mi::simple_autogain_bank_set_params(p->bank, 0, &q) != MI_OK)
         return;
     if (!p->hand_over_state({ fCurrGain }, send_simple_state))
         return;
-    if (mi_dspu_copy_h2d(p->d_buf, src, count * sizeof(float), nullptr) != MI_OK ||
-        mi_simple_autogain_bank_process(p->bank, p->d_buf, p->d_buf, count, count, count, nullptr) != MI_OK ||
-        mi_dspu_copy_d2h(dst, p->d_buf, count * sizeof(float), nullptr) != MI_OK ||
+    if (!p->buf.up(0, src, count) ||
+        mi_simple_autogain_bank_process(p->bank, p->buf.row(0), p->buf.row(0), count, count, count, nullptr) != MI_OK ||
+        !p->buf.down(dst, 0, count) ||
         mi_simple_autogain_bank_get_state(p->bank, 0, &p->held.gain, nullptr) != MI_OK)
         return;
     fCurrGain = p->held.gain;

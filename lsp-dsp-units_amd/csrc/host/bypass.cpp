@@ -19,7 +19,7 @@ namespace
 {
     // a fresh bank's state is construct()'s
     struct bypass_held { uint32_t state = MI_BYPASS_OFF; float delta = 0.0f, gain = 0.0f; };
-    typedef mi_host::registry<mi_bypass_bank_t, bypass_held, mi_bypass_bank_create, mi_bypass_bank_destroy> bypasses;
+    typedef mi_host::registry<mi_host::beside<mi_bypass_bank_t, bypass_held, mi_bypass_bank_destroy> > bypasses;
 
     int send_state(mi_bypass_bank_t *bank, const bypass_held &now)
     {
@@ -33,18 +33,17 @@ namespace
     void run(const void *self, int variant, float *dst, const float *dry, const float *wet, float dry_gain, float wet_gain, size_t count,
              bypass_held *fields)
     {
-        bypasses::entry *p = bypasses::of(self);
-        if (p == nullptr || !p->hand_over_state(*fields, send_state) || !p->reserve(count, 3))
+        bypasses::entry *p = bypasses::of_one(self, mi_bypass_bank_create);
+        if (p == nullptr || !p->hand_over_state(*fields, send_state) || !p->buf.reserve(count, 3))
             return;
-        float *d_dst = p->d_buf, *d_wet = p->d_buf + p->cap, *d_dry = (dry != NULL) ? p->d_buf + 2 * p->cap : NULL;
-        if (mi_dspu_copy_h2d(d_wet, wet, count * sizeof(float), nullptr) != MI_OK ||
-            (dry != NULL && mi_dspu_copy_h2d(d_dry, dry, count * sizeof(float), nullptr) != MI_OK))
+        float *d_dst = p->buf.row(0), *d_wet = p->buf.row(1), *d_dry = (dry != NULL) ? p->buf.row(2) : NULL;
+        if (!p->buf.up(1, wet, count) || (dry != NULL && !p->buf.up(2, dry, count)))
             return;
         const int r = (variant == PROCESS) ? mi_bypass_bank_process(p->bank, d_dst, d_dry, d_wet, count, count, count, count, nullptr) :
                       (variant == PROCESS_WET) ? mi_bypass_bank_process_wet(p->bank, d_dst, d_dry, d_wet, wet_gain, count, count, count, count, nullptr) :
                       mi_bypass_bank_process_drywet(p->bank, d_dst, d_dry, d_wet, dry_gain, wet_gain, count, count, count, count, nullptr);
         mi_bypass_state_t s;
-        if (r != MI_OK || mi_dspu_copy_d2h(dst, d_dst, count * sizeof(float), nullptr) != MI_OK ||
+        if (r != MI_OK || !p->buf.down(dst, 0, count) ||
             mi_bypass_bank_get_state(p->bank, 0, &s, nullptr) != MI_OK)
             return;
         p->held = bypass_held{ s.state, s.delta, s.gain };

@@ -17,7 +17,7 @@ namespace dspu
 {
 namespace
 {
-    typedef mi_host::registry<mi_compressor_bank_t, mi_host::follow_held, mi_compressor_bank_create, mi_compressor_bank_destroy> besides;
+    typedef mi_host::registry<mi_host::beside<mi_compressor_bank_t, mi_host::follow_held, mi_compressor_bank_destroy> > besides;
 
     inline float knee_gain(float x, float lx, const dsp::compressor_knee_t &k)     // Compressor.cpp:302-307
     {
@@ -122,17 +122,17 @@ namespace
 void Compressor::process(float *out, float *env, const float *in, size_t samples)      // :222-267
 {
     update_settings();
-    besides::entry *p = besides::of(this);
-    if (p == nullptr || samples == 0 || !p->reserve(samples, 2) ||
+    besides::entry *p = besides::of_one(this, mi_compressor_bank_create);
+    if (p == nullptr || samples == 0 || !p->buf.reserve(samples, 2) ||
         !hand_over(p, fTauAttack, fTauRelease, fReleaseThresh, nHold, sComp) ||
         !p->hand_over_state({ fEnvelope, fPeak, uint32_t(nHoldCounter) }, send_state))
         return;
-    float *d_in = p->d_buf, *d_env = p->d_buf + p->cap;
-    if (mi_dspu_copy_h2d(d_in, in, samples * sizeof(float), nullptr) != MI_OK ||
+    float *d_in = p->buf.row(0), *d_env = p->buf.row(1);
+    if (!p->buf.up(0, in, samples) ||
         mi_compressor_bank_process(p->bank, d_in, (env != nullptr) ? d_env : nullptr, d_in, samples, samples, samples, samples, nullptr) != MI_OK ||
-        mi_dspu_copy_d2h(out, d_in, samples * sizeof(float), nullptr) != MI_OK)
+        !p->buf.down(out, 0, samples))
         return;
-    if (env != nullptr && mi_dspu_copy_d2h(env, d_env, samples * sizeof(float), nullptr) != MI_OK)
+    if (env != nullptr && !p->buf.down(env, 1, samples))
         return;
     if (mi_compressor_bank_get_state(p->bank, 0, &p->held.e, &p->held.peak, &p->held.hold, nullptr) != MI_OK)
         return;
@@ -150,13 +150,13 @@ float Compressor::process(float *env, float in)                 // :269-311: one
 
 void Compressor::curve(float *out, const float *in, size_t dots)                        // :313-316
 {
-    besides::entry *p = besides::of(this);
-    if (p == nullptr || dots == 0 || !p->reserve(dots, 2) ||
+    besides::entry *p = besides::of_one(this, mi_compressor_bank_create);
+    if (p == nullptr || dots == 0 || !p->buf.reserve(dots, 2) ||
         !hand_over(p, fTauAttack, fTauRelease, fReleaseThresh, nHold, sComp))
         return;
-    if (mi_dspu_copy_h2d(p->d_buf, in, dots * sizeof(float), nullptr) == MI_OK &&
-        mi_compressor_bank_curve(p->bank, p->d_buf, p->d_buf, dots, dots, dots, nullptr) == MI_OK &&
-        mi_dspu_copy_d2h(out, p->d_buf, dots * sizeof(float), nullptr) == MI_OK)
+    if (p->buf.up(0, in, dots) &&
+        mi_compressor_bank_curve(p->bank, p->buf.row(0), p->buf.row(0), dots, dots, dots, nullptr) == MI_OK &&
+        p->buf.down(out, 0, dots))
         mi_dspu_stream_synchronize(nullptr);
 }
 

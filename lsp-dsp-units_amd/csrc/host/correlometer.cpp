@@ -18,13 +18,13 @@ namespace
 
     struct corr_held { float v = 0.0f, a = 0.0f, b = 0.0f; uint32_t head = 0, window = 0, known = 0; };
 
-    // the bank of the object being served: beside.h's create takes the channels only
-    thread_local uint32_t g_max_period = 1;
-    int create_one(mi_correlometer_bank_t **bank, uint32_t channels)
+    typedef mi_host::registry<mi_host::beside<mi_correlometer_bank_t, corr_held, mi_correlometer_bank_destroy> > correlometers;
+
+    // the entry of `self`, its bank made for the object's nMaxPeriod at the first call
+    correlometers::entry *of(const void *self, uint32_t max_period)
     {
-        return mi_correlometer_bank_create(bank, channels, g_max_period);
+        return correlometers::of(self, [max_period](correlometers::entry &e) { return mi_correlometer_bank_create(&e.bank, 1, max_period); });
     }
-    typedef mi_host::registry<mi_correlometer_bank_t, corr_held, create_one, mi_correlometer_bank_destroy> correlometers;
 
     int send_state(mi_correlometer_bank_t *bank, const corr_held &now)
     {
@@ -92,8 +92,7 @@ void Correlometer::clear()                                      // :122-132
     nHead = nPeriod;
     if (nMaxPeriod == 0)
         return;
-    g_max_period = nMaxPeriod;
-    correlometers::entry *p = correlometers::of(this);
+    correlometers::entry *p = of(this, nMaxPeriod);
     if (p == nullptr)
         return;
     const mi_correlometer_state_t s = { 0.0f, 0.0f, 0.0f, nHead, 0 };
@@ -106,9 +105,8 @@ void Correlometer::process(float *dst, const float *a, const float *b, size_t co
     update_settings();
     if (count == 0 || nPeriod == 0 || nCapacity == 0)
         return;                                                 // a period of 0: the reference never returns
-    g_max_period = nMaxPeriod;
-    correlometers::entry *p = correlometers::of(this);
-    if (p == nullptr || !p->reserve(count, 3))
+    correlometers::entry *p = of(this, nMaxPeriod);
+    if (p == nullptr || !p->buf.reserve(count, 3))
         return;
     mi_correlometer_params_t q;
     if (mi_correlometer_bank_get_params(p->bank, 0, &q) != MI_OK)
@@ -122,12 +120,11 @@ void Correlometer::process(float *dst, const float *a, const float *b, size_t co
     if (!p->hand_over_state({ sCorr.v, sCorr.a, sCorr.b, nHead % nCapacity, (nWindow < nPeriod) ? nWindow : nPeriod, 1 }, send_state))
         return;
     p->held.known = 0;
-    float *d_a = p->d_buf, *d_b = p->d_buf + p->cap, *d_out = p->d_buf + 2 * p->cap;
+    float *d_a = p->buf.row(0), *d_b = p->buf.row(1), *d_out = p->buf.row(2);
     mi_correlometer_state_t s;
-    if (mi_dspu_copy_h2d(d_a, a, count * sizeof(float), nullptr) != MI_OK ||
-        mi_dspu_copy_h2d(d_b, b, count * sizeof(float), nullptr) != MI_OK ||
+    if (!p->buf.up(0, a, count) || !p->buf.up(1, b, count) ||
         mi_correlometer_bank_process(p->bank, d_out, d_a, d_b, count, count, count, count, nullptr) != MI_OK ||
-        mi_dspu_copy_d2h(dst, d_out, count * sizeof(float), nullptr) != MI_OK ||
+        !p->buf.down(dst, 2, count) ||
         mi_correlometer_bank_get_state(p->bank, 0, &s, nullptr) != MI_OK)
         return;
     p->held = corr_held{ s.v, s.a, s.b, s.head, s.window, 1 };

@@ -19,7 +19,7 @@ namespace
 {
     // a fresh bank's state is construct()'s
     struct fade_held { uint32_t counter = 0; float delta = 0.0f, gain = 1.0f; };
-    typedef mi_host::registry<mi_crossfade_bank_t, fade_held, mi_crossfade_bank_create, mi_crossfade_bank_destroy> crossfades;
+    typedef mi_host::registry<mi_host::beside<mi_crossfade_bank_t, fade_held, mi_crossfade_bank_destroy> > crossfades;
 
     int send_state(mi_crossfade_bank_t *bank, const fade_held &now)
     {
@@ -76,17 +76,17 @@ void Crossfade::process(float *dst, const float *fade_out, const float *fade_in,
 {
     if (count == 0)
         return;
-    crossfades::entry *p = crossfades::of(this);
+    crossfades::entry *p = crossfades::of_one(this, mi_crossfade_bank_create);
     // a counter set beyond 32 bits through a derived class is beyond every block as well
     const fade_held now = { (nCounter < size_t(UINT32_MAX)) ? uint32_t(nCounter) : UINT32_MAX, fDelta, fGain };
-    if (p == nullptr || !p->hand_over_state(now, send_state) || !p->reserve(count, 3))
+    if (p == nullptr || !p->hand_over_state(now, send_state) || !p->buf.reserve(count, 3))
         return;
-    float *d_dst = p->d_buf, *d_out = (fade_out != NULL) ? p->d_buf + p->cap : NULL, *d_in = (fade_in != NULL) ? p->d_buf + 2 * p->cap : NULL;
+    float *d_dst = p->buf.row(0), *d_out = (fade_out != NULL) ? p->buf.row(1) : NULL, *d_in = (fade_in != NULL) ? p->buf.row(2) : NULL;
     mi_crossfade_state_t s;
-    if ((fade_out != NULL && mi_dspu_copy_h2d(d_out, fade_out, count * sizeof(float), nullptr) != MI_OK) ||
-        (fade_in != NULL && mi_dspu_copy_h2d(d_in, fade_in, count * sizeof(float), nullptr) != MI_OK) ||
+    if ((fade_out != NULL && !p->buf.up(1, fade_out, count)) ||
+        (fade_in != NULL && !p->buf.up(2, fade_in, count)) ||
         mi_crossfade_bank_process(p->bank, d_dst, d_out, d_in, count, count, count, count, nullptr) != MI_OK ||
-        mi_dspu_copy_d2h(dst, d_dst, count * sizeof(float), nullptr) != MI_OK ||
+        !p->buf.down(dst, 0, count) ||
         mi_crossfade_bank_get_state(p->bank, 0, &s, nullptr) != MI_OK)
         return;
     p->held = fade_held{ s.counter, s.delta, s.gain };

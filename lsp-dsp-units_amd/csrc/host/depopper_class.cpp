@@ -20,7 +20,7 @@ namespace
 {
     // the state words as the device holds them, in 32-bit fields (the offsets stay below 2^31, the counters below 2^30)
     struct depopper_held { float rms = 0.0f; uint32_t state = 0; int32_t counter = 0, delay = 0; uint32_t rms_off = 0, look_off = 0, buffers = 0; };
-    typedef mi_host::registry<mi_depopper_bank_t, depopper_held, mi_depopper_bank_create, mi_depopper_bank_destroy> depoppers;
+    typedef mi_host::registry<mi_host::beside<mi_depopper_bank_t, depopper_held, mi_depopper_bank_destroy> > depoppers;
 
     static_assert(sizeof(void *) != 8 || sizeof(Depopper) == 248, "sizeof(Depopper)");
 
@@ -236,8 +236,8 @@ void Depopper::process(float *env, float *gain, const float *src, size_t count) 
     reconfigure();
     if (count == 0 || pData == NULL || bReconfigure)
         return;
-    depoppers::entry *p = depoppers::of(this);
-    if (p == NULL || !p->reserve(count, 3))
+    depoppers::entry *p = depoppers::of_one(this, mi_depopper_bank_create);
+    if (p == NULL || !p->buf.reserve(count, 3))
         return;
 
     mi_depopper_params_t s = {};
@@ -258,19 +258,19 @@ void Depopper::process(float *env, float *gain, const float *src, size_t count) 
         p->held = now;
     }
 
-    float *d_src = p->d_buf, *d_env = p->d_buf + p->cap, *d_gain = p->d_buf + 2 * p->cap;
+    float *d_src = p->buf.row(0), *d_env = p->buf.row(1), *d_gain = p->buf.row(2);
     mi_depopper_state_t st;
     const size_t kept_squares = nRmsMin, kept_gains = nLookMin;
     std::vector<float> squares(kept_squares), gains(kept_gains);
-    if (mi_dspu_copy_h2d(d_src, src, count * sizeof(float), NULL) != MI_OK ||
+    if (!p->buf.up(0, src, count) ||
         mi_depopper_bank_process(p->bank, (env != NULL) ? d_env : NULL, d_gain, d_src, count, count, count, count, NULL) != MI_OK ||
         mi_depopper_bank_get_state(p->bank, 0, &st, squares.data(), gains.data(), NULL) != MI_OK)
     {
         p->held = depopper_held();
         return;
     }
-    if ((env != NULL && mi_dspu_copy_d2h(env, d_env, count * sizeof(float), NULL) != MI_OK) ||
-        mi_dspu_copy_d2h(gain, d_gain, count * sizeof(float), NULL) != MI_OK || mi_dspu_stream_synchronize(NULL) != MI_OK)
+    if ((env != NULL && !p->buf.down(env, 1, count)) ||
+        !p->buf.down(gain, 2, count) || mi_dspu_stream_synchronize(NULL) != MI_OK)
     {
         p->held = depopper_held();
         return;

@@ -35,6 +35,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "beside.h"
 #include "filter_design.h"
 
 // lsp::dspu::filter_params_t is the reference's own type (so that the mangled names match); the C-ABI's record has the same
@@ -64,34 +65,19 @@ void clear_last_status()    { tl_last_status = MI_OK; }
 
 namespace
 {
-    // a pair of device rows that grows on demand
+    // A pair of device blocks that grow on demand, each an allocation of its own (beside.h's rows, of one row): the banks
+    // choose their vector paths by a block's 16-byte alignment, which a second row `cap` floats behind the first would lose at
+    // every length that is no multiple of 4.
     struct staging
     {
-        float  *d_in = nullptr, *d_out = nullptr;
-        size_t  cap = 0;
+        mi_host::rows in, out;
 
-        bool reserve(size_t n)
-        {
-            if (n <= cap)
-                return true;
-            release();
-            if (mi_dspu_malloc(reinterpret_cast<void **>(&d_in), n * sizeof(float)) != MI_OK) return false;
-            if (mi_dspu_malloc(reinterpret_cast<void **>(&d_out), n * sizeof(float)) != MI_OK) return false;
-            cap = n;
-            return true;
-        }
-        void release()
-        {
-            mi_dspu_free(d_in); mi_dspu_free(d_out);
-            d_in = d_out = nullptr;
-            cap = 0;
-        }
-        bool up(const float *src, size_t n)     { return mi_dspu_copy_h2d(d_in, src, n * sizeof(float), nullptr) == MI_OK; }
-        bool down(float *dst, size_t n)
-        {
-            return mi_dspu_copy_d2h(dst, d_out, n * sizeof(float), nullptr) == MI_OK &&
-                   mi_dspu_stream_synchronize(nullptr) == MI_OK;
-        }
+        bool reserve(size_t n)                  { return in.reserve(n) && out.reserve(n); }
+        void release()                          { in.release(); out.release(); }
+        float *d_in() const                     { return in.row(0); }
+        float *d_out() const                    { return out.row(0); }
+        bool up(const float *src, size_t n)     { return in.up(0, src, n); }
+        bool down(float *dst, size_t n)         { return out.down(dst, 0, n) && mi_dspu_stream_synchronize(nullptr) == MI_OK; }
     };
 } // namespace
 
@@ -246,7 +232,7 @@ void FilterBank::process(float *out, const float *in, size_t samples)
         return;
     bank_ext *x = reinterpret_cast<bank_ext *>(vData);
     if (x == nullptr || !x->st.reserve(samples) || !x->st.up(in, samples) ||
-        last_status(mi_biquad_bank_process(dev_bank(vFilters), x->st.d_out, x->st.d_in, samples, samples, samples, nullptr)) != MI_OK ||
+        last_status(mi_biquad_bank_process(dev_bank(vFilters), x->st.d_out(), x->st.d_in(), samples, samples, samples, nullptr)) != MI_OK ||
         !x->st.down(out, samples))
     {
         if (out != in)
@@ -260,7 +246,7 @@ void FilterBank::impulse_response(float *out, size_t samples)
         return;
     bank_ext *x = reinterpret_cast<bank_ext *>(vData);
     if (x == nullptr || !x->st.reserve(samples) ||
-        last_status(mi_biquad_bank_impulse_response(dev_bank(vFilters), x->st.d_out, samples, samples, nullptr)) != MI_OK ||
+        last_status(mi_biquad_bank_impulse_response(dev_bank(vFilters), x->st.d_out(), samples, samples, nullptr)) != MI_OK ||
         !x->st.down(out, samples))
         std::memset(out, 0, samples * sizeof(float));
 }
@@ -756,7 +742,7 @@ void Equalizer::process(float *out, const float *in, size_t samples)
         return;
     impl_t *p = impl();
     if (p == nullptr || !p->st.reserve(samples) || !p->st.up(in, samples) ||
-        last_status(mi_equalizer_bank_process(p->bank, p->st.d_out, p->st.d_in, samples, samples, samples, nullptr)) != MI_OK ||
+        last_status(mi_equalizer_bank_process(p->bank, p->st.d_out(), p->st.d_in(), samples, samples, samples, nullptr)) != MI_OK ||
         !p->st.down(out, samples))
     {
         if (out != in)
@@ -824,8 +810,7 @@ struct DynamicFilters::impl_t
     std::vector<filter_params_t>    raw;            // as handed to set_params()
     std::vector<uint8_t>            sent;           // the bank has this filter's parameters
     staging                         st;
-    float                          *d_gain = nullptr;
-    size_t                          gain_cap = 0;
+    mi_host::rows                   d_gain;         // [1][cap]: the staged gain row
 };
 static_assert(sizeof(DynamicFilters) == 64, "DynamicFilters keeps the reference's layout");
 
@@ -875,7 +860,7 @@ void DynamicFilters::destroy()
     if (impl_t *p = impl())
     {
         mi_dynfilter_bank_destroy(p->bank);
-        mi_dspu_free(p->d_gain);
+        p->d_gain.release();
         p->st.release();
         delete p;
     }
@@ -924,17 +909,8 @@ void DynamicFilters::process(size_t id, float *out, const float *in, const float
     {
         // the inline set_filter_active() only touches the host array: tell the bank now
         mi_dynfilter_bank_set_filter_active(p->bank, uint32_t(id), 1);
-        if (samples > p->gain_cap)
-        {
-            mi_dspu_free(p->d_gain);
-            p->d_gain = nullptr;
-            p->gain_cap = 0;
-            if (mi_dspu_malloc(reinterpret_cast<void **>(&p->d_gain), samples * sizeof(float)) == MI_OK)
-                p->gain_cap = samples;
-        }
-        done = p->gain_cap >= samples && p->st.reserve(samples) && p->st.up(in, samples) &&
-               mi_dspu_copy_h2d(p->d_gain, gain, samples * sizeof(float), nullptr) == MI_OK &&
-               last_status(mi_dynfilter_bank_process(p->bank, uint32_t(id), p->st.d_out, p->st.d_in, p->d_gain, samples,
+        done = p->d_gain.reserve(samples) && p->st.reserve(samples) && p->st.up(in, samples) && p->d_gain.up(0, gain, samples) &&
+               last_status(mi_dynfilter_bank_process(p->bank, uint32_t(id), p->st.d_out(), p->st.d_in(), p->d_gain.row(0), samples,
                                                      samples, samples, samples, nullptr)) == MI_OK &&
                p->st.down(out, samples);
         bClearMem = false;
@@ -1077,7 +1053,7 @@ void Convolver::process(float *dst, const float *src, size_t count)
         return;
     impl_t *p = impl();
     if (p == nullptr || !p->st.reserve(count) || !p->st.up(src, count) ||
-        last_status(mi_convolver_bank_process(p->bank, p->st.d_out, p->st.d_in, count, count, count, nullptr)) != MI_OK ||
+        last_status(mi_convolver_bank_process(p->bank, p->st.d_out(), p->st.d_in(), count, count, count, nullptr)) != MI_OK ||
         !p->st.down(dst, count))
     {
         std::memset(dst, 0, count * sizeof(float));
@@ -1224,7 +1200,7 @@ void SpectralProcessor::process(float *dst, const float *src, size_t count)
         return;
     impl_t *p = impl();
     if (p == nullptr || !p->st.reserve(count) || !p->st.up(src, count) ||
-        last_status(mi_spectral_bank_process(p->bank, p->st.d_out, p->st.d_in, count, count, count, nullptr)) != MI_OK ||
+        last_status(mi_spectral_bank_process(p->bank, p->st.d_out(), p->st.d_in(), count, count, count, nullptr)) != MI_OK ||
         !p->st.down(dst, count))
     {
         std::memset(dst, 0, count * sizeof(float));
@@ -1239,7 +1215,7 @@ void SpectralProcessor::process(const float *src, size_t count)
     impl_t *p = impl();
     if (count == 0 || p == nullptr || !p->st.reserve(count) || !p->st.up(src, count))
         return;
-    last_status(mi_spectral_bank_process(p->bank, nullptr, p->st.d_in, count, count, count, nullptr));
+    last_status(mi_spectral_bank_process(p->bank, nullptr, p->st.d_in(), count, count, count, nullptr));
     mi_dspu_stream_synchronize(nullptr);
     bUpdate = false;
     nOffset = (size_t(1) << (nRank - 1)) - remaining();
@@ -1282,21 +1258,8 @@ struct MultiSpectralProcessor::impl_t
     std::vector<uint8_t>       has_in, has_out;
     std::vector<float>         host_io, host_spec;
     std::vector<float *>       spec_ptr;
-    float  *d_in = nullptr, *d_out = nullptr;
-    size_t  cap = 0;
-
-    bool reserve(size_t channels, size_t count)
-    {
-        if (count <= cap)
-            return true;
-        mi_dspu_free(d_in); mi_dspu_free(d_out);
-        d_in = d_out = nullptr;
-        cap = 0;
-        if (mi_dspu_malloc(reinterpret_cast<void **>(&d_in), channels * count * sizeof(float)) != MI_OK) return false;
-        if (mi_dspu_malloc(reinterpret_cast<void **>(&d_out), channels * count * sizeof(float)) != MI_OK) return false;
-        cap = count;
-        return true;
-    }
+    staging st;                             // [channels][count], packed: sized by the product, so a changed channel count
+                                            // would be covered too -- it cannot change, init() makes the impl_t and its bank anew
 
     // device-side hook: bring all spectra to the host, run the user's handler on the per-channel pointers, send them back
     static void trampoline(void *object, void *, float *spectrum, size_t rank, size_t channels, void *stream)
@@ -1370,8 +1333,7 @@ void MultiSpectralProcessor::destroy()
     if (impl_t *p = impl())
     {
         mi_spectral_bank_destroy(p->bank);
-        mi_dspu_free(p->d_in);
-        mi_dspu_free(p->d_out);
+        p->st.release();
         delete p;
     }
     pData = nullptr;
@@ -1471,7 +1433,7 @@ void MultiSpectralProcessor::process(size_t count)
         p->has_in[i]  = (vChannels[i].pIn != nullptr) ? 1 : 0;
         p->has_out[i] = (vChannels[i].pOut != nullptr) ? 1 : 0;
     }
-    bool ok = p->reserve(C, count) &&
+    bool ok = p->st.reserve(C * count) &&
               mi_spectral_bank_bind_channels(p->bank, p->has_in.data(), p->has_out.data(), nullptr) == MI_OK;
     if (ok)
     {
@@ -1480,10 +1442,9 @@ void MultiSpectralProcessor::process(size_t count)
         for (size_t i = 0; i < C; ++i)
             if (vChannels[i].pIn != nullptr)
                 std::memcpy(&p->host_io[i * count], vChannels[i].pIn, count * sizeof(float));
-        ok = mi_dspu_copy_h2d(p->d_in, p->host_io.data(), C * count * sizeof(float), nullptr) == MI_OK &&
-             mi_spectral_bank_process(p->bank, p->d_out, p->d_in, count, count, count, nullptr) == MI_OK &&
-             mi_dspu_copy_d2h(p->host_io.data(), p->d_out, C * count * sizeof(float), nullptr) == MI_OK &&
-             mi_dspu_stream_synchronize(nullptr) == MI_OK;
+        ok = p->st.up(p->host_io.data(), C * count) &&
+             mi_spectral_bank_process(p->bank, p->st.d_out(), p->st.d_in(), count, count, count, nullptr) == MI_OK &&
+             p->st.down(p->host_io.data(), C * count);
     }
     for (size_t i = 0; i < C; ++i)                           // the bound pointers move on (:310-320)
     {
@@ -2633,22 +2594,9 @@ struct LoudnessMeter::impl_t
                     bs::channel_t designation = bs::CHANNEL_NONE; bool active = true; };
     std::vector<chan_t> ch;
     std::vector<float>  host;
-    float  *d_in = nullptr, *d_out = nullptr, *d_ch = nullptr;
-    size_t  cap = 0;
-
-    bool reserve(size_t channels, size_t n)
-    {
-        if (n <= cap)
-            return true;
-        mi_dspu_free(d_in); mi_dspu_free(d_out); mi_dspu_free(d_ch);
-        d_in = d_out = d_ch = nullptr;
-        cap = 0;
-        if (mi_dspu_malloc(reinterpret_cast<void **>(&d_in), channels * n * sizeof(float)) != MI_OK) return false;
-        if (mi_dspu_malloc(reinterpret_cast<void **>(&d_ch), channels * n * sizeof(float)) != MI_OK) return false;
-        if (mi_dspu_malloc(reinterpret_cast<void **>(&d_out), n * sizeof(float)) != MI_OK) return false;
-        cap = n;
-        return true;
-    }
+    // [channels][n] packed in d_in and d_ch, [n] in d_out: an allocation each (see staging).  The channel count is init()'s,
+    // which makes the impl_t anew; rows would cover a change of it all the same.
+    mi_host::rows d_in, d_ch, d_out;
 };
 
 LoudnessMeter::LoudnessMeter() { construct(); }
@@ -2679,7 +2627,7 @@ void LoudnessMeter::destroy()
     if (impl_t *p = impl())
     {
         mi_loudness_bank_destroy(p->bank);
-        mi_dspu_free(p->d_in); mi_dspu_free(p->d_out); mi_dspu_free(p->d_ch);
+        p->d_in.release(); p->d_out.release(); p->d_ch.release();
         delete p;
     }
     pData = nullptr;
@@ -2841,7 +2789,7 @@ void LoudnessMeter::run(float *out, size_t count, float gain, bool with_gain)
 {
     impl_t *p = impl();
     const size_t K = nChannels;
-    if (p == nullptr || count == 0 || !p->reserve(K, count))
+    if (p == nullptr || count == 0 || !p->d_in.reserve(count, K) || !p->d_ch.reserve(count, K) || !p->d_out.reserve(count))
         return;
     p->host.assign(K * count, 0.0f);
     bool want_ch = false;
@@ -2853,13 +2801,14 @@ void LoudnessMeter::run(float *out, size_t count, float gain, bool with_gain)
             std::memcpy(&p->host[c * count], p->ch[c].in, count * sizeof(float));      // vIn is read from its start every call (:424)
         want_ch = want_ch || (p->ch[c].out != nullptr);
     }
-    bool ok = mi_dspu_copy_h2d(p->d_in, p->host.data(), K * count * sizeof(float), nullptr) == MI_OK &&
-              (with_gain ? mi_loudness_bank_process_gain(p->bank, p->d_out, want_ch ? p->d_ch : nullptr, p->d_in, count, count, count, gain, nullptr)
-                         : mi_loudness_bank_process(p->bank, p->d_out, want_ch ? p->d_ch : nullptr, p->d_in, count, count, count, nullptr)) == MI_OK;
+    float *d_in = p->d_in.row(0), *d_out = p->d_out.row(0), *d_ch = want_ch ? p->d_ch.row(0) : nullptr;
+    bool ok = p->d_in.up(0, p->host.data(), K * count) &&
+              (with_gain ? mi_loudness_bank_process_gain(p->bank, d_out, d_ch, d_in, count, count, count, gain, nullptr)
+                         : mi_loudness_bank_process(p->bank, d_out, d_ch, d_in, count, count, count, nullptr)) == MI_OK;
     if (ok && out != nullptr)
-        ok = mi_dspu_copy_d2h(out, p->d_out, count * sizeof(float), nullptr) == MI_OK;
+        ok = p->d_out.down(out, 0, count);
     if (ok && want_ch)
-        ok = mi_dspu_copy_d2h(p->host.data(), p->d_ch, K * count * sizeof(float), nullptr) == MI_OK;
+        ok = p->d_ch.down(p->host.data(), 0, K * count);
     ok = ok && mi_dspu_stream_synchronize(nullptr) == MI_OK;
     for (size_t c = 0; c < K; ++c)
     {
@@ -2933,21 +2882,7 @@ struct ILUFSMeter::impl_t
     struct chan_t { const float *in = nullptr; bs::channel_t designation = bs::CHANNEL_NONE; bool active = true, bound = true; };
     std::vector<chan_t> ch;
     std::vector<float>  host;
-    float  *d_in = nullptr, *d_out = nullptr;
-    size_t  cap = 0;
-
-    bool reserve(size_t channels, size_t n)
-    {
-        if (n <= cap)
-            return true;
-        mi_dspu_free(d_in); mi_dspu_free(d_out);
-        d_in = d_out = nullptr;
-        cap = 0;
-        if (mi_dspu_malloc(reinterpret_cast<void **>(&d_in), channels * n * sizeof(float)) != MI_OK) return false;
-        if (mi_dspu_malloc(reinterpret_cast<void **>(&d_out), n * sizeof(float)) != MI_OK) return false;
-        cap = n;
-        return true;
-    }
+    mi_host::rows d_in, d_out;              // [channels][n] packed and [n], as in LoudnessMeter::impl_t
 };
 
 ILUFSMeter::ILUFSMeter() { construct(); }
@@ -2977,7 +2912,7 @@ void ILUFSMeter::destroy()
     if (impl_t *p = impl())
     {
         mi_ilufs_bank_destroy(p->bank);
-        mi_dspu_free(p->d_in); mi_dspu_free(p->d_out);
+        p->d_in.release(); p->d_out.release();
         delete p;
     }
     pData = nullptr;
@@ -3108,7 +3043,7 @@ void ILUFSMeter::process(float *out, size_t count, float gain)
 {
     impl_t *p = impl();
     const size_t K = nChannels;
-    if (p == nullptr || count == 0 || !p->reserve(K, count))
+    if (p == nullptr || count == 0 || !p->d_in.reserve(count, K) || !p->d_out.reserve(count))
         return;
     p->host.assign(K * count, 0.0f);
     for (size_t c = 0; c < K; ++c)
@@ -3123,10 +3058,10 @@ void ILUFSMeter::process(float *out, size_t count, float gain)
         if (on)
             std::memcpy(&p->host[c * count], p->ch[c].in, count * sizeof(float));
     }
-    bool ok = mi_dspu_copy_h2d(p->d_in, p->host.data(), K * count * sizeof(float), nullptr) == MI_OK &&
-              mi_ilufs_bank_process(p->bank, (out != nullptr) ? p->d_out : nullptr, p->d_in, count, count, count, gain, nullptr) == MI_OK;
+    bool ok = p->d_in.up(0, p->host.data(), K * count) &&
+              mi_ilufs_bank_process(p->bank, (out != nullptr) ? p->d_out.row(0) : nullptr, p->d_in.row(0), count, count, count, gain, nullptr) == MI_OK;
     if (ok && out != nullptr)
-        ok = mi_dspu_copy_d2h(out, p->d_out, count * sizeof(float), nullptr) == MI_OK;
+        ok = p->d_out.down(out, 0, count);
     ok = ok && mi_dspu_stream_synchronize(nullptr) == MI_OK;
     if (ok)
         mi_ilufs_bank_loudness(p->bank, &fLoudness, nullptr);
@@ -3190,33 +3125,20 @@ struct Delay::impl_t
 {
     mi_delay_bank_t *bank = nullptr;
     staging st;
-    float  *d_gain = nullptr;
-    size_t  gain_cap = 0;
+    mi_host::rows d_gain;                   // [1][cap]: the staged gain row
 
-    bool gain_up(const float *g, size_t n)
-    {
-        if (n > gain_cap)
-        {
-            mi_dspu_free(d_gain);
-            d_gain = nullptr;
-            gain_cap = 0;
-            if (mi_dspu_malloc(reinterpret_cast<void **>(&d_gain), n * sizeof(float)) != MI_OK)
-                return false;
-            gain_cap = n;
-        }
-        return mi_dspu_copy_h2d(d_gain, g, n * sizeof(float), nullptr) == MI_OK;
-    }
+    bool gain_up(const float *g, size_t n) { return d_gain.reserve(n) && d_gain.up(0, g, n); }
 
     // common body of process / process_add with the three gain forms
     void run(float *dst, const float *src, size_t count, int add, int gmode, float gain, const float *gvec)
     {
         if (count == 0 || !st.reserve(count) || !st.up(src, count))
             return;
-        if (add && mi_dspu_copy_h2d(st.d_out, dst, count * sizeof(float), nullptr) != MI_OK)
+        if (add && !st.out.up(0, dst, count))
             return;
         if (gmode == MI_GAIN_VECTOR && !gain_up(gvec, count))
             return;
-        if (mi_delay_bank_process(bank, st.d_out, st.d_in, count, count, count, add, gmode, gain, d_gain, count, nullptr) == MI_OK)
+        if (mi_delay_bank_process(bank, st.d_out(), st.d_in(), count, count, count, add, gmode, gain, d_gain.row(0), count, nullptr) == MI_OK)
             st.down(dst, count);
     }
 
@@ -3227,7 +3149,7 @@ struct Delay::impl_t
         if (gmode == MI_GAIN_VECTOR && !gain_up(gvec, count))
             return;
         const uint32_t nd = uint32_t(delay);
-        if (mi_delay_bank_process_ramping(bank, st.d_out, st.d_in, &nd, count, count, count, gmode, gain, d_gain, count, nullptr) == MI_OK)
+        if (mi_delay_bank_process_ramping(bank, st.d_out(), st.d_in(), &nd, count, count, count, gmode, gain, d_gain.row(0), count, nullptr) == MI_OK)
             st.down(dst, count);
     }
 };
@@ -3248,7 +3170,7 @@ void Delay::destroy()
     if (impl_t *p = impl())
     {
         mi_delay_bank_destroy(p->bank);
-        mi_dspu_free(p->d_gain);
+        p->d_gain.release();
         p->st.release();
         delete p;
     }
@@ -3283,7 +3205,7 @@ void Delay::append(const float *src, size_t count)
     impl_t *p = impl();
     if (p && count && p->st.reserve(count) && p->st.up(src, count))
     {
-        last_status(mi_delay_bank_append(p->bank, p->st.d_in, count, count, nullptr));
+        last_status(mi_delay_bank_append(p->bank, p->st.d_in(), count, count, nullptr));
         mi_dspu_stream_synchronize(nullptr);
         sync_positions();
     }
@@ -3423,7 +3345,7 @@ size_t RingBuffer::append(const float *data, size_t count)
     impl_t *p = impl();
     if (p && count && p->st.reserve(count) && p->st.up(data, count))
     {
-        last_status(mi_ring_bank_append(p->bank, p->st.d_in, count, count, &n, nullptr));
+        last_status(mi_ring_bank_append(p->bank, p->st.d_in(), count, count, &n, nullptr));
         mi_dspu_stream_synchronize(nullptr);
         sync_head();
     }
@@ -3449,7 +3371,7 @@ size_t RingBuffer::get(float *dst, size_t offset, size_t count) const
     impl_t *p = impl();
     if (p == nullptr || count == 0 || !p->st.reserve(count))
         return 0;
-    if (last_status(mi_ring_bank_get(p->bank, p->st.d_out, offset, count, count, &n, nullptr)) != MI_OK || !p->st.down(dst, count))
+    if (last_status(mi_ring_bank_get(p->bank, p->st.d_out(), offset, count, count, &n, nullptr)) != MI_OK || !p->st.down(dst, count))
         return 0;
     return n;
 }
@@ -4059,7 +3981,7 @@ bool FilterArray::process_host(float *out, const float *in, size_t samples, size
     if (samples == 0)
         return true;
     const size_t n = a->params.size() * stride;
-    return a->st.reserve(n) && a->st.up(in, n) && process(a->st.d_out, a->st.d_in, samples, stride, nullptr) && a->st.down(out, n);
+    return a->st.reserve(n) && a->st.up(in, n) && process(a->st.d_out(), a->st.d_in(), samples, stride, nullptr) && a->st.down(out, n);
 }
 
 // ---- EqualizerArray / ConvolverArray (extensions: the batched mode under the class API, like FilterArray) -----------------
@@ -4163,7 +4085,7 @@ bool EqualizerArray::process_host(float *out, const float *in, size_t samples, s
     if (samples == 0)
         return true;
     const size_t n = a->count * stride;
-    return a->st.reserve(n) && a->st.up(in, n) && process(a->st.d_out, a->st.d_in, samples, stride, nullptr) && a->st.down(out, n);
+    return a->st.reserve(n) && a->st.up(in, n) && process(a->st.d_out(), a->st.d_in(), samples, stride, nullptr) && a->st.down(out, n);
 }
 
 ConvolverArray::ConvolverArray() { construct(); }
@@ -4249,7 +4171,7 @@ bool ConvolverArray::process_host(float *out, const float *in, size_t samples, s
     if (samples == 0)
         return true;
     const size_t n = a->count * stride;
-    return a->st.reserve(n) && a->st.up(in, n) && process(a->st.d_out, a->st.d_in, samples, stride, nullptr) && a->st.down(out, n);
+    return a->st.reserve(n) && a->st.up(in, n) && process(a->st.d_out(), a->st.d_in(), samples, stride, nullptr) && a->st.down(out, n);
 }
 
 } // namespace dspu

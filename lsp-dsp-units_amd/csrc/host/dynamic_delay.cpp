@@ -7,7 +7,7 @@
 #include <cstddef>
 #include <new>
 
-#include "mi_dspu.h"
+#include "beside.h"
 
 namespace lsp
 {
@@ -18,33 +18,13 @@ namespace
     struct handle
     {
         mi_dyndelay_bank_t *bank = nullptr;
-        float              *d_buf = nullptr;        // [5][cap]
-        size_t              cap = 0;
+        mi_host::rows       buf;                    // [5][cap]: out, in, delay, fgain, fdelay
         uint32_t            head = 0;               // nHead on the device
+
+        ~handle() { mi_dyndelay_bank_destroy(bank); }
     };
 
     handle *of(uint8_t *p) { return reinterpret_cast<handle *>(p); }
-
-    void release(handle *h)
-    {
-        if (h == nullptr)
-            return;
-        mi_dyndelay_bank_destroy(h->bank);
-        mi_dspu_free(h->d_buf);
-        delete h;
-    }
-
-    bool reserve(handle *h, size_t n)
-    {
-        if (n <= h->cap)
-            return true;
-        mi_dspu_free(h->d_buf);
-        h->d_buf = nullptr, h->cap = 0;
-        if (mi_dspu_malloc(reinterpret_cast<void **>(&h->d_buf), 5 * n * sizeof(float)) != MI_OK)
-            return false;
-        h->cap = n;
-        return true;
-    }
 
     // the member's head to the device where the two differ
     bool hand_over_head(handle *h, uint32_t head)
@@ -83,7 +63,7 @@ void DynamicDelay::destroy()                                    // :51-63
 {
     if (pData == NULL)
         return;
-    release(of(pData));
+    delete of(pData);
     vDelay = NULL;
     nHead = 0;
     nCapacity = 0;
@@ -99,11 +79,11 @@ status_t DynamicDelay::init(size_t max_size)                    // :65-89
     uint32_t max_delay = 0, capacity = 0;
     if (mi_dyndelay_bank_create(&h->bank, 1, max_size) != MI_OK || mi_dyndelay_bank_get(h->bank, 0, &max_delay, &capacity, nullptr) != MI_OK)
     {
-        release(h);
+        delete h;
         return STATUS_NO_MEM;
     }
     if (pData != NULL)
-        release(of(pData));
+        delete of(pData);
     nHead = 0;
     nCapacity = capacity;
     nMaxDelay = int32_t(max_delay);
@@ -122,18 +102,19 @@ void DynamicDelay::clear()                                      // :91-95
 void DynamicDelay::process(float *out, const float *in, const float *delay, const float *fgain, const float *fdelay, size_t samples)   // :97-118
 {
     handle *h = of(pData);
-    if (h == nullptr || samples == 0 || !hand_over_head(h, nHead) || !reserve(h, samples))
+    if (h == nullptr || samples == 0 || !hand_over_head(h, nHead) || !h->buf.reserve(samples, 5))
         return;
-    const float *rows[4] = { in, delay, fgain, fdelay };
+    const mi_host::rows &b = h->buf;
+    const float *staged[4] = { in, delay, fgain, fdelay };
     for (size_t k = 0; k < 4; ++k)
-        if (mi_dspu_copy_h2d(h->d_buf + (k + 1) * h->cap, rows[k], samples * sizeof(float), nullptr) != MI_OK)
+        if (!b.up(k + 1, staged[k], samples))
             return;
-    if (mi_dyndelay_bank_process(h->bank, h->d_buf, h->d_buf + h->cap, h->d_buf + 2 * h->cap, h->d_buf + 3 * h->cap, h->d_buf + 4 * h->cap,
-                                 samples, h->cap, h->cap, h->cap, h->cap, h->cap, nullptr) != MI_OK)
+    const size_t cap = b.capacity();
+    if (mi_dyndelay_bank_process(h->bank, b.row(0), b.row(1), b.row(2), b.row(3), b.row(4), samples, cap, cap, cap, cap, cap, nullptr) != MI_OK)
         return;
     nHead = uint32_t((size_t(nHead) + samples) % nCapacity);     // what the kernel leaves in the device's head
     h->head = nHead;
-    mi_dspu_copy_d2h(out, h->d_buf, samples * sizeof(float), nullptr);
+    b.down(out, 0, samples);
 }
 
 void DynamicDelay::copy(DynamicDelay *s)                        // :124-148

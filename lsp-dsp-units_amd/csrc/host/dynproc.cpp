@@ -149,7 +149,7 @@ namespace dspu
 {
 namespace
 {
-    typedef mi_host::registry<mi_dynproc_bank_t, mi_host::follow_held, mi_dynproc_bank_create, mi_dynproc_bank_destroy> besides;
+    typedef mi_host::registry<mi_host::beside<mi_dynproc_bank_t, mi_host::follow_held, mi_dynproc_bank_destroy> > besides;
 
     // the object's computed fields as the bank's channel 0 (the three tables have the C-ABI's layouts)
     bool hand_over(besides::entry *p, uint32_t splines, uint32_t attacks, uint32_t releases, uint32_t hold, const void *attack,
@@ -277,17 +277,17 @@ float DynamicProcessor::solve_reaction(const reaction_t *s, float x, size_t coun
 
 void DynamicProcessor::process(float *out, float *env, const float *in, size_t samples)         // :397-442
 {
-    besides::entry *p = besides::of(this);
-    if (p == nullptr || samples == 0 || !p->reserve(samples, 2) ||
+    besides::entry *p = besides::of_one(this, mi_dynproc_bank_create);
+    if (p == nullptr || samples == 0 || !p->buf.reserve(samples, 2) ||
         !hand_over(p, fCount[CT_SPLINES], fCount[CT_ATTACK], fCount[CT_RELEASE], nHold, vAttack, vRelease, vSplines) ||
         !p->hand_over_state({ fEnvelope, fPeak, nHoldCounter }, send_state))
         return;
-    float *d_in = p->d_buf, *d_env = p->d_buf + p->cap;
-    if (mi_dspu_copy_h2d(d_in, in, samples * sizeof(float), nullptr) != MI_OK ||
+    float *d_in = p->buf.row(0), *d_env = p->buf.row(1);
+    if (!p->buf.up(0, in, samples) ||
         mi_dynproc_bank_process(p->bank, d_in, (env != nullptr) ? d_env : nullptr, d_in, samples, samples, samples, samples, nullptr) != MI_OK ||
-        mi_dspu_copy_d2h(out, d_in, samples * sizeof(float), nullptr) != MI_OK)
+        !p->buf.down(out, 0, samples))
         return;
-    if (env != nullptr && mi_dspu_copy_d2h(env, d_env, samples * sizeof(float), nullptr) != MI_OK)
+    if (env != nullptr && !p->buf.down(env, 1, samples))
         return;
     if (mi_dynproc_bank_get_state(p->bank, 0, &p->held.e, &p->held.peak, &p->held.hold, nullptr) != MI_OK)
         return;
@@ -323,13 +323,13 @@ float DynamicProcessor::process(float *env, float s)            // :444-472: on 
 
 void DynamicProcessor::curve(float *out, const float *in, size_t dots)                  // :474-496
 {
-    besides::entry *p = besides::of(this);
-    if (p == nullptr || dots == 0 || !p->reserve(dots, 2) ||
+    besides::entry *p = besides::of_one(this, mi_dynproc_bank_create);
+    if (p == nullptr || dots == 0 || !p->buf.reserve(dots, 2) ||
         !hand_over(p, fCount[CT_SPLINES], fCount[CT_ATTACK], fCount[CT_RELEASE], nHold, vAttack, vRelease, vSplines))
         return;
-    if (mi_dspu_copy_h2d(p->d_buf, in, dots * sizeof(float), nullptr) == MI_OK &&
-        mi_dynproc_bank_curve(p->bank, p->d_buf, p->d_buf, dots, dots, dots, nullptr) == MI_OK &&
-        mi_dspu_copy_d2h(out, p->d_buf, dots * sizeof(float), nullptr) == MI_OK)
+    if (p->buf.up(0, in, dots) &&
+        mi_dynproc_bank_curve(p->bank, p->buf.row(0), p->buf.row(0), dots, dots, dots, nullptr) == MI_OK &&
+        p->buf.down(out, 0, dots))
         mi_dspu_stream_synchronize(nullptr);
 }
 
@@ -345,13 +345,13 @@ float DynamicProcessor::curve(float in)                         // :498-516
 
 void DynamicProcessor::model(float *out, const float *in, size_t dots)                  // :518-540
 {
-    besides::entry *p = besides::of(this);
-    if (p == nullptr || dots == 0 || !p->reserve(dots, 2) ||
+    besides::entry *p = besides::of_one(this, mi_dynproc_bank_create);
+    if (p == nullptr || dots == 0 || !p->buf.reserve(dots, 2) ||
         !hand_over(p, fCount[CT_SPLINES], fCount[CT_ATTACK], fCount[CT_RELEASE], nHold, vAttack, vRelease, vSplines))
         return;
-    if (mi_dspu_copy_h2d(p->d_buf, in, dots * sizeof(float), nullptr) == MI_OK &&
-        mi_dynproc_bank_model(p->bank, p->d_buf, p->d_buf, dots, dots, dots, nullptr) == MI_OK &&
-        mi_dspu_copy_d2h(out, p->d_buf, dots * sizeof(float), nullptr) == MI_OK)
+    if (p->buf.up(0, in, dots) &&
+        mi_dynproc_bank_model(p->bank, p->buf.row(0), p->buf.row(0), dots, dots, dots, nullptr) == MI_OK &&
+        p->buf.down(out, 0, dots))
         mi_dspu_stream_synchronize(nullptr);
 }
 

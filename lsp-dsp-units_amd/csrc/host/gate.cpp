@@ -18,7 +18,7 @@ namespace dspu
 namespace
 {
     struct gate_held { float e = 0.0f, peak = 0.0f; uint32_t hold = 0, curve = 0; };    // the state as the device holds it
-    typedef mi_host::registry<mi_gate_bank_t, gate_held, mi_gate_bank_create, mi_gate_bank_destroy> besides;
+    typedef mi_host::registry<mi_host::beside<mi_gate_bank_t, gate_held, mi_gate_bank_destroy> > besides;
 
     // the object's computed fields as the bank's channel 0
     bool hand_over(besides::entry *p, float ta, float tr, uint32_t hold, const dsp::gate_knee_t &k0, const dsp::gate_knee_t &k1)
@@ -112,17 +112,17 @@ void Gate::update_settings()                                    // :180-205: com
 
 void Gate::process(float *out, float *env, const float *in, size_t samples)            // :267-367: no update_settings()
 {
-    besides::entry *p = besides::of(this);
-    if (p == nullptr || samples == 0 || !p->reserve(samples, 2) ||
+    besides::entry *p = besides::of_one(this, mi_gate_bank_create);
+    if (p == nullptr || samples == 0 || !p->buf.reserve(samples, 2) ||
         !hand_over(p, fTauAttack, fTauRelease, nHold, sCurves[0].sKnee, sCurves[1].sKnee) ||
         !p->hand_over_state({ fEnvelope, fPeak, uint32_t(nHoldCounter), (nCurve != 0) ? 1u : 0u }, send_state))
         return;
-    float *d_in = p->d_buf, *d_env = p->d_buf + p->cap;
-    if (mi_dspu_copy_h2d(d_in, in, samples * sizeof(float), nullptr) != MI_OK ||
+    float *d_in = p->buf.row(0), *d_env = p->buf.row(1);
+    if (!p->buf.up(0, in, samples) ||
         mi_gate_bank_process(p->bank, d_in, (env != nullptr) ? d_env : nullptr, d_in, samples, samples, samples, samples, nullptr) != MI_OK ||
-        mi_dspu_copy_d2h(out, d_in, samples * sizeof(float), nullptr) != MI_OK)
+        !p->buf.down(out, 0, samples))
         return;
-    if (env != nullptr && mi_dspu_copy_d2h(env, d_env, samples * sizeof(float), nullptr) != MI_OK)
+    if (env != nullptr && !p->buf.down(env, 1, samples))
         return;
     if (mi_gate_bank_get_state(p->bank, 0, &p->held.e, &p->held.peak, &p->held.hold, &p->held.curve, nullptr) != MI_OK)
         return;
@@ -165,13 +165,13 @@ float Gate::process(float *env, float s)                        // :369-407: one
 
 void Gate::curve(float *out, const float *in, size_t dots, bool hyst) const            // :207-210
 {
-    besides::entry *p = besides::of(this);
-    if (p == nullptr || dots == 0 || !p->reserve(dots, 2) ||
+    besides::entry *p = besides::of_one(this, mi_gate_bank_create);
+    if (p == nullptr || dots == 0 || !p->buf.reserve(dots, 2) ||
         !hand_over(p, fTauAttack, fTauRelease, nHold, sCurves[0].sKnee, sCurves[1].sKnee))
         return;
-    if (mi_dspu_copy_h2d(p->d_buf, in, dots * sizeof(float), nullptr) == MI_OK &&
-        mi_gate_bank_curve(p->bank, p->d_buf, p->d_buf, dots, hyst ? 1 : 0, dots, dots, nullptr) == MI_OK &&
-        mi_dspu_copy_d2h(out, p->d_buf, dots * sizeof(float), nullptr) == MI_OK)
+    if (p->buf.up(0, in, dots) &&
+        mi_gate_bank_curve(p->bank, p->buf.row(0), p->buf.row(0), dots, hyst ? 1 : 0, dots, dots, nullptr) == MI_OK &&
+        p->buf.down(out, 0, dots))
         mi_dspu_stream_synchronize(nullptr);
 }
 

@@ -4,9 +4,9 @@
 // exponent of its own, so one kernel serves the twelve modes and expf is this file's for every one of them (a device expf that
 // differs in the last bit would move a peak decision, and everything after it).
 //
-// Below them lsp::dspu::Limiter on a mi_limiter_bank of one channel, in the manner of host/beside.h: the class has no member
-// to hang the bank on (its 216 bytes are the reference's), so the bank and its staging buffer live in a table keyed by the
-// object's address: made in init(), dropped in destroy() and in construct().  Every setter goes to the bank as well, so the
+// Below them lsp::dspu::Limiter on a mi_limiter_bank of one channel: the class has no member to hang the bank on (its 216
+// bytes are the reference's), so the bank and its staging buffer live beside the object in host/beside.h's registry, keyed by
+// the object's address: made in init(), dropped in destroy() and in construct().  Every setter goes to the bank as well, so the
 // bank's own update_settings() sees what the object's sees; nHead and sALR.fEnvelope are read back after every process().
 #include "limiter_bank.h"
 
@@ -15,9 +15,8 @@
 
 #include <cmath>
 #include <cstring>
-#include <mutex>
-#include <new>
-#include <unordered_map>
+
+#include "beside.h"
 
 #pragma clang fp contract(off)      // every product and every sum below rounds on its own
 
@@ -190,52 +189,13 @@ namespace
     struct limiter_impl
     {
         mi_limiter_bank_t *bank = nullptr;
-        float  *d_buf = nullptr;            // [cap]: the staged sidechain, the gain in place on it
-        size_t  cap = 0;
+        mi_host::rows buf;                  // [1][cap]: the staged sidechain, the gain in place on it
 
-        bool reserve(size_t n)
-        {
-            if (n <= cap)
-                return true;
-            mi_dspu_free(d_buf);
-            d_buf = nullptr;
-            cap = 0;
-            if (mi_dspu_malloc(reinterpret_cast<void **>(&d_buf), n * sizeof(float)) != MI_OK)
-                return false;
-            cap = n;
-            return true;
-        }
+        ~limiter_impl() { if (bank != nullptr) mi_limiter_bank_destroy(bank); }
     };
+    typedef mi_host::registry<limiter_impl> limiters;
 
-    std::mutex g_lock;
-    std::unordered_map<const void *, limiter_impl *> &table()
-    {
-        static std::unordered_map<const void *, limiter_impl *> t;
-        return t;
-    }
-
-    limiter_impl *impl_of(const void *self)
-    {
-        std::lock_guard<std::mutex> guard(g_lock);
-        auto it = table().find(self);
-        return (it != table().end()) ? it->second : nullptr;
-    }
-
-    void drop(const void *self)
-    {
-        limiter_impl *p = nullptr;
-        {
-            std::lock_guard<std::mutex> guard(g_lock);
-            auto it = table().find(self);
-            if (it == table().end())
-                return;
-            p = it->second;
-            table().erase(it);
-        }
-        mi_limiter_bank_destroy(p->bank);
-        mi_dspu_free(p->d_buf);
-        delete p;
-    }
+    limiter_impl *impl_of(const void *self) { return limiters::find(self); }
 }
 
 Limiter::Limiter()  { construct(); }
@@ -243,7 +203,7 @@ Limiter::~Limiter() { destroy(); }
 
 void Limiter::construct()                                       // Limiter.cpp:47-73
 {
-    drop(this);                                                 // whatever lived at this address before
+    limiters::drop(this);                                       // whatever lived at this address before
     fThreshold = 1.0f;
     fReqThreshold = 1.0f;
     fLookahead = 0.0f;
@@ -270,7 +230,7 @@ void Limiter::construct()                                       // Limiter.cpp:4
 
 void Limiter::destroy()                                         // :75-85
 {
-    drop(this);
+    limiters::drop(this);
     vGainBuf = NULL;
     vTmpBuf = NULL;
     vData = NULL;
@@ -278,15 +238,13 @@ void Limiter::destroy()                                         // :75-85
 
 bool Limiter::init(size_t max_sr, float max_lookahead)          // :87-109
 {
-    drop(this);
-    limiter_impl *p = new (std::nothrow) limiter_impl();
+    limiters::drop(this);
+    limiter_impl *p = limiters::of(this, [max_sr, max_lookahead](limiter_impl &e)
+    {
+        return mi_limiter_bank_create(&e.bank, 1, uint32_t(max_sr), max_lookahead);
+    });
     if (p == nullptr)
         return false;
-    if (mi_limiter_bank_create(&p->bank, 1, uint32_t(max_sr), max_lookahead) != MI_OK)
-    {
-        delete p;
-        return false;
-    }
     nMaxLookahead = size_t(millis_to_samples(float(max_sr), max_lookahead));
     nHead = 0;
     nMaxSampleRate = max_sr;
@@ -304,8 +262,6 @@ bool Limiter::init(size_t max_sr, float max_lookahead)          // :87-109
     mi_limiter_bank_set_alr_release(p->bank, 0, sALR.fRelease);
     mi_limiter_bank_set_alr_knee(p->bank, 0, sALR.fKnee);
     mi_limiter_bank_set_alr(p->bank, 0, sALR.bEnable ? 1 : 0);
-    std::lock_guard<std::mutex> guard(g_lock);
-    table()[this] = p;
     return true;
 }
 
@@ -489,11 +445,11 @@ void Limiter::process(float *gain, const float *sc, size_t samples)             
 {
     update_settings();
     limiter_impl *p = impl_of(this);
-    if (p == nullptr || samples == 0 || !p->reserve(samples))
+    if (p == nullptr || samples == 0 || !p->buf.reserve(samples))
         return;
-    if (mi_dspu_copy_h2d(p->d_buf, sc, samples * sizeof(float), nullptr) != MI_OK ||
-        mi_limiter_bank_process(p->bank, p->d_buf, p->d_buf, samples, samples, samples, nullptr) != MI_OK ||
-        mi_dspu_copy_d2h(gain, p->d_buf, samples * sizeof(float), nullptr) != MI_OK)
+    if (!p->buf.up(0, sc, samples) ||
+        mi_limiter_bank_process(p->bank, p->buf.row(0), p->buf.row(0), samples, samples, samples, nullptr) != MI_OK ||
+        !p->buf.down(gain, 0, samples))
         return;
     uint32_t head = 0;
     float env = 0.0f;

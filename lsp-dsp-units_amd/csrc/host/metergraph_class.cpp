@@ -21,15 +21,15 @@ namespace
     // what the bank of one channel holds: its ring's size, the settings, and the state that the last call read back
     struct graph_held { uint32_t frames = 0, period = 0, method = 0, count = 0, head = 0; float current = 0.0f; };
 
-    int create_one(mi_metergraph_bank_t **bank, uint32_t channels) { return mi_metergraph_bank_create(bank, channels, 1); }
-    typedef mi_host::registry<mi_metergraph_bank_t, graph_held, create_one, mi_metergraph_bank_destroy> graphs;
+    typedef mi_host::registry<mi_host::beside<mi_metergraph_bank_t, graph_held, mi_metergraph_bank_destroy> > graphs;
 
     static_assert(sizeof(MeterGraph) == 40, "sizeof(MeterGraph)");
 
     // the bank of `self` with a ring of `frames` words and the object's settings and state on the device
     graphs::entry *ready(const void *self, uint32_t frames, uint32_t period, uint32_t method, float current, uint32_t count)
     {
-        graphs::entry *p = graphs::of(self);
+        // a ring of 1 until the first call tells the size: held.frames is 0 then, and the bank is made anew just below
+        graphs::entry *p = graphs::of(self, [](graphs::entry &e) { return mi_metergraph_bank_create(&e.bank, 1, 1); });
         if (p == nullptr)
             return nullptr;
         graph_held &h = p->held;
@@ -121,18 +121,18 @@ namespace
         outcome o = { false, current, count, {}, 0 };
         graphs::entry *p = ready(self, frames, period, method, current, count);
         const size_t cap = (n > size_t(frames) + 1) ? n : size_t(frames) + 1;
-        if (p == nullptr || !p->reserve(cap, 2))
+        if (p == nullptr || !p->buf.reserve(cap, 2))
             return o;
-        float *d_src = p->d_buf, *d_out = p->d_buf + p->cap;
+        float *d_src = p->buf.row(0), *d_out = p->buf.row(1);
         const mi_metergraph::plan pl = mi_metergraph::make_plan(count, period, uint32_t(n));
         const uint32_t kept = (pl.frames < frames) ? pl.frames : frames;
         mi_metergraph_state_t st;
         o.frames.resize(kept);
-        if (mi_dspu_copy_h2d(d_src, s, n * sizeof(float), nullptr) != MI_OK ||
-            (gain != nullptr && mi_dspu_copy_h2d(d_out + frames, gain, sizeof(float), nullptr) != MI_OK) ||
+        if (!p->buf.up(0, s, n) ||
+            (gain != nullptr && mi_dspu_copy_h2d(d_out + frames, gain, sizeof(float), nullptr) != MI_OK) ||  // behind the frames; cap > frames
             mi_metergraph_bank_process(p->bank, d_src, (gain != nullptr) ? d_out + frames : nullptr, n, n, nullptr) != MI_OK ||
             (kept != 0 && mi_metergraph_bank_read(p->bank, d_out, kept, kept, nullptr) != MI_OK) ||
-            (kept != 0 && mi_dspu_copy_d2h(o.frames.data(), d_out, kept * sizeof(float), nullptr) != MI_OK) ||
+            (kept != 0 && !p->buf.down(o.frames.data(), 1, kept)) ||
             mi_metergraph_bank_get_state(p->bank, 0, &st, nullptr, nullptr) != MI_OK)
             return o;
         p->held.current = st.current, p->held.count = st.count, p->held.head = st.head;

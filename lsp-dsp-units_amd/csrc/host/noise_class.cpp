@@ -9,7 +9,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "mi_dspu.h"
+#include "beside.h"
 #include "mls_device.h"
 
 #pragma clang fp contract(off)
@@ -31,39 +31,25 @@ namespace
     {
         mi_lcg_bank_t  *lcg = nullptr;
         mi_mls_bank_t  *mls = nullptr;
-        float          *d_buf = nullptr;                        // [2][cap]: dst, src
-        size_t          cap = 0;
+        mi_host::rows   buf;                                    // [2][cap]: dst, src
 
         ~bench()
         {
             mi_lcg_bank_destroy(lcg);
             mi_mls_bank_destroy(mls);
-            mi_dspu_free(d_buf);
-        }
-
-        bool reserve(size_t n)
-        {
-            if (n <= cap)
-                return true;
-            mi_dspu_free(d_buf);
-            d_buf = nullptr, cap = 0;
-            if (mi_dspu_malloc(reinterpret_cast<void **>(&d_buf), 2 * n * sizeof(float)) != MI_OK)
-                return false;
-            cap = n;
-            return true;
         }
 
         // one piece: src up, launch() between, dst down
         template <class Launch> bool piece(float *dst, const float *src, size_t n, Launch launch)
         {
-            if (!reserve(n))
+            if (!buf.reserve(n, 2))
                 return false;
-            float *d_dst = d_buf, *d_src = (src != nullptr) ? d_buf + cap : nullptr;
-            if (src != nullptr && mi_dspu_copy_h2d(d_src, src, n * sizeof(float), nullptr) != MI_OK)
+            float *d_dst = buf.row(0), *d_src = (src != nullptr) ? buf.row(1) : nullptr;
+            if (src != nullptr && !buf.up(1, src, n))
                 return false;
             if (launch(d_dst, d_src) != MI_OK)
                 return false;
-            return mi_dspu_copy_d2h(dst, d_dst, n * sizeof(float), nullptr) == MI_OK && mi_dspu_stream_synchronize(nullptr) == MI_OK;
+            return buf.down(dst, 0, n) && mi_dspu_stream_synchronize(nullptr) == MI_OK;
         }
     };
     thread_local bench tl_bench;

@@ -10,7 +10,7 @@
 #include <new>
 #include <vector>
 
-#include "mi_dspu.h"
+#include "beside.h"
 
 #define PROCESS_BUF_LIMIT_SIZE  (12 * 1024)                     // :26
 
@@ -23,35 +23,15 @@ namespace
     struct handle
     {
         mi_oscillator_bank_t       *bank = nullptr;
-        float                      *d_buf = nullptr;            // [2][cap]: dst, src
-        size_t                      cap = 0;
+        mi_host::rows               buf;                        // [2][cap]: dst, src
         mi_oscillator_settings_t    given = {};                 // what the bank is to hold
         bool                        built = false, any = false; // given was made by update_settings(); the bank has it
         uint32_t                    acc = 0;                    // nPhaseAcc on the device
+
+        ~handle() { mi_oscillator_bank_destroy(bank); }
     };
 
     handle *of(uint8_t *p) { return reinterpret_cast<handle *>(p); }
-
-    void release(handle *h)
-    {
-        if (h == nullptr)
-            return;
-        mi_oscillator_bank_destroy(h->bank);
-        mi_dspu_free(h->d_buf);
-        delete h;
-    }
-
-    bool reserve(handle *h, size_t n)
-    {
-        if (n <= h->cap)
-            return true;
-        mi_dspu_free(h->d_buf);
-        h->d_buf = nullptr, h->cap = 0;
-        if (mi_dspu_malloc(reinterpret_cast<void **>(&h->d_buf), 2 * n * sizeof(float)) != MI_OK)
-            return false;
-        h->cap = n;
-        return true;
-    }
 
     // the members and the phase go to the bank where it does not hold them
     bool hand_over(handle *h, uint32_t acc)
@@ -121,7 +101,7 @@ bool Oscillator::init()                                         // :119-135
             return false;
         if (mi_oscillator_bank_create(&h->bank, 1) != MI_OK)
         {
-            release(h);
+            delete h;
             return false;
         }
         pData = reinterpret_cast<uint8_t *>(h);
@@ -136,7 +116,7 @@ void Oscillator::destroy()                                      // :137-149
     sOverGetPeriods.destroy();
     if (pData != NULL)
     {
-        release(of(pData));
+        delete of(pData);
         pData = NULL;
     }
     vProcessBuffer = NULL;
@@ -213,7 +193,7 @@ void Oscillator::do_process(Oversampler *os, float *dst, size_t count)      // :
 {
     handle *h = of(pData);
     (void)os;                                                   // the bank runs the band-limited functions through its own
-    if (h == nullptr || count == 0 || !reserve(h, count))
+    if (h == nullptr || count == 0 || !h->buf.reserve(count, 2))
         return;
     if (!h->built)                                              // init() after the last update_settings(): the same members again
     {
@@ -222,13 +202,13 @@ void Oscillator::do_process(Oversampler *os, float *dst, size_t count)      // :
     }
     if (!hand_over(h, nPhaseAcc))
         return;
-    if (mi_oscillator_bank_process(h->bank, h->d_buf, nullptr, count, h->cap, h->cap, MI_OSC_OVERWRITE, nullptr) != MI_OK)
+    if (mi_oscillator_bank_process(h->bank, h->buf.row(0), nullptr, count, h->buf.capacity(), h->buf.capacity(), MI_OSC_OVERWRITE, nullptr) != MI_OK)
         return;
     const bool over = enFunction >= FG_BL_RECTANGULAR;
     const phacc_t n = phacc_t(over ? nOversampling * count : count), w = over ? nFreqCtrlWord_Over : nFreqCtrlWord;
     nPhaseAcc = (nPhaseAcc + n * w) & nPhaseAccMask;            // what the advance kernel leaves on the device
     h->acc = nPhaseAcc;
-    mi_dspu_copy_d2h(dst, h->d_buf, count * sizeof(float), nullptr);
+    h->buf.down(dst, 0, count);
 }
 
 void Oscillator::get_periods(float *dst, size_t periods, size_t periodsSkip, size_t samples)   // :635-689
@@ -237,11 +217,11 @@ void Oscillator::get_periods(float *dst, size_t periods, size_t periodsSkip, siz
     // own (sOverGetPeriods' part), the picks gathered on the device.  nPhaseAcc stays (:637, :688).  A period that is not positive
     // and finite is refused there, and nothing is written.
     handle *h = of(pData);
-    if (h == nullptr || samples == 0 || !hand_over(h, nPhaseAcc) || !reserve(h, samples))
+    if (h == nullptr || samples == 0 || !hand_over(h, nPhaseAcc) || !h->buf.reserve(samples, 2))
         return;
-    if (mi_oscillator_bank_get_periods(h->bank, 0, h->d_buf, periods, periodsSkip, samples, nullptr) != MI_OK)
+    if (mi_oscillator_bank_get_periods(h->bank, 0, h->buf.row(0), periods, periodsSkip, samples, nullptr) != MI_OK)
         return;
-    mi_dspu_copy_d2h(dst, h->d_buf, samples * sizeof(float), nullptr);
+    h->buf.down(dst, 0, samples);
 }
 
 void Oscillator::process_add(float *dst, const float *src, size_t count)       // :691-710

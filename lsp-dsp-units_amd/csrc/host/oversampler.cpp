@@ -8,7 +8,7 @@
 #include <new>
 #include <vector>
 
-#include "mi_dspu.h"
+#include "beside.h"
 
 namespace lsp
 {
@@ -19,24 +19,9 @@ namespace
     struct oversampler_impl
     {
         mi_oversampler_bank_t *bank = nullptr;
-        float  *d_base = nullptr;           // the staged base-rate block
-        float  *d_over = nullptr;           // the staged oversampled block
-        size_t  cap_base = 0, cap_over = 0;
+        mi_host::rows over;                 // [1][cap]: the staged oversampled block; two buffers, their lengths differ
+        mi_host::rows base;                 // [1][cap]: the staged base-rate block (declared last: released first, as ever)
         std::vector<float> h_over;
-
-        static bool grow(float **p, size_t *cap, size_t n)
-        {
-            if (n <= *cap)
-                return true;
-            mi_dspu_free(*p);
-            *p = nullptr;
-            *cap = 0;
-            if (mi_dspu_malloc(reinterpret_cast<void **>(p), n * sizeof(float)) != MI_OK)
-                return false;
-            *cap = n;
-            return true;
-        }
-        bool reserve(size_t base, size_t over) { return grow(&d_base, &cap_base, base) && grow(&d_over, &cap_over, over); }
     };
 
     inline oversampler_impl *impl_of(uint8_t *p) { return reinterpret_cast<oversampler_impl *>(p); }
@@ -116,8 +101,6 @@ void Oversampler::destroy()                                     // :95-106
     if (oversampler_impl *p = impl_of(bData))
     {
         mi_oversampler_bank_destroy(p->bank);
-        mi_dspu_free(p->d_base);
-        mi_dspu_free(p->d_over);
         delete p;
     }
     fUpBuffer = nullptr;
@@ -196,11 +179,11 @@ void Oversampler::upsample(float *dst, const float *src, size_t samples)       /
 {
     oversampler_impl *p = synced(bData, nMode, bFilter);
     const size_t os = get_oversampling();
-    if (p == nullptr || samples == 0 || !p->reserve(samples, samples * os))
+    if (p == nullptr || samples == 0 || !p->base.reserve(samples) || !p->over.reserve(samples * os))
         return;
-    if (mi_dspu_copy_h2d(p->d_base, src, samples * sizeof(float), nullptr) == MI_OK &&
-        mi_oversampler_bank_upsample(p->bank, p->d_over, p->d_base, samples, samples * os, samples, nullptr) == MI_OK &&
-        mi_dspu_copy_d2h(dst, p->d_over, samples * os * sizeof(float), nullptr) == MI_OK)
+    if (p->base.up(0, src, samples) &&
+        mi_oversampler_bank_upsample(p->bank, p->over.row(0), p->base.row(0), samples, samples * os, samples, nullptr) == MI_OK &&
+        p->over.down(dst, 0, samples * os))
         mi_dspu_stream_synchronize(nullptr);
 }
 
@@ -208,11 +191,11 @@ void Oversampler::downsample(float *dst, const float *src, size_t samples)     /
 {
     oversampler_impl *p = synced(bData, nMode, bFilter);
     const size_t os = get_oversampling();
-    if (p == nullptr || samples == 0 || !p->reserve(samples, samples * os))
+    if (p == nullptr || samples == 0 || !p->base.reserve(samples) || !p->over.reserve(samples * os))
         return;
-    if (mi_dspu_copy_h2d(p->d_over, src, samples * os * sizeof(float), nullptr) == MI_OK &&
-        mi_oversampler_bank_downsample(p->bank, p->d_base, p->d_over, samples, samples, samples * os, nullptr) == MI_OK &&
-        mi_dspu_copy_d2h(dst, p->d_base, samples * sizeof(float), nullptr) == MI_OK)
+    if (p->over.up(0, src, samples * os) &&
+        mi_oversampler_bank_downsample(p->bank, p->base.row(0), p->over.row(0), samples, samples, samples * os, nullptr) == MI_OK &&
+        p->base.down(dst, 0, samples))
         mi_dspu_stream_synchronize(nullptr);
 }
 
@@ -227,11 +210,11 @@ void Oversampler::process(float *dst, const float *src, size_t samples, IOversam
         }
         // nothing between up and down: the bank's process() keeps the oversampled block on the device
         oversampler_impl *p = synced(bData, nMode, bFilter);
-        if (p == nullptr || samples == 0 || !p->reserve(samples, 0))
+        if (p == nullptr || samples == 0 || !p->base.reserve(samples))
             return;
-        if (mi_dspu_copy_h2d(p->d_base, src, samples * sizeof(float), nullptr) == MI_OK &&
-            mi_oversampler_bank_process(p->bank, p->d_base, p->d_base, samples, samples, samples, nullptr, nullptr, nullptr) == MI_OK &&
-            mi_dspu_copy_d2h(dst, p->d_base, samples * sizeof(float), nullptr) == MI_OK)
+        if (p->base.up(0, src, samples) &&
+            mi_oversampler_bank_process(p->bank, p->base.row(0), p->base.row(0), samples, samples, samples, nullptr, nullptr, nullptr) == MI_OK &&
+            p->base.down(dst, 0, samples))
             mi_dspu_stream_synchronize(nullptr);
         return;
     }

@@ -18,13 +18,13 @@ namespace
 
     struct pan_held { float va = 0.0f, vb = 0.0f; uint32_t head = 0, window = 0, known = 0; };
 
-    // the bank of the object being served: beside.h's create takes the channels only
-    thread_local uint32_t g_max_period = 1;
-    int create_one(mi_panometer_bank_t **bank, uint32_t channels)
+    typedef mi_host::registry<mi_host::beside<mi_panometer_bank_t, pan_held, mi_panometer_bank_destroy> > panometers;
+
+    // the entry of `self`, its bank made for the object's nMaxPeriod at the first call
+    panometers::entry *of(const void *self, uint32_t max_period)
     {
-        return mi_panometer_bank_create(bank, channels, g_max_period);
+        return panometers::of(self, [max_period](panometers::entry &e) { return mi_panometer_bank_create(&e.bank, 1, max_period); });
     }
-    typedef mi_host::registry<mi_panometer_bank_t, pan_held, create_one, mi_panometer_bank_destroy> panometers;
 
     int send_state(mi_panometer_bank_t *bank, const pan_held &now)
     {
@@ -94,8 +94,7 @@ void Panometer::clear()                                         // :125-131
     nHead = nPeriod;
     if (nMaxPeriod == 0)
         return;
-    g_max_period = nMaxPeriod;
-    panometers::entry *p = panometers::of(this);
+    panometers::entry *p = of(this, nMaxPeriod);
     if (p == nullptr)
         return;
     const mi_panometer_state_t s = { fValueA, fValueB, nHead, 0 };
@@ -107,9 +106,8 @@ void Panometer::process(float *dst, const float *a, const float *b, size_t count
 {
     if (count == 0 || nPeriod == 0 || nCapacity == 0)
         return;                                                 // a period of 0: the reference never returns
-    g_max_period = nMaxPeriod;
-    panometers::entry *p = panometers::of(this);
-    if (p == nullptr || !p->reserve(count, 3))
+    panometers::entry *p = of(this, nMaxPeriod);
+    if (p == nullptr || !p->buf.reserve(count, 3))
         return;
     mi_panometer_params_t q;
     if (mi_panometer_bank_get_params(p->bank, 0, &q) != MI_OK)
@@ -126,12 +124,11 @@ void Panometer::process(float *dst, const float *a, const float *b, size_t count
     if (!p->hand_over_state({ fValueA, fValueB, nHead % nCapacity, (nWindow < nPeriod) ? nWindow : nPeriod, 1 }, send_state))
         return;
     p->held.known = 0;
-    float *d_a = p->d_buf, *d_b = p->d_buf + p->cap, *d_out = p->d_buf + 2 * p->cap;
+    float *d_a = p->buf.row(0), *d_b = p->buf.row(1), *d_out = p->buf.row(2);
     mi_panometer_state_t s;
-    if (mi_dspu_copy_h2d(d_a, a, count * sizeof(float), nullptr) != MI_OK ||
-        mi_dspu_copy_h2d(d_b, b, count * sizeof(float), nullptr) != MI_OK ||
+    if (!p->buf.up(0, a, count) || !p->buf.up(1, b, count) ||
         mi_panometer_bank_process(p->bank, d_out, d_a, d_b, count, count, count, count, nullptr) != MI_OK ||
-        mi_dspu_copy_d2h(dst, d_out, count * sizeof(float), nullptr) != MI_OK ||
+        !p->buf.down(dst, 2, count) ||
         mi_panometer_bank_get_state(p->bank, 0, &s, nullptr) != MI_OK)
         return;
     p->held = pan_held{ s.value_a, s.value_b, s.head, s.window, 1 };

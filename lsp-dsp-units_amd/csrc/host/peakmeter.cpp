@@ -19,7 +19,7 @@ namespace dspu
 namespace
 {
     struct peak_held { float peak = 0.0f; uint32_t counter = 0; };
-    typedef mi_host::registry<mi_peakmeter_bank_t, peak_held, mi_peakmeter_bank_create, mi_peakmeter_bank_destroy> peakmeters;
+    typedef mi_host::registry<mi_host::beside<mi_peakmeter_bank_t, peak_held, mi_peakmeter_bank_destroy> > peakmeters;
 
     int send_state(mi_peakmeter_bank_t *bank, const peak_held &now)
     {
@@ -115,7 +115,7 @@ namespace
     // the bank of `self` with the object's fTau, nHold, fPeak and nCounter on the device
     peakmeters::entry *ready(const void *self, float tau, uint32_t hold, float peak, uint32_t counter)
     {
-        peakmeters::entry *p = peakmeters::of(self);
+        peakmeters::entry *p = peakmeters::of_one(self, mi_peakmeter_bank_create);
         if (p == nullptr)
             return nullptr;
         mi_peakmeter_params_t q;
@@ -137,13 +137,13 @@ float PeakMeter::process(float *dst, const float *src, size_t count)       // :1
     if (count == 0)
         return fPeak;
     peakmeters::entry *p = ready(this, fTau, nHold, fPeak, nCounter);
-    if (p == nullptr || !p->reserve(count, 2))
+    if (p == nullptr || !p->buf.reserve(count, 2))
         return fPeak;
-    float *d_src = p->d_buf, *d_dst = p->d_buf + p->cap;
+    float *d_src = p->buf.row(0), *d_dst = p->buf.row(1);
     mi_peakmeter_state_t s;
-    if (mi_dspu_copy_h2d(d_src, src, count * sizeof(float), nullptr) != MI_OK ||
+    if (!p->buf.up(0, src, count) ||
         mi_peakmeter_bank_process(p->bank, (dst != NULL) ? d_dst : NULL, d_src, NULL, count, count, count, nullptr) != MI_OK ||
-        (dst != NULL && mi_dspu_copy_d2h(dst, d_dst, count * sizeof(float), nullptr) != MI_OK) ||
+        (dst != NULL && !p->buf.down(dst, 1, count)) ||
         mi_peakmeter_bank_get_state(p->bank, 0, &s, nullptr) != MI_OK)
         return fPeak;
     p->held = peak_held{ s.peak, s.counter };
@@ -161,13 +161,13 @@ float PeakMeter::process(float value, size_t count)                        // :1
 {
     update_settings();
     peakmeters::entry *p = ready(this, fTau, nHold, fPeak, nCounter);
-    if (p == nullptr || !p->reserve(1, 2))
+    if (p == nullptr || !p->buf.reserve(1, 2))
         return fPeak;
     // a count beyond 32 bits is beyond every counter: UINT32_MAX decays as far (the factor underflows to 0 or is 1 long before)
     const size_t n = (count < size_t(UINT32_MAX)) ? count : size_t(UINT32_MAX);
     mi_peakmeter_state_t s;
-    if (mi_dspu_copy_h2d(p->d_buf, &value, sizeof(float), nullptr) != MI_OK ||
-        mi_peakmeter_bank_process_value(p->bank, NULL, p->d_buf, n, nullptr) != MI_OK ||
+    if (!p->buf.up(0, &value, 1) ||
+        mi_peakmeter_bank_process_value(p->bank, NULL, p->buf.row(0), n, nullptr) != MI_OK ||
         mi_peakmeter_bank_get_state(p->bank, 0, &s, nullptr) != MI_OK)
         return fPeak;
     p->held = peak_held{ s.peak, s.counter };

@@ -1,6 +1,6 @@
 // lsp::dspu::Sidechain (src/main/util/Sidechain.cpp) on a mi_sidechain_bank of one channel.  The class has no member to hang
-// the bank on (its 80 bytes are the reference's), so the bank and its staging buffers live in a table keyed by the object's
-// address: made at the first call that needs the device, dropped in destroy() and in construct().  Before every device call
+// the bank on (its 80 bytes are the reference's), so the bank and its staging buffers live beside the object (beside.h's
+// registry): made at the first call that needs the device, dropped in destroy() and in construct().  Before every device call
 // the bank is handed the object's own nReactivity, fTau, nMode, nSource, fGain, the mid-side flag and the ring's capacity;
 // process() also sends fRmsValue, nRefresh and the ring position when they are not what it read back after the previous
 // call (set_mode() zeroes fRmsValue, update_settings() writes nRefresh, a subclass may write the protected fields), and
@@ -12,10 +12,8 @@
 #include <cmath>
 #include <cstddef>
 #include <cstring>
-#include <mutex>
-#include <new>
-#include <unordered_map>
 
+#include "beside.h"
 #include "sidechain_bank.h"
 
 namespace lsp
@@ -31,71 +29,27 @@ namespace
     {
         mi_sidechain_bank_t *bank = nullptr;
         uint32_t inputs = 0;
-        float  *d_buf = nullptr;            // [3][cap]: the staged inputs, the output
-        size_t  cap = 0;
+        mi_host::rows buf;                  // [3][cap]: the staged inputs, the output
         float   rms = 0.0f;                 // the state as the device holds it: a fresh bank's, then what process() read back
         uint32_t refresh = 0, head = 0;
         bool    known = false;              // ... which it does only after the first hand-over
 
-        bool reserve(size_t n)
-        {
-            if (n <= cap)
-                return true;
-            mi_dspu_free(d_buf);
-            d_buf = nullptr;
-            cap = 0;
-            if (mi_dspu_malloc(reinterpret_cast<void **>(&d_buf), 3 * n * sizeof(float)) != MI_OK)
-                return false;
-            cap = n;
-            return true;
-        }
+        ~sidechain_impl() { if (bank != nullptr) mi_sidechain_bank_destroy(bank); }
     };
-
-    std::mutex g_lock;
-    std::unordered_map<const void *, sidechain_impl *> &table()
-    {
-        static std::unordered_map<const void *, sidechain_impl *> t;
-        return t;
-    }
-
-    void drop(const void *self)
-    {
-        sidechain_impl *p = nullptr;
-        {
-            std::lock_guard<std::mutex> guard(g_lock);
-            auto it = table().find(self);
-            if (it == table().end())
-                return;
-            p = it->second;
-            table().erase(it);
-        }
-        mi_sidechain_bank_destroy(p->bank);
-        mi_dspu_free(p->d_buf);
-        delete p;
-    }
+    typedef mi_host::registry<sidechain_impl> sidechains;
 
     // the object's bank of `inputs` inputs
     sidechain_impl *impl_of(const void *self, uint32_t inputs)
     {
+        sidechain_impl *p = sidechains::find(self);
+        if (p != nullptr && p->inputs == inputs)
+            return p;
+        sidechains::drop(self);                                 // init() changed the number of inputs
+        return sidechains::of(self, [inputs](sidechain_impl &e)
         {
-            std::lock_guard<std::mutex> guard(g_lock);
-            auto it = table().find(self);
-            if (it != table().end() && it->second->inputs == inputs)
-                return it->second;
-        }
-        drop(self);                                             // init() changed the number of inputs
-        sidechain_impl *p = new (std::nothrow) sidechain_impl();
-        if (p == nullptr)
-            return nullptr;
-        p->inputs = inputs;
-        if (mi_sidechain_bank_create(&p->bank, 1, inputs, 0.0f) != MI_OK)
-        {
-            delete p;
-            return nullptr;
-        }
-        std::lock_guard<std::mutex> guard(g_lock);
-        table()[self] = p;
-        return p;
+            e.inputs = inputs;
+            return mi_sidechain_bank_create(&e.bank, 1, inputs, 0.0f);
+        });
     }
 
     // the layout of the reference class, LP64
@@ -125,7 +79,7 @@ Sidechain::~Sidechain() { destroy(); }
 
 void Sidechain::construct()                                     // Sidechain.cpp:43-60
 {
-    drop(this);                                                 // whatever lived at this address before
+    sidechains::drop(this);                                     // whatever lived at this address before
     sBuffer.construct();
     nReactivity = 0;
     fReactivity = 0.0f;
@@ -144,7 +98,7 @@ void Sidechain::construct()                                     // Sidechain.cpp
 
 void Sidechain::destroy()                                       // :62-65
 {
-    drop(this);
+    sidechains::drop(this);
     sBuffer.destroy();
 }
 
@@ -247,7 +201,7 @@ void Sidechain::process(float *out, const float **in, size_t samples)      // :4
     if (capacity < nReactivity + RING_EXTRA || nReactivity < 1)
         return;                                                 // no sample rate was set: the reference has no ring either
     sidechain_impl *p = impl_of(this, nChannels);
-    if (p == nullptr || !p->reserve(samples))
+    if (p == nullptr || !p->buf.reserve(samples, 3))
         return;
 
     // the object's fields as the bank's channel 0
@@ -270,12 +224,11 @@ void Sidechain::process(float *out, const float **in, size_t samples)      // :4
     }
     p->known = false;
 
-    float *d_in0 = p->d_buf, *d_in1 = p->d_buf + p->cap, *d_out = p->d_buf + 2 * p->cap;
+    float *d_in0 = p->buf.row(0), *d_in1 = p->buf.row(1), *d_out = p->buf.row(2);
     const bool two = nChannels == 2;
     if (in != NULL)
     {
-        if (mi_dspu_copy_h2d(d_in0, in[0], samples * sizeof(float), nullptr) != MI_OK ||
-            (two && mi_dspu_copy_h2d(d_in1, in[1], samples * sizeof(float), nullptr) != MI_OK))
+        if (!p->buf.up(0, in[0], samples) || (two && !p->buf.up(1, in[1], samples)))
             return;
     }
     const float *a = (in != NULL) ? d_in0 : nullptr, *b = (in != NULL && two) ? d_in1 : nullptr;
@@ -283,16 +236,16 @@ void Sidechain::process(float *out, const float **in, size_t samples)      // :4
     {
         // the signed source, the equalizer on it, then magnitude, gain, ring and detector
         if (mi_sidechain_bank_premix(p->bank, d_out, a, b, samples, samples, samples, samples, nullptr) != MI_OK ||
-            mi_dspu_copy_d2h(out, d_out, samples * sizeof(float), nullptr) != MI_OK)
+            !p->buf.down(out, 2, samples))
             return;
         pPreEq->process(out, out, samples);
-        if (mi_dspu_copy_h2d(d_out, out, samples * sizeof(float), nullptr) != MI_OK ||
+        if (!p->buf.up(2, out, samples) ||
             mi_sidechain_bank_process_premixed(p->bank, d_out, d_out, samples, samples, samples, nullptr) != MI_OK)
             return;
     }
     else if (mi_sidechain_bank_process(p->bank, d_out, a, b, samples, samples, samples, samples, nullptr) != MI_OK)
         return;
-    if (mi_dspu_copy_d2h(out, d_out, samples * sizeof(float), nullptr) != MI_OK ||
+    if (!p->buf.down(out, 2, samples) ||
         mi_sidechain_bank_get_state(p->bank, 0, &p->rms, &p->refresh, &p->head, nullptr) != MI_OK)
         return;
     p->known = true;

@@ -15,7 +15,7 @@ namespace dspu
 namespace
 {
     struct surge_held { float gain = 0.0f; uint32_t transition = 0, shutdown = 0, on = 0; };
-    typedef mi_host::registry<mi_surge_bank_t, surge_held, mi_surge_bank_create, mi_surge_bank_destroy> protectors;
+    typedef mi_host::registry<mi_host::beside<mi_surge_bank_t, surge_held, mi_surge_bank_destroy> > protectors;
 
     int send_state(mi_surge_bank_t *bank, const surge_held &now)
     {
@@ -84,7 +84,7 @@ namespace
     // the bank of `self` with the object's settings and state on the device
     protectors::entry *ready(const void *self, const mi_surge_params_t &want, const surge_held &now)
     {
-        protectors::entry *p = protectors::of(self);
+        protectors::entry *p = protectors::of_one(self, mi_surge_bank_create);
         if (p == nullptr)
             return nullptr;
         mi_surge_params_t q;
@@ -127,13 +127,13 @@ void SurgeProtector::process(float *out, const float *in, size_t samples)      /
         return;
     const mi_surge_params_t want = { narrow(nTransitionMax), narrow(nShutdownMax), fOnThreshold, fOffThreshold };
     protectors::entry *p = ready(this, want, surge_held{ fGain, narrow(nTransitionTime), narrow(nShutdownTime), bOn ? 1u : 0u });
-    if (p == nullptr || !p->reserve(samples, 2))
+    if (p == nullptr || !p->buf.reserve(samples, 2))
         return;
-    float *d_in = p->d_buf, *d_out = p->d_buf + p->cap;
+    float *d_in = p->buf.row(0), *d_out = p->buf.row(1);
     mi_surge_state_t s;
-    if (mi_dspu_copy_h2d(d_in, in, samples * sizeof(float), nullptr) != MI_OK ||
+    if (!p->buf.up(0, in, samples) ||
         mi_surge_bank_process(p->bank, (out != NULL) ? d_out : NULL, d_in, samples, samples, samples, nullptr) != MI_OK ||
-        (out != NULL && mi_dspu_copy_d2h(out, d_out, samples * sizeof(float), nullptr) != MI_OK) ||
+        (out != NULL && !p->buf.down(out, 1, samples)) ||
         mi_surge_bank_get_state(p->bank, 0, &s, nullptr) != MI_OK)
         return;
     p->held = surge_held{ s.gain, s.transition_time, s.shutdown_time, s.on };
@@ -154,14 +154,13 @@ void SurgeProtector::process_mul(float *out, const float *in, size_t samples)  /
         return;
     const mi_surge_params_t want = { narrow(nTransitionMax), narrow(nShutdownMax), fOnThreshold, fOffThreshold };
     protectors::entry *p = ready(this, want, surge_held{ fGain, narrow(nTransitionTime), narrow(nShutdownTime), bOn ? 1u : 0u });
-    if (p == nullptr || !p->reserve(samples, 2))
+    if (p == nullptr || !p->buf.reserve(samples, 2))
         return;
-    float *d_in = p->d_buf, *d_out = p->d_buf + p->cap;
+    float *d_in = p->buf.row(0), *d_out = p->buf.row(1);
     mi_surge_state_t s;
-    if (mi_dspu_copy_h2d(d_in, in, samples * sizeof(float), nullptr) != MI_OK ||
-        mi_dspu_copy_h2d(d_out, out, samples * sizeof(float), nullptr) != MI_OK ||
+    if (!p->buf.up(0, in, samples) || !p->buf.up(1, out, samples) ||
         mi_surge_bank_process_mul(p->bank, d_out, d_in, samples, samples, samples, nullptr) != MI_OK ||
-        mi_dspu_copy_d2h(out, d_out, samples * sizeof(float), nullptr) != MI_OK ||
+        !p->buf.down(out, 1, samples) ||
         mi_surge_bank_get_state(p->bank, 0, &s, nullptr) != MI_OK)
         return;
     p->held = surge_held{ s.gain, s.transition_time, s.shutdown_time, s.on };

@@ -7,7 +7,7 @@
 #include <cmath>
 #include <new>
 
-#include "mi_dspu.h"
+#include "beside.h"
 
 namespace lsp
 {
@@ -18,22 +18,8 @@ namespace
     struct truepeak_impl
     {
         mi_truepeak_bank_t *bank = nullptr;
-        float  *d_buf = nullptr;            // the staged block (process() runs in place on it)
+        mi_host::rows buf;                  // [1][cap]: the staged block (process() runs in place on it)
         float  *d_peak = nullptr;
-        size_t  cap = 0;
-
-        bool reserve(size_t n)
-        {
-            if (n <= cap)
-                return true;
-            mi_dspu_free(d_buf);
-            d_buf = nullptr;
-            cap = 0;
-            if (mi_dspu_malloc(reinterpret_cast<void **>(&d_buf), n * sizeof(float)) != MI_OK)
-                return false;
-            cap = n;
-            return true;
-        }
     };
 
     inline truepeak_impl *impl_of(uint8_t *p) { return reinterpret_cast<truepeak_impl *>(p); }
@@ -71,7 +57,7 @@ void TruePeakMeter::destroy()                                   // :59-67
     if (truepeak_impl *p = impl_of(pData))
     {
         mi_truepeak_bank_destroy(p->bank);
-        mi_dspu_free(p->d_buf);
+        p->buf.release();
         mi_dspu_free(p->d_peak);
         delete p;
     }
@@ -168,11 +154,11 @@ void TruePeakMeter::process(float *dst, const float *src, size_t count)    // :1
 {
     update_settings();
     truepeak_impl *p = impl_of(pData);
-    if (p == nullptr || count == 0 || !p->reserve(count))
+    if (p == nullptr || count == 0 || !p->buf.reserve(count))
         return;
-    if (mi_dspu_copy_h2d(p->d_buf, src, count * sizeof(float), nullptr) == MI_OK &&
-        mi_truepeak_bank_process(p->bank, p->d_buf, p->d_buf, count, count, count, nullptr) == MI_OK &&
-        mi_dspu_copy_d2h(dst, p->d_buf, count * sizeof(float), nullptr) == MI_OK)
+    if (p->buf.up(0, src, count) &&
+        mi_truepeak_bank_process(p->bank, p->buf.row(0), p->buf.row(0), count, count, count, nullptr) == MI_OK &&
+        p->buf.down(dst, 0, count))
         mi_dspu_stream_synchronize(nullptr);
 }
 
@@ -186,11 +172,11 @@ float TruePeakMeter::process_max(const float *src, size_t count)
 {
     update_settings();
     truepeak_impl *p = impl_of(pData);
-    if (p == nullptr || count == 0 || !p->reserve(count))
+    if (p == nullptr || count == 0 || !p->buf.reserve(count))
         return 0.0f;
     float peak = 0.0f;
-    if (mi_dspu_copy_h2d(p->d_buf, src, count * sizeof(float), nullptr) != MI_OK ||
-        mi_truepeak_bank_process_max(p->bank, p->d_peak, p->d_buf, count, count, nullptr) != MI_OK ||
+    if (!p->buf.up(0, src, count) ||
+        mi_truepeak_bank_process_max(p->bank, p->d_peak, p->buf.row(0), count, count, nullptr) != MI_OK ||
         mi_dspu_copy_d2h(&peak, p->d_peak, sizeof(float), nullptr) != MI_OK ||
         mi_dspu_stream_synchronize(nullptr) != MI_OK)
         return 0.0f;

@@ -6,7 +6,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "mi_dspu.h"
+#include "beside.h"
 
 #pragma clang fp contract(off)
 
@@ -22,26 +22,9 @@ namespace
     struct bench
     {
         mi_velvet_bank_t   *bank = nullptr;
-        float              *d_buf = nullptr;                    // [2][cap]: dst, src
-        size_t              cap = 0;
+        mi_host::rows       buf;                                // [2][cap]: dst, src
 
-        ~bench()
-        {
-            mi_velvet_bank_destroy(bank);
-            mi_dspu_free(d_buf);
-        }
-
-        bool reserve(size_t n)
-        {
-            if (n <= cap)
-                return true;
-            mi_dspu_free(d_buf);
-            d_buf = nullptr, cap = 0;
-            if (mi_dspu_malloc(reinterpret_cast<void **>(&d_buf), 2 * n * sizeof(float)) != MI_OK)
-                return false;
-            cap = n;
-            return true;
-        }
+        ~bench() { mi_velvet_bank_destroy(bank); }
     };
     thread_local bench tl_bench;
 
@@ -146,14 +129,14 @@ void Velvet::run(float *dst, const float *src, size_t count, unsigned op)
     for (size_t at = 0; at < count; at += piece)
     {
         const size_t n = (count - at < piece) ? count - at : piece;
-        if (!b.reserve(n))
+        if (!b.buf.reserve(n, 2))
             break;
-        float *d_dst = b.d_buf, *d_src = (src != nullptr) ? b.d_buf + b.cap : nullptr;
-        if (src != nullptr && mi_dspu_copy_h2d(d_src, src + at, n * sizeof(float), nullptr) != MI_OK)
+        float *d_dst = b.buf.row(0), *d_src = (src != nullptr) ? b.buf.row(1) : nullptr;
+        if (src != nullptr && !b.buf.up(1, src + at, n))
             break;
         if (mi_velvet_bank_process(b.bank, d_dst, d_src, n, n, n, op, nullptr) != MI_OK)
             break;
-        if (mi_dspu_copy_d2h(dst + at, d_dst, n * sizeof(float), nullptr) != MI_OK || mi_dspu_stream_synchronize(nullptr) != MI_OK)
+        if (!b.buf.down(dst + at, 0, n) || mi_dspu_stream_synchronize(nullptr) != MI_OK)
             break;
     }
     if (mi_velvet_bank_get_state(b.bank, 0, &s, nullptr) != MI_OK)     // where the device got to, also behind a piece that failed
