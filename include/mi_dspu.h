@@ -715,6 +715,10 @@ int mi_crossover_bank_freq_chart(mi_crossover_bank_t *bank, uint32_t band, float
  * (meters/LoudnessMeter.h:47-330, src/main/meters/LoudnessMeter.cpp): per channel a weighting filter (K by default,
  * ITU-R BS.1770), a sliding mean square over `period` ms, the channels mixed with their BS.2051 designation weights,
  * square root.  Rows of the sample buffers: row = meter * channels + channel.
+ * The weighting filters of this bank and of mi_ilufs_bank follow the process-wide exact / fast default; mi_loudness_bank_set_exact
+ * and mi_ilufs_bank_set_exact choose per bank.  A meter does not always average a filter's round-off away: a window of a few
+ * samples, a step through the K curve's high-pass or gating blocks of the filter's decaying memory read it; a host
+ * that needs the reference's reading to 1e-5 there switches the exact mode on and pays the serial recurrence's latency.
  */
 typedef struct mi_loudness_bank mi_loudness_bank_t;
 enum { MI_BS_WEIGHT_NONE = 0, MI_BS_WEIGHT_A, MI_BS_WEIGHT_B, MI_BS_WEIGHT_C, MI_BS_WEIGHT_D, MI_BS_WEIGHT_K };   /* bs::weighting_t */
@@ -734,7 +738,11 @@ int mi_loudness_bank_set_weighting(mi_loudness_bank_t *bank, int weighting);
 int mi_loudness_bank_set_designation(mi_loudness_bank_t *bank, uint32_t channel, int designation);
 int mi_loudness_bank_set_link(mi_loudness_bank_t *bank, uint32_t channel, float link);
 int mi_loudness_bank_set_active(mi_loudness_bank_t *bank, uint32_t channel, int active, void *stream);
-/* clear(), LoudnessMeter.cpp:280-295; latency() in samples, :323-326 */
+/* clear(): fLoudness, the lines and running sums of the enabled channels, and the weighting filters' memory are zeroed; the
+ * filters stay as they are.  A DELIBERATE DEVIATION from LoudnessMeter.cpp:274-289, whose sFilter.clear() on a Filter with an
+ * external bank makes the next process() add the cascades to the bank a second time (sBank.nItems 2 -> 4 with the K curve) over
+ * stale packed sections and delays that were not zeroed, until the next filter update: ill-defined there.
+ * This is what the reference computes for clear() followed by a forced filter update.  latency() in samples, :326-329 */
 int mi_loudness_bank_clear(mi_loudness_bank_t *bank, void *stream);
 /* bind(id, out, in) with / without an input: an enabled channel without an input is left out of the blocks (its filter does
  * not run, its squares line is not written, it is not mixed: LoudnessMeter.cpp:421-422) but keeps taking part in
@@ -756,6 +764,8 @@ int mi_loudness_bank_process_gain(mi_loudness_bank_t *bank, float *out, float *c
                                   size_t out_stride, size_t in_stride, float gain, void *stream);
 /* loudness(): the last value of the mixed loudness recorded by process() (HOST array of `meters` floats; synchronises) */
 int mi_loudness_bank_loudness(mi_loudness_bank_t *bank, float *loudness, void *stream);
+/* mi_biquad_bank_set_exact of the weighting filters (the bank starts with the process-wide default) */
+int mi_loudness_bank_set_exact(mi_loudness_bank_t *bank, int on);
 
 /*
  * mi_ilufs_bank: `meters` x lsp::dspu::ILUFSMeter(channels) sharing one configuration
@@ -785,8 +795,12 @@ int mi_ilufs_bank_needs_update(const mi_ilufs_bank_t *bank, int *pending);
 int mi_ilufs_bank_update_settings(mi_ilufs_bank_t *bank, void *stream);
 int mi_ilufs_bank_loudness(mi_ilufs_bank_t *bank, float *loudness, void *stream);
 /* The gating-block history as the meters hold it (vLoudness / nMSHead / nMSCount of ILUFSMeter.h): hist is HOST memory
- * [meters][*size] (NULL: only the size is wanted), head / count HOST [meters] or NULL. */
+ * [meters][*size] (NULL: only the size is wanted), head / count HOST [meters] or NULL.  *size is nMSSize: max(int_count, 64)
+ * floats rounded up to DEFAULT_ALIGN = 0x40 bytes (ILUFSMeter.cpp:299; the constant is lsp-common-lib's and unpinned). */
 int mi_ilufs_bank_history(mi_ilufs_bank_t *bank, float *hist, uint32_t *size, uint32_t *head, uint32_t *count, void *stream);
+/* mi_biquad_bank_set_exact of the weighting filters (the bank starts with the process-wide default); on: reserves the buffer
+ * of the exact path, so that process() never allocates.  In the exact mode the bookkeeping is always a launch of its own. */
+int mi_ilufs_bank_set_exact(mi_ilufs_bank_t *bank, int on);
 
 /* ---- true-peak meter bank (ITU-R BS.1770-4 Annex 2) ------------------------------------------------------------------ */
 /*

@@ -2074,6 +2074,7 @@ namespace mi
     // `ep` != NULL: the integrated meter's bookkeeping for this call; *rode tells whether it went with the launch (then
     // the caller has nothing left to do) or the call did not qualify (the caller launches its own kernel behind this one).
     void biquad_bank_output_reread(mi_biquad_bank *b, bool yes) { if (b != nullptr) b->out_reread = yes; }
+    bool biquad_bank_exact(const mi_biquad_bank *b) { return b != nullptr && b->exact; }
 
     int biquad_bank_sumsq(mi_biquad_bank *b, const float *in, size_t in_stride, size_t samples, const uint32_t seg_end[3],
                           float *sums, hipStream_t st, const mi_meters::ilufs_epilogue *ep, bool *rode)

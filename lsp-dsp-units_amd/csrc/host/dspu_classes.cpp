@@ -2768,6 +2768,7 @@ status_t LoudnessMeter::set_sample_rate(size_t sample_rate)
         return STATUS_OK;
     if (mi_loudness_bank_set_sample_rate(p->bank, uint32_t(sample_rate), nullptr) != MI_OK)
         return STATUS_NO_MEM;
+    fLoudness = 0.0f;                                       // clear() (:321, :276)
     nSampleRate = sample_rate;
     nFlags |= F_UPD_ALL;
     return STATUS_OK;
@@ -2789,6 +2790,8 @@ void LoudnessMeter::run(float *out, size_t count, float gain, bool with_gain)
 {
     impl_t *p = impl();
     const size_t K = nChannels;
+    if (p != nullptr && count == 0)                         // no samples: update_settings() all the same (:465, :518)
+        update_settings();
     if (p == nullptr || count == 0 || !p->d_in.reserve(count, K) || !p->d_ch.reserve(count, K) || !p->d_out.reserve(count))
         return;
     p->host.assign(K * count, 0.0f);
@@ -3019,6 +3022,8 @@ void ILUFSMeter::set_integration_period(float period)           // :264-289
     period = (period < lo) ? lo : (period > fMaxIntTime) ? fMaxIntTime : period;       // lsp_limit, :266
     if (fIntTime == period)
         return;
+    if (fIntTime <= 0 || period <= 0.0f)                    // clear_block_buffers() drops F_BLK_FULL (:531)
+        nFlags &= ~uint32_t(F_BLK_FULL);
     fIntTime = period;
     nFlags |= F_UPD_TIME;
     mi_ilufs_bank_set_integration_period(p->bank, period, nullptr);
@@ -3035,7 +3040,7 @@ status_t ILUFSMeter::set_sample_rate(size_t sample_rate)
         return STATUS_NO_MEM;
     fLoudness = 0.0f;
     nSampleRate = uint32_t(sample_rate);
-    nFlags |= F_UPD_ALL;
+    nFlags = F_UPD_ALL;                                     // assigned (:315)
     return STATUS_OK;
 }
 
@@ -3043,6 +3048,8 @@ void ILUFSMeter::process(float *out, size_t count, float gain)
 {
     impl_t *p = impl();
     const size_t K = nChannels;
+    if (p != nullptr && count == 0)                         // no samples: update_settings() all the same (:358)
+        update_settings();
     if (p == nullptr || count == 0 || !p->d_in.reserve(count, K) || !p->d_out.reserve(count))
         return;
     p->host.assign(K * count, 0.0f);
@@ -3065,7 +3072,11 @@ void ILUFSMeter::process(float *out, size_t count, float gain)
     ok = ok && mi_dspu_stream_synchronize(nullptr) == MI_OK;
     if (ok)
         mi_ilufs_bank_loudness(p->bank, &fLoudness, nullptr);
-    nFlags = 0;                                             // process() starts with update_settings() (:357-358)
+    // process() starts with update_settings() (:357-358); a gating block completed since then leaves F_BLK_FULL set (:394),
+    // which needs_update() reports like any other flag
+    int full = 0;
+    mi_ilufs_bank_needs_update(p->bank, &full);
+    nFlags = full ? F_BLK_FULL : 0;
 }
 
 void ILUFSMeter::clear()
@@ -3074,6 +3085,7 @@ void ILUFSMeter::clear()
     if (p == nullptr)
         return;
     fLoudness = 0.0f;
+    nFlags &= ~uint32_t(F_BLK_FULL);                        // clear_block_buffers() (:531)
     mi_ilufs_bank_clear(p->bank, nullptr);
 }
 

@@ -919,8 +919,8 @@ static int loudness_process(mi_loudness_bank_t *b, float *out, float *ch_out, co
                             size_t out_stride, size_t in_stride, float gain, bool remember, void *stream)
 {
     MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_loudness_bank_process: NULL bank");
-    if (count == 0)
-        return MI_OK;
+    if (count == 0)                                         // still update_settings() (LoudnessMeter.cpp:465, :518)
+        return (b->sample_rate != 0) ? update_settings(b, mi::as_stream(stream)) : MI_OK;
     {
         const int rc = mi::capture_touch(mi::as_stream(stream), b, "loudness meter", loudness_bank_positions);
         if (rc != MI_OK)
@@ -1005,6 +1005,14 @@ int mi_loudness_bank_process_gain(mi_loudness_bank_t *b, float *out, float *ch_o
     return loudness_process(b, out, ch_out, in, count, out_stride, in_stride, gain, false, stream);
 }
 
+/* The weighting filters in the reference's serial recurrence (mi_biquad_bank_set_exact) or in the time-parallel kernels; the bank
+ * starts with the process-wide default. */
+int mi_loudness_bank_set_exact(mi_loudness_bank_t *b, int on)
+{
+    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_loudness_bank_set_exact: NULL bank");
+    return mi_biquad_bank_set_exact(b->filters, on);
+}
+
 int mi_loudness_bank_loudness(mi_loudness_bank_t *b, float *loudness, void *stream)
 {
     MI_REQUIRE(b != nullptr && loudness != nullptr, MI_EINVAL, "mi_loudness_bank_loudness: bad argument");
@@ -1047,8 +1055,38 @@ namespace
     }
 } // namespace
 
+namespace
+{
+    // The sums of squares of the filtered rows over the up to four pieces of a call, one wave per row: seg[row * 4 + k] += the
+    // squares of flt[row][from_k .. to_k).  Rows of channels that are switched off hold nothing and add nothing.
+    struct piece_ends { uint32_t from[4], to[4], count; };
+    constexpr size_t EXACT_PASS = 4096;                     // samples of a pass in the exact mode: what d_flt holds per row
+
+    __global__ __launch_bounds__(64)
+    void ilufs_sumsq_kernel(float *seg, const float *__restrict__ flt, size_t flt_stride, const piece_ends pe,
+                            const chan_cfg *__restrict__ cfg, uint32_t channels)
+    {
+        const uint32_t row = blockIdx.x;
+        if (!cfg[row % channels].enabled)
+            return;
+        const float *x = flt + size_t(row) * flt_stride;
+        for (uint32_t k = 0; k < pe.count; ++k)
+        {
+            float s = 0.0f;
+            for (uint32_t i = pe.from[k] + threadIdx.x; i < pe.to[k]; i += 64)
+                s = fmaf(x[i], x[i], s);
+            #pragma unroll
+            for (int w = 32; w > 0; w >>= 1)
+                s += __shfl_xor(s, w);
+            if (threadIdx.x == 0)
+                seg[size_t(row) * 4 + k] += s;
+        }
+    }
+} // namespace
+
 struct mi_ilufs_bank
 {
+    float      *d_flt = nullptr;            // [rows][EXACT_PASS]: the weighting filters' output of one pass in the exact mode
     uint32_t    meters = 0, channels = 0, rows = 0;
     uint32_t    sample_rate = 0, block_size = 0, block_offset = 0, block_part = 0, ms_size = 0, ms_int = 0;
     float       block_period = 400.0f, int_time = 60.0f, max_int_time = 60.0f, avg = 1.0f;
@@ -1161,6 +1199,8 @@ int mi_ilufs_bank_create(mi_ilufs_bank_t **bank, uint32_t meters, uint32_t chann
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b->d_cfg), channels * sizeof(chan_cfg));
         if (e == hipSuccess) e = hipMemset(b->d_block, 0, size_t(b->rows) * 4 * sizeof(float));
         if (e == hipSuccess) e = hipMemset(b->d_state, 0, meters * sizeof(ilufs_state));
+        if (e == hipSuccess && mi::biquad_bank_exact(b->filters))       // the process-wide default: the buffer of the exact path
+            e = hipMalloc(reinterpret_cast<void **>(&b->d_flt), size_t(b->rows) * EXACT_PASS * sizeof(float));
     }
     if (r != MI_OK || e != hipSuccess)
     {
@@ -1177,6 +1217,7 @@ int mi_ilufs_bank_destroy(mi_ilufs_bank_t *b)
         return MI_OK;
     mi_biquad_bank_destroy(b->filters);
     (void)hipFree(b->d_block); (void)hipFree(b->d_hist); (void)hipFree(b->d_seg); (void)hipFree(b->d_state); (void)hipFree(b->d_cfg); (void)hipFree(b->d_arrived);
+    (void)hipFree(b->d_flt);
     delete b;
     return MI_OK;
 }
@@ -1208,7 +1249,9 @@ int mi_ilufs_bank_set_sample_rate(mi_ilufs_bank_t *b, uint32_t sample_rate, void
     MI_REQUIRE(blk > 0, MI_EINVAL, "mi_ilufs_bank_set_sample_rate: block period too short for %u Hz", sample_rate);
     const size_t int_count = (size_t(b->max_int_time * float(sample_rate)) + blk - 1) / blk;
     size_t blocks = (int_count > MIN_GATING_BLOCKS) ? int_count : MIN_GATING_BLOCKS;
-    blocks = (blocks + 3) & ~size_t(3);                     // align_size(.., DEFAULT_ALIGN = 16 bytes)
+    // align_size(.., DEFAULT_ALIGN), :299.  DEFAULT_ALIGN belongs to a library the reference tree lacks: 0x40 bytes (16 floats)
+    // here, as everywhere else in this project (the Correlometer, Panometer and Depopper banks); see DESIGN.md
+    blocks = (blocks + 15) & ~size_t(15);
     (void)hipFree(b->d_hist);
     b->d_hist = nullptr;
     MI_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&b->d_hist), size_t(b->meters) * blocks * sizeof(float)));
@@ -1300,8 +1343,11 @@ int mi_ilufs_bank_process(mi_ilufs_bank_t *b, float *out, const float *in, size_
                           size_t in_stride, float gain, void *stream)
 {
     MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_ilufs_bank_process: NULL bank");
-    if (count == 0)
-        return MI_OK;
+    if (count == 0)                                         // still update_settings() (:358), which wipes F_BLK_FULL too (:519)
+    {
+        b->blk_full = false;
+        return (b->sample_rate != 0) ? ilufs_update(b, mi::as_stream(stream)) : MI_OK;
+    }
     {
         const int rc = mi::capture_touch(mi::as_stream(stream), b, "integrated loudness meter", ilufs_bank_positions);
         if (rc != MI_OK)
@@ -1319,6 +1365,11 @@ int mi_ilufs_bank_process(mi_ilufs_bank_t *b, float *out, const float *in, size_
     b->blk_full = false;
     // Up to four pieces (runs inside one quarter of a gating block) per pair of launches: the weighting filter walks
     // them as one block and leaves the pieces' sums of squares, the meters' kernel does the bookkeeping piece by piece.
+    // In the exact mode (mi_ilufs_bank_set_exact) the filter is the serial recurrence into d_flt, a wave per row sums the pieces'
+    // squares, and the bookkeeping is always a launch of its own.
+    const bool exact = mi::biquad_bank_exact(b->filters);
+    MI_REQUIRE(!exact || b->d_flt != nullptr, MI_ESTATE, "mi_ilufs_bank_process: no buffer for the exact mode");
+    const size_t pass = exact ? EXACT_PASS : (size_t(1) << 30);
     size_t offset = 0;
     while (offset < count)
     {
@@ -1326,10 +1377,9 @@ int mi_ilufs_bank_process(mi_ilufs_bank_t *b, float *out, const float *in, size_
         pcs.count = 0;
         uint32_t ends[3] = { 0, 0, 0 };
         size_t taken = 0;
-        while (pcs.count < 4 && offset + taken < count && taken < (size_t(1) << 30))
+        while (pcs.count < 4 && offset + taken < count && taken < pass)
         {
-            const size_t n = std::min<size_t>(std::min<size_t>(count - offset - taken, b->block_size - b->block_offset),
-                                              (size_t(1) << 30) - taken);
+            const size_t n = std::min<size_t>(std::min<size_t>(count - offset - taken, b->block_size - b->block_offset), pass - taken);
             ilufs_piece &pc = pcs.p[pcs.count];
             pc.offset = uint32_t(taken);
             pc.n = uint32_t(n);
@@ -1355,18 +1405,37 @@ int mi_ilufs_bank_process(mi_ilufs_bank_t *b, float *out, const float *in, size_
         }
         for (uint32_t k = pcs.count; k < 3; ++k)
             ends[k] = uint32_t(taken);
-        mi_meters::ilufs_epilogue ep;
-        ep.arrived = b->d_arrived; ep.block = b->d_block; ep.cfg = b->d_cfg; ep.channels = b->channels;
-        ep.out = out ? out + offset : nullptr; ep.out_stride = out_stride; ep.st = b->d_state; ep.gain = gain;
-        ep.hist = b->d_hist; ep.size = b->ms_size; ep.ms_int = b->ms_int; ep.avg = b->avg; ep.pieces = pcs;
+        float *const o = out ? out + offset : nullptr;
         bool rode = false;
-        r = mi::biquad_bank_sumsq(b->filters, in + offset, in_stride, taken, ends, b->d_seg, st, &ep, &rode);
-        if (r != MI_OK)
-            return r;
-        if (!rode)                                          // short or ragged call: the bookkeeping in a launch of its own
+        if (exact)
+        {
+            r = mi_biquad_bank_process(b->filters, b->d_flt, in + offset, taken, EXACT_PASS, in_stride, stream);
+            if (r != MI_OK)
+                return r;
+            piece_ends pe;
+            pe.count = pcs.count;
+            for (uint32_t k = 0; k < 4; ++k)
+            {
+                pe.from[k] = (k < pcs.count) ? pcs.p[k].offset : 0u;
+                pe.to[k] = (k < pcs.count) ? pcs.p[k].offset + pcs.p[k].n : 0u;
+            }
+            hipLaunchKernelGGL(ilufs_sumsq_kernel, dim3(b->rows), dim3(64), 0, st, b->d_seg, b->d_flt, EXACT_PASS, pe, b->d_cfg, b->channels);
+            MI_HIP_CHECK(hipGetLastError());
+        }
+        else
+        {
+            mi_meters::ilufs_epilogue ep;
+            ep.arrived = b->d_arrived; ep.block = b->d_block; ep.cfg = b->d_cfg; ep.channels = b->channels;
+            ep.out = o; ep.out_stride = out_stride; ep.st = b->d_state; ep.gain = gain;
+            ep.hist = b->d_hist; ep.size = b->ms_size; ep.ms_int = b->ms_int; ep.avg = b->avg; ep.pieces = pcs;
+            r = mi::biquad_bank_sumsq(b->filters, in + offset, in_stride, taken, ends, b->d_seg, st, &ep, &rode);
+            if (r != MI_OK)
+                return r;
+        }
+        if (!rode)                                          // exact, short or ragged call: the bookkeeping in a launch of its own
         {
             hipLaunchKernelGGL(ilufs_call_kernel, dim3(b->meters), dim3(LT), 0, st, b->d_block, b->d_seg, pcs, b->d_cfg, b->channels,
-                               ep.out, out_stride, b->d_state, gain, b->d_hist, b->ms_size, b->ms_int, b->avg);
+                               o, out_stride, b->d_state, gain, b->d_hist, b->ms_size, b->ms_int, b->avg);
             MI_HIP_CHECK(hipGetLastError());
         }
         offset += taken;
@@ -1374,10 +1443,22 @@ int mi_ilufs_bank_process(mi_ilufs_bank_t *b, float *out, const float *in, size_
     return MI_OK;
 }
 
+/* The weighting filters in the reference's serial recurrence (mi_biquad_bank_set_exact) or in the time-parallel kernels; the bank
+ * starts with the process-wide default.  Switching on reserves the exact path's buffer, so that process() never allocates. */
+int mi_ilufs_bank_set_exact(mi_ilufs_bank_t *b, int on)
+{
+    MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_ilufs_bank_set_exact: NULL bank");
+    if (on && b->d_flt == nullptr)
+        MI_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&b->d_flt), size_t(b->rows) * EXACT_PASS * sizeof(float)));
+    return mi_biquad_bank_set_exact(b->filters, on);
+}
+
 int mi_ilufs_bank_needs_update(const mi_ilufs_bank_t *b, int *pending)                        // ILUFSMeter.h:244
 {
     MI_REQUIRE(b != nullptr && pending != nullptr, MI_EINVAL, "mi_ilufs_bank_needs_update: bad argument");
-    *pending = (b->upd_filters || b->upd_time) ? 1 : 0;
+    // nFlags != 0, and F_BLK_FULL is one of nFlags' bits (ILUFSMeter.h:62-66): the reference's meter reports a pending update
+    // from the first full gating block of a call until the next update_settings() or clear_block_buffers()
+    *pending = (b->upd_filters || b->upd_time || b->blk_full) ? 1 : 0;
     return MI_OK;
 }
 
@@ -1385,6 +1466,7 @@ int mi_ilufs_bank_update_settings(mi_ilufs_bank_t *b, void *stream)             
 {
     MI_REQUIRE(b != nullptr, MI_ESTATE, "mi_ilufs_bank_update_settings: NULL bank");
     MI_REQUIRE(b->sample_rate != 0, MI_ESTATE, "mi_ilufs_bank_update_settings: set_sample_rate() first");
+    b->blk_full = false;                                    // nFlags = 0 (:519)
     return ilufs_update(b, mi::as_stream(stream));
 }
 

@@ -88,6 +88,7 @@ namespace mi
     // ep != NULL: the integrated loudness meter's bookkeeping of this call (ilufs_device.h) goes with the launch when the
     // call qualifies (*rode = true: the last workgroup of every meter does it), otherwise the caller's own kernel follows.
     void        biquad_bank_output_reread(mi_biquad_bank_t *bank, bool yes);   // process()'s output feeds the owner's next launch
+    bool        biquad_bank_exact(const mi_biquad_bank_t *bank);               // the bank's mode (mi_biquad_bank_set_exact, or the default it started with)
     int         biquad_bank_sumsq(mi_biquad_bank_t *bank, const float *in, size_t in_stride, size_t samples,
                                   const uint32_t seg_end[3], float *sums, hipStream_t st,
                                   const mi_meters::ilufs_epilogue *ep = nullptr, bool *rode = nullptr);

@@ -2937,6 +2937,9 @@ class LoudnessBank:
         else:
             check(lib.mi_loudness_bank_process_gain(*args, float(gain), _stream(stream)))
 
+    def set_exact(self, on=True):
+        check(lib.mi_loudness_bank_set_exact(self.handle, 1 if on else 0))
+
     def loudness(self, stream=None):
         v = (c_float * self.meters)()
         check(lib.mi_loudness_bank_loudness(self.handle, v, _stream(stream)))
@@ -2985,6 +2988,9 @@ class ILUFSBank:
         check(lib.mi_ilufs_bank_process(self.handle, _ptr(out) if out is not None else None, _ptr(inp), count,
                                         count if out_stride is None else out_stride,
                                         count if in_stride is None else in_stride, float(gain), _stream(stream)))
+
+    def set_exact(self, on=True):
+        check(lib.mi_ilufs_bank_set_exact(self.handle, 1 if on else 0))
 
     def loudness(self, stream=None):
         v = (c_float * self.meters)()

@@ -26,6 +26,15 @@ their sanitizer twins, drivers filter_driver.cpp and dynfilter_driver.cpp, stand
 ref_overlay/filters/; tests/golden/filter_ref_*.npz and dynfilter_ref_*.npz,
 tests/test_filter_reference_*.py and tests/test_dynfilter_reference_*.py): the designer,
 Filter::limit, the bank's packing and clear / keep rules, the dynamic cascade builders.
+LoudnessMeter and ILUFSMeter likewise, with the reference's own Filter, FilterBank and
+designation table (Makefile -> _ref/loudness_ref and _ref/loudness_ref_san, driver
+loudness_driver.cpp, stand-ins in ref_overlay/meters/; tests/golden/loudness_ref_vectors.npz
+and ilufs_ref_vectors.npz, tests/test_loudness_reference_*.py): the ring and its refresh
+schedule, the two process() forms, linking, binding and nOffset, the gating blocks, the
+lost F_BLK_FULL, the history and its halving.  Not pinned there: the summation order of
+dsp::h_sum / h_sqr_sum, the result type of the mixed lsp_min, DEFAULT_ALIGN (0x40: the
+length of the ILUFSMeter's history) -- and LoudnessMeter::clear(), which the reference
+leaves ill-defined (loudness.py): only its forced-update equivalent is.
 It does not pin lsp-dsp-lib's array primitives or their SIMD variants (dsp::max_index
 and dsp::abs_mul3 of the Limiter among them), the order of the Sidechain's refresh sums,
 the Lanczos tables or the arithmetic inside an IIR section (the Sidechain's detectors

@@ -10,7 +10,10 @@ the reference's chunking (BUFFER_SIZE 0x400) and these behaviours of the referen
     within the same call.
 
 The reference has no unit test for it (src/test/mtest/meters/ilufs.cpp is a manual test without expected values).  Pinned
-instead by the standard: a 0 dBFS 997 Hz sine integrates to -3.01 LKFS (ITU-R BS.1770-4), tests/test_oracle_ilufs.py.
+by the standard: a 0 dBFS 997 Hz sine integrates to -3.01 LKFS (ITU-R BS.1770-4), tests/test_oracle_ilufs.py; and by the
+reference's own class compiled from its unmodified text (oracle/_ref/loudness_ref): every output and every state value it recorded
+after every call in tests/golden/ilufs_ref_vectors.npz, bit for bit (tests/test_loudness_reference_host.py).  UNPINNED there:
+DEFAULT_ALIGN (0x40), which decides the history's length, and the serial order of h_sqr_sum.
 lsp-dsp-lib primitives restated: h_sqr_sum (sequential float sum of x*x), fill, mul_k2.
 """
 import numpy as np
@@ -36,7 +39,7 @@ def _h_sqr_sum(v):
 class ILUFSMeter:
     def __init__(self, channels, max_int_time=60.0, block_period=400.0):
         self.nch = channels
-        self.ch = [dict(weight=F(0.0), enabled=True, block=np.zeros(4, np.float32), coef=None, state=None)
+        self.ch = [dict(weight=F(0.0), enabled=True, bound=True, block=np.zeros(4, np.float32), coef=None, state=None)
                    for _ in range(channels)]
         if channels == 1:
             self.ch[0]["weight"] = channel_weighting(CHANNEL_CENTER)
@@ -62,6 +65,15 @@ class ILUFSMeter:
 
     def set_active(self, i, active=True):
         self.ch[i]["enabled"] = bool(active)
+
+    def set_bound(self, i, bound=True):                       # bind(id, in) with in == NULL or not: left out like a disabled one (:370)
+        self.ch[i]["bound"] = bool(bound)
+
+    def needs_update(self):                                   # nFlags != 0, and F_BLK_FULL is one of its bits (ILUFSMeter.h:62-66, :244)
+        return bool(self.upd_filters or self.upd_time or self.blk_full)
+
+    def update_settings(self):
+        self._update()
 
     def set_weighting(self, w):
         if w != self.weighting:
@@ -106,7 +118,9 @@ class ILUFSMeter:
         self.sr = sr
         blk = self._blk()
         int_count = (int(F(self.max_int_time * F(sr))) + blk - 1) // blk
-        blocks = (max(int_count, MIN_GATING_BLOCKS) + 3) & ~3
+        # align_size(.., DEFAULT_ALIGN), :299.  UNPINNED: DEFAULT_ALIGN is lsp-common-lib's, which the reference tree lacks; 0x40 bytes
+        # (16 floats) is this project's one reading of it (oracle/ref_shim, the Correlometer, Panometer and Depopper banks)
+        blocks = (max(int_count, MIN_GATING_BLOCKS) + 15) & ~15
         self.hist = np.zeros(blocks, np.float32)
         self.avg = F(F(0.25) / F(blk))
         self.block_size = blk; self.ms_size = blocks
@@ -166,7 +180,7 @@ class ILUFSMeter:
             todo = min(n - off, self.block_size - self.block_offset, BUFFER_SIZE)
             if todo > 0:
                 for i, c in enumerate(self.ch):
-                    if not c["enabled"]:
+                    if not c["enabled"] or not c["bound"]:
                         continue
                     y, c["state"] = B.biquad_cascade(x[i, off:off + todo], c["coef"], c["state"])
                     c["block"][self.block_part] = F(c["block"][self.block_part] + _h_sqr_sum(y))

@@ -4,8 +4,20 @@ ORACLE (test infrastructure only).  Restatement of lsp::dspu::LoudnessMeter
 :381-407 refresh_rms, :409-466 process_channels, :468-560 process) with the reference's own chunking (BUFFER_SIZE 0x400),
 running-sum update order and refresh schedule, float32 throughout.
 
-The reference has no unit test for it.  Pinned instead by the standard it implements: a 0 dBFS 997 Hz sine reads
--3.01 LKFS (ITU-R BS.1770-4, and the -0.691 dB of misc/broadcast.h:96), see tests/test_oracle_loudness.py.
+The reference has no unit test for it.  Pinned by the standard it implements: a 0 dBFS 997 Hz sine reads
+-3.01 LKFS (ITU-R BS.1770-4, and the -0.691 dB of misc/broadcast.h:96), see tests/test_oracle_loudness.py; and by the reference's
+own class compiled from its unmodified text (oracle/_ref/loudness_ref): every output and every state value it recorded after every
+call in tests/golden/loudness_ref_vectors.npz, bit for bit (tests/test_loudness_reference_host.py).
+
+DELIBERATE DEVIATION: clear().  The reference's (LoudnessMeter.cpp:274-289) calls sFilter.clear(), which on a Filter whose bank is
+external only sets FF_CLEAR; the next Filter::process then runs rebuild() without begin() / end() (Filter.cpp:208-212, 398-402): the
+cascades are added to the bank a second time (sBank.nItems 2 -> 4 for K, 3 -> 4 for A, nLastItems unchanged), the packed biquad_t
+is not repacked, the delays are not zeroed, and FilterBank::process walks a union packed for fewer sections until the next filter
+update -- outputs up to 23 for 0.2-rms noise, and other bytes from a sanitizer build than from a plain one.  Ill-defined, so not
+restated: clear() here zeroes the filter memory and the lines and keeps the filter, which is what the reference computes for clear()
+followed by a forced filter update (set_weighting(other); set_weighting(back)), the recorded case "clear defined".  The recording keeps
+the bare clear() as a fact only (nItems before and after).  set_sample_rate(), which calls clear() and then rebuilds everything, is
+well defined and matched.
 lsp-dsp-lib primitives restated: sqr2 (x*x), h_sum (sequential float sum), ssqrt1 (sqrt of the non-negative part),
 mul_k3 / fmadd_k3 / mix_copy2 (one multiply-add per element).
 """
@@ -105,6 +117,12 @@ class LoudnessMeter:
 
     def latency(self):
         return int(F(F(self.period_ms * F(0.001)) * F(self.sr)))
+
+    def needs_update(self):                                   # LoudnessMeter.h:264
+        return bool(self.upd_filters or self.upd_time)
+
+    def update_settings(self):
+        self._update()
 
     def _update(self):
         if self.upd_time:
