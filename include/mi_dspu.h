@@ -2574,6 +2574,59 @@ int mi_metergraph_bank_process_value(mi_metergraph_bank_t *bank, const float *va
 int mi_metergraph_bank_read(mi_metergraph_bank_t *bank, float *dst, size_t count, size_t stride, void *stream);
 int mi_metergraph_bank_level(mi_metergraph_bank_t *bank, float *levels, void *stream);
 
+/* ---- ScaledMeterGraph bank (display frames of a period that can change: a zoomable time graph) ------------------------------------ */
+/*
+ * mi_scaled_metergraph_bank: `channels` x lsp::dspu::ScaledMeterGraph (util/ScaledMeterGraph.h, src/main/util/ScaledMeterGraph.cpp).
+ * Every channel samples its row twice: into a history ring of sub-samples of `subsampling` samples each, and into a ring of
+ * display frames of the period last taken over.  The call after a set_period() that changed the period re-decimates the history
+ * into the frame ring instead (update_period(), :269-342).  Both rings, both heads and every state word are the reference's in
+ * every bit (DESIGN.md 3.31 lists the quirks that are kept).
+ *   - one process() call is one process(s, n) (gains == NULL) or process(s, gain, n) of every channel;
+ *   - create() leaves every channel as construct() does (ABS_MAXIMUM, no rings); a channel needs init() and then set_period() before
+ *     the bank processes or reads: MI_ESTATE otherwise (with sFrames.nPeriod == 0 the reference's process() never returns);
+ *   - where the reference is undefined init() answers MI_EINVAL: subsampling == 0, frames == 0, max_period < subsampling; also
+ *     where frames * max_period reaches 2^31 (the reference multiplies in 32 bits) or the rings are larger than create() made them;
+ *   - init(), the setters and fill() pend until update_settings(), which process(), process_value(), read(), level(), get_state()
+ *     and set_state() run first; with something pending that is MI_ESTATE on a stream being captured;
+ *   - process(), process_value(), read() and level() are capturable: the kernels keep the state and decide on the device whether
+ *     to re-decimate, so a replay appends again and re-decimates only where the periods differ.
+ */
+typedef struct mi_scaled_metergraph_bank mi_scaled_metergraph_bank_t;
+/* sHistory's fCurrent, nCount and its ring's nHead; sFrames' three and sFrames.nPeriod (the period last taken over, 0: none) */
+typedef struct { float history_current; uint32_t history_count, history_head; float frames_current; uint32_t frames_count, frames_head,
+                 frames_period; } mi_scaled_metergraph_state_t;
+/* enMethod, nPeriod (the target, 0: none set), nMaxPeriod, sHistory.nPeriod, sFrames.nFrames, sHistory.nFrames.  The rings hold
+ * subframes + 16 and frames + 16 words (FRAMES_GAP, :30) */
+typedef struct { uint32_t method, period, max_period, subsampling, frames, subframes; } mi_scaled_metergraph_params_t;
+/* max_subframes: the most ceil(frames * max_period / subsampling) of any init() to come, max_frames .. 2^24 */
+int mi_scaled_metergraph_bank_create(mi_scaled_metergraph_bank_t **bank, uint32_t channels, uint32_t max_frames, uint32_t max_subframes);
+int mi_scaled_metergraph_bank_destroy(mi_scaled_metergraph_bank_t *bank);
+/* init(frames, subsampling, max_period), :67-91: zeroed rings, every state word 0, no period; enMethod stays */
+int mi_scaled_metergraph_bank_init(mi_scaled_metergraph_bank_t *bank, uint32_t channel, size_t frames, size_t subsampling, size_t max_period);
+/* a method outside the enum runs as MI_MM_ABS_MAXIMUM (the reference's default: label); takes effect in mid-frame too */
+int mi_scaled_metergraph_bank_set_method(mi_scaled_metergraph_bank_t *bank, uint32_t channel, uint32_t method);
+/* the target only, limited to subsampling .. max_period (:95); MI_ESTATE before init() */
+int mi_scaled_metergraph_bank_set_period(mi_scaled_metergraph_bank_t *bank, uint32_t channel, size_t period);
+/* fill(level), :376-383: every word of both rings, both nCount = 0; heads and fCurrent stay.  channel UINT32_MAX: all */
+int mi_scaled_metergraph_bank_fill(mi_scaled_metergraph_bank_t *bank, uint32_t channel, float level);
+int mi_scaled_metergraph_bank_update_settings(mi_scaled_metergraph_bank_t *bank, void *stream);
+int mi_scaled_metergraph_bank_get_params(const mi_scaled_metergraph_bank_t *bank, uint32_t channel, mi_scaled_metergraph_params_t *params);
+/* history, ring: NULL, or HOST arrays of the channel's subframes + 16 and frames + 16 words in storage order.  set_state: heads
+ * inside their rings, history_count < subsampling, frames_period 0 or in subsampling .. max_period, frames_count below it */
+int mi_scaled_metergraph_bank_get_state(mi_scaled_metergraph_bank_t *bank, uint32_t channel, mi_scaled_metergraph_state_t *state,
+                                        float *history, float *ring, void *stream);
+int mi_scaled_metergraph_bank_set_state(mi_scaled_metergraph_bank_t *bank, uint32_t channel, const mi_scaled_metergraph_state_t *state,
+                                        const float *history, const float *ring, void *stream);
+/* src [channels][stride] device rows, read only; gains: NULL, or a DEVICE array of `channels` floats; count < 2^31 */
+int mi_scaled_metergraph_bank_process(mi_scaled_metergraph_bank_t *bank, const float *src, const float *gains, size_t count, size_t stride,
+                                      void *stream);
+/* process(sample) of every channel, :344-349: values is a device array of `channels` floats */
+int mi_scaled_metergraph_bank_process_value(mi_scaled_metergraph_bank_t *bank, const float *values, void *stream);
+/* read(dst, count), :365-369, of every channel into dst [channels][stride]: the newest min(count, frames) frames, oldest first;
+ * what lies behind them in the row is not written.  level(): the newest frame, levels a device array [channels]. */
+int mi_scaled_metergraph_bank_read(mi_scaled_metergraph_bank_t *bank, float *dst, size_t count, size_t stride, void *stream);
+int mi_scaled_metergraph_bank_level(mi_scaled_metergraph_bank_t *bank, float *levels, void *stream);
+
 /*
  * Host-only introspection of the per-section device table (no GPU needed): the
  * chunk-parallel form of the TDF-II section used by the kernel.

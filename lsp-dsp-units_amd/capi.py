@@ -204,6 +204,18 @@ class MeterGraphParams(ctypes.Structure):
     _fields_ = [("method", c_uint32), ("period", c_uint32), ("frames", c_uint32), ("default_value", c_float)]
 
 
+class ScaledMeterGraphState(ctypes.Structure):
+    """mi_scaled_metergraph_state_t: sHistory's fCurrent, nCount, nHead; sFrames' three and sFrames.nPeriod."""
+    _fields_ = [("history_current", c_float), ("history_count", c_uint32), ("history_head", c_uint32), ("frames_current", c_float),
+                ("frames_count", c_uint32), ("frames_head", c_uint32), ("frames_period", c_uint32)]
+
+
+class ScaledMeterGraphParams(ctypes.Structure):
+    """mi_scaled_metergraph_params_t: enMethod, nPeriod, nMaxPeriod, sHistory.nPeriod, sFrames.nFrames, sHistory.nFrames."""
+    _fields_ = [("method", c_uint32), ("period", c_uint32), ("max_period", c_uint32), ("subsampling", c_uint32), ("frames", c_uint32),
+                ("subframes", c_uint32)]
+
+
 class SurgeParams(ctypes.Structure):
     """mi_surge_params_t: nTransitionMax, nShutdownMax, fOnThreshold, fOffThreshold."""
     _fields_ = [("transition_max", c_uint32), ("shutdown_max", c_uint32), ("on_threshold", c_float), ("off_threshold", c_float)]
@@ -847,6 +859,20 @@ PROTOTYPES = {
     "mi_metergraph_bank_process_value": (c_int, [c_void_p, c_void_p, c_void_p]),
     "mi_metergraph_bank_read": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
     "mi_metergraph_bank_level": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "mi_scaled_metergraph_bank_create": (c_int, [POINTER(c_void_p), c_uint32, c_uint32, c_uint32]),
+    "mi_scaled_metergraph_bank_destroy": (c_int, [c_void_p]),
+    "mi_scaled_metergraph_bank_init": (c_int, [c_void_p, c_uint32, c_size_t, c_size_t, c_size_t]),
+    "mi_scaled_metergraph_bank_set_method": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "mi_scaled_metergraph_bank_set_period": (c_int, [c_void_p, c_uint32, c_size_t]),
+    "mi_scaled_metergraph_bank_fill": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_scaled_metergraph_bank_update_settings": (c_int, [c_void_p, c_void_p]),
+    "mi_scaled_metergraph_bank_get_params": (c_int, [c_void_p, c_uint32, POINTER(ScaledMeterGraphParams)]),
+    "mi_scaled_metergraph_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(ScaledMeterGraphState), c_void_p, c_void_p, c_void_p]),
+    "mi_scaled_metergraph_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(ScaledMeterGraphState), c_void_p, c_void_p, c_void_p]),
+    "mi_scaled_metergraph_bank_process": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
+    "mi_scaled_metergraph_bank_process_value": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "mi_scaled_metergraph_bank_read": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
+    "mi_scaled_metergraph_bank_level": (c_int, [c_void_p, c_void_p, c_void_p]),
     "mi_oscillator_settings_init": (c_int, [POINTER(OscillatorSettings)]),
     "mi_oscillator_settings_set": (c_int, [POINTER(OscillatorSettings), c_uint32, c_double, c_double]),
     "mi_oscillator_settings_update": (c_int, [POINTER(OscillatorSettings)]),

@@ -2565,6 +2565,89 @@ class MeterGraphBank:
             pass
 
 
+class ScaledMeterGraphBank:
+    """`channels` x lsp::dspu::ScaledMeterGraph (mi_scaled_metergraph_bank_*): full-rate rows sampled into a history of sub-samples
+    and into a ring of display frames whose period can change; a new period re-decimates the history.  Methods as MeterGraphBank's."""
+    ALL = 0xFFFFFFFF
+    ABS_MAXIMUM, ABS_MINIMUM, SIGN_MAXIMUM, SIGN_MINIMUM, PEAK = range(5)
+    FRAMES_GAP = 16
+
+    def __init__(self, channels, max_frames, max_subframes):
+        h = c_void_p()
+        check(lib.mi_scaled_metergraph_bank_create(byref(h), channels, max_frames, max_subframes))
+        self.handle, self.channels, self.max_frames, self.max_subframes = h, channels, max_frames, max_subframes
+
+    def init(self, channel, frames, subsampling, max_period):
+        check(lib.mi_scaled_metergraph_bank_init(self.handle, channel, frames, subsampling, max_period))
+
+    def set_method(self, channel, method):
+        check(lib.mi_scaled_metergraph_bank_set_method(self.handle, channel, method))
+
+    def set_period(self, channel, period):
+        check(lib.mi_scaled_metergraph_bank_set_period(self.handle, channel, period))
+
+    def fill(self, level, channel=ALL):
+        check(lib.mi_scaled_metergraph_bank_fill(self.handle, channel, float(level)))
+
+    def update_settings(self, stream=None):
+        check(lib.mi_scaled_metergraph_bank_update_settings(self.handle, _stream(stream)))
+
+    def get_params(self, channel):
+        from .capi import ScaledMeterGraphParams
+        p = ScaledMeterGraphParams()
+        check(lib.mi_scaled_metergraph_bank_get_params(self.handle, channel, byref(p)))
+        return {n: getattr(p, n) for n, _ in ScaledMeterGraphParams._fields_}
+
+    def get_state(self, channel, stream=None):
+        """Both samplers' words (mi_scaled_metergraph_state_t's names) and both rings in storage order: "history", "ring"."""
+        from .capi import ScaledMeterGraphState
+        s = ScaledMeterGraphState()
+        p = self.get_params(channel)
+        rings = p["frames"] != 0
+        history = np.zeros(p["subframes"] + self.FRAMES_GAP if rings else 1, np.float32)
+        ring = np.zeros(p["frames"] + self.FRAMES_GAP if rings else 1, np.float32)
+        check(lib.mi_scaled_metergraph_bank_get_state(self.handle, channel, byref(s), history.ctypes.data_as(c_void_p), ring.ctypes.data_as(c_void_p),
+                                                      _stream(stream)))
+        out = {n: getattr(s, n) for n, _ in ScaledMeterGraphState._fields_}
+        out["history_current"], out["frames_current"] = np.float32(s.history_current), np.float32(s.frames_current)
+        out["history"], out["ring"] = (history, ring) if rings else (history[:0], ring[:0])
+        return out
+
+    def set_state(self, channel, state, history=None, ring=None, stream=None):
+        """state: a dict with mi_scaled_metergraph_state_t's names; history and ring: host arrays in storage order, or None."""
+        from .capi import ScaledMeterGraphState
+        s = ScaledMeterGraphState(*[(float if n.endswith("current") else int)(state[n]) for n, _ in ScaledMeterGraphState._fields_])
+        h = None if history is None else np.ascontiguousarray(history, np.float32)
+        r = None if ring is None else np.ascontiguousarray(ring, np.float32)
+        check(lib.mi_scaled_metergraph_bank_set_state(self.handle, channel, byref(s), None if h is None else h.ctypes.data_as(c_void_p),
+                                                      None if r is None else r.ctypes.data_as(c_void_p), _stream(stream)))
+
+    def process(self, src, count, gains=None, stride=None, stream=None):
+        """process(s, n) of every channel, or process(s, gain, n) with gains a device array of `channels` floats."""
+        check(lib.mi_scaled_metergraph_bank_process(self.handle, _opt(src), _opt(gains), count, count if stride is None else stride, _stream(stream)))
+
+    def process_value(self, values, stream=None):
+        """process(sample) of every channel: values is a device array of `channels` floats."""
+        check(lib.mi_scaled_metergraph_bank_process_value(self.handle, _opt(values), _stream(stream)))
+
+    def read(self, dst, count, stride=None, stream=None):
+        check(lib.mi_scaled_metergraph_bank_read(self.handle, _opt(dst), count, count if stride is None else stride, _stream(stream)))
+
+    def level(self, levels, stream=None):
+        check(lib.mi_scaled_metergraph_bank_level(self.handle, _opt(levels), _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            lib.mi_scaled_metergraph_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class SurgeProtectorBank:
     """`channels` x lsp::dspu::SurgeProtector (mi_surge_bank_*): a fade-in when the level row appears, a fade-out when it stops."""
     ALL = 0xFFFFFFFF
