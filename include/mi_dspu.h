@@ -2627,6 +2627,65 @@ int mi_scaled_metergraph_bank_process_value(mi_scaled_metergraph_bank_t *bank, c
 int mi_scaled_metergraph_bank_read(mi_scaled_metergraph_bank_t *bank, float *dst, size_t count, size_t stride, void *stream);
 int mi_scaled_metergraph_bank_level(mi_scaled_metergraph_bank_t *bank, float *levels, void *stream);
 
+/* ---- QuantizedCounter bank (sliding-window histograms of full-rate rows) -------------------------------------------------------- */
+/*
+ * mi_qcounter_bank: `channels` x lsp::dspu::QuantizedCounter (stat/QuantizedCounter.h, src/main/stat/QuantizedCounter.cpp).  Every
+ * channel keeps the histogram of the last `period` samples of its rows over `levels` quantisation levels of [min, max), with one
+ * counter for what lies below the range and one for above.  History ring, counters, nHead and nCount live on the device and are
+ * the reference's in every word:
+ *   - the bin of a sample is trunc((v - min) * rstep) in float32; where C++ leaves the reference's conversion undefined the bank
+ *     DEFINES it as the reference's compiled class has it: a NaN, a product >= 2^31 or <= -1 counts as below, one in
+ *     [levels, 2^31) as above;
+ *   - one process() call is one process(data, count) of every channel and leaves the window of the last min(period, samples seen)
+ *     samples for ANY count.  The reference does so only while count <= nCapacity - nPeriod (always for count <= 1024); beyond
+ *     that its single call corrupts its window, a defect that is not reproduced: the bank gives what the reference gives for the
+ *     same row fed in pieces of at most nCapacity - nPeriod;
+ *   - create() leaves every channel as construct() and init() do: no period, no levels, bUpdate set.  process() before
+ *     set_period() and set_levels() or set_range() is MI_ESTATE (the reference divides by zero into a meaningless state);
+ *   - the setters are host work; those that change levels, min or max set the channel's bUpdate, a setter that changes nothing
+ *     does not.  The recount under the new step (update_settings(), :162-187) is decided on the device by process() or by
+ *     update_settings(): it counts the nCount samples held, those beyond a reduced period included;
+ *   - read(), get_state(), set_state(), update_settings() and process() send changed settings and pending clear()s to the device
+ *     first; with something to send that is MI_ESTATE on a stream being captured.  read() recounts nothing;
+ *   - process(), update_settings() and read() are capturable: the kernel keeps nHead, nCount and which settings the counters were
+ *     counted under, so a replay counts its row again and recounts for a changed range at the first replay only.
+ */
+typedef struct mi_qcounter_bank mi_qcounter_bank_t;
+/* nPeriod, nLevels, fMinValue, fMaxValue, fRStep (that of the last update) and bUpdate */
+typedef struct { uint32_t period, levels; float min_value, max_value, rstep; uint32_t update; } mi_qcounter_params_t;
+typedef struct { uint32_t head, count, capacity; } mi_qcounter_state_t;                                  /* nHead, nCount, nCapacity */
+/* init(max_period, max_levels), :72-98: 1 <= max_levels <= 2^24, 1 <= max_period with a ring of max_period + 1024 samples (rounded
+ * up to 64 bytes) that fits 32 bits */
+int mi_qcounter_bank_create(mi_qcounter_bank_t **bank, uint32_t channels, size_t max_period, size_t max_levels);
+int mi_qcounter_bank_destroy(mi_qcounter_bank_t *bank);
+/* limited to 1 .. max_period; takes effect at the next process(): until then count may exceed period */
+int mi_qcounter_bank_set_period(mi_qcounter_bank_t *bank, uint32_t channel, size_t period);
+/* levels limited to 1 .. max_levels */
+int mi_qcounter_bank_set_levels(mi_qcounter_bank_t *bank, uint32_t channel, size_t levels);
+int mi_qcounter_bank_set_min_value(mi_qcounter_bank_t *bank, uint32_t channel, float min_value);
+int mi_qcounter_bank_set_max_value(mi_qcounter_bank_t *bank, uint32_t channel, float max_value);
+int mi_qcounter_bank_set_value_range(mi_qcounter_bank_t *bank, uint32_t channel, float min_value, float max_value);
+int mi_qcounter_bank_set_range(mi_qcounter_bank_t *bank, uint32_t channel, float min_value, float max_value, size_t levels);
+int mi_qcounter_bank_needs_update(const mi_qcounter_bank_t *bank, uint32_t channel, int *needs);
+/* the recount of every channel whose bUpdate is set, nothing evicted; MI_ESTATE where such a channel has no levels */
+int mi_qcounter_bank_update_settings(mi_qcounter_bank_t *bank, void *stream);
+/* clear(), :189-196: counters, nHead and nCount; the ring's words and bUpdate stay.  channel UINT32_MAX: all */
+int mi_qcounter_bank_clear(mi_qcounter_bank_t *bank, uint32_t channel);
+/* src [channels][stride] device rows, read only; count < 2^31, and a count of 0 still takes settings over and evicts */
+int mi_qcounter_bank_process(mi_qcounter_bank_t *bank, const float *src, size_t count, size_t stride, void *stream);
+/* counters [channels][stride] DEVICE words: with L the largest levels of any channel, words [0, L) are vCounters[0 .. L), word L
+ * is below() and word L + 1 above(); stride >= L + 2 */
+int mi_qcounter_bank_read(mi_qcounter_bank_t *bank, uint32_t *counters, size_t stride, void *stream);
+int mi_qcounter_bank_get_params(const mi_qcounter_bank_t *bank, uint32_t channel, mi_qcounter_params_t *params);
+/* ring: NULL, or a HOST array of nCapacity words in storage order; counters: NULL, or a HOST array of max_levels + 2 words as
+ * vCounters has them.  set_state: head < nCapacity, count <= nCapacity; state->capacity is not read */
+int mi_qcounter_bank_get_state(mi_qcounter_bank_t *bank, uint32_t channel, mi_qcounter_state_t *state, float *ring, uint32_t *counters,
+                               void *stream);
+int mi_qcounter_bank_set_state(mi_qcounter_bank_t *bank, uint32_t channel, const mi_qcounter_state_t *state, const float *ring,
+                               const uint32_t *counters, void *stream);
+/* measurements only: 0 compiles the wave-level combining of equal bins out of process() (the result is the same) */
+int mi_qcounter_bank_set_wave_combining(mi_qcounter_bank_t *bank, int on);
+
 /*
  * Host-only introspection of the per-section device table (no GPU needed): the
  * chunk-parallel form of the TDF-II section used by the kernel.

@@ -14,6 +14,6 @@ name carries the reference's name and is not a Python identifier).
 from .capi import LIB_PATH, MiError, check, lib          # noqa: F401
 from .units import (ADSREnvelopeBank, AnalyzerBank, AutoGainBank, BiquadBank, BypassBank, Comm, CompressorBank, ConvolverBank, CorrelometerBank, CrossfadeBank, CrossoverBank, DelayBank, DepopperBank, DeviceBuffer, DynFilterBank, DynamicDelayBank, DynamicProcessorBank, EqualizerBank,  # noqa: F401
                     ExpanderBank, GateBank, ILUFSBank, LCGBank, LimiterBank, LoudnessBank, MLSBank, MeterGraphBank, NoiseGeneratorBank, OscillatorBank, OversamplerBank, PanometerBank,
-                    PeakMeterBank, RingBank, ScaledMeterGraphBank, SidechainBank, SimpleAutoGainBank,
+                    PeakMeterBank, QuantizedCounterBank, RingBank, ScaledMeterGraphBank, SidechainBank, SimpleAutoGainBank,
                     SpectralBank, SpectralTiltBank, SurgeProtectorBank, SplitterBank, TruePeakBank, VelvetBank, crossover_fft_mask,
                     design_filter, device_count, last_launch, last_stream_clock, source_sha, dynfilter_freq_chart, dynfilter_sections, filter_freq_chart, make_window, make_window_general)

@@ -210,6 +210,17 @@ class ScaledMeterGraphState(ctypes.Structure):
                 ("frames_count", c_uint32), ("frames_head", c_uint32), ("frames_period", c_uint32)]
 
 
+class QuantizedCounterParams(ctypes.Structure):
+    """mi_qcounter_params_t: nPeriod, nLevels, fMinValue, fMaxValue, fRStep, bUpdate."""
+    _fields_ = [("period", c_uint32), ("levels", c_uint32), ("min_value", c_float), ("max_value", c_float), ("rstep", c_float),
+                ("update", c_uint32)]
+
+
+class QuantizedCounterState(ctypes.Structure):
+    """mi_qcounter_state_t: nHead, nCount, nCapacity."""
+    _fields_ = [("head", c_uint32), ("count", c_uint32), ("capacity", c_uint32)]
+
+
 class ScaledMeterGraphParams(ctypes.Structure):
     """mi_scaled_metergraph_params_t: enMethod, nPeriod, nMaxPeriod, sHistory.nPeriod, sFrames.nFrames, sHistory.nFrames."""
     _fields_ = [("method", c_uint32), ("period", c_uint32), ("max_period", c_uint32), ("subsampling", c_uint32), ("frames", c_uint32),
@@ -873,6 +884,23 @@ PROTOTYPES = {
     "mi_scaled_metergraph_bank_process_value": (c_int, [c_void_p, c_void_p, c_void_p]),
     "mi_scaled_metergraph_bank_read": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
     "mi_scaled_metergraph_bank_level": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "mi_qcounter_bank_create": (c_int, [POINTER(c_void_p), c_uint32, c_size_t, c_size_t]),
+    "mi_qcounter_bank_destroy": (c_int, [c_void_p]),
+    "mi_qcounter_bank_set_period": (c_int, [c_void_p, c_uint32, c_size_t]),
+    "mi_qcounter_bank_set_levels": (c_int, [c_void_p, c_uint32, c_size_t]),
+    "mi_qcounter_bank_set_min_value": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_qcounter_bank_set_max_value": (c_int, [c_void_p, c_uint32, c_float]),
+    "mi_qcounter_bank_set_value_range": (c_int, [c_void_p, c_uint32, c_float, c_float]),
+    "mi_qcounter_bank_set_range": (c_int, [c_void_p, c_uint32, c_float, c_float, c_size_t]),
+    "mi_qcounter_bank_needs_update": (c_int, [c_void_p, c_uint32, POINTER(c_int)]),
+    "mi_qcounter_bank_update_settings": (c_int, [c_void_p, c_void_p]),
+    "mi_qcounter_bank_clear": (c_int, [c_void_p, c_uint32]),
+    "mi_qcounter_bank_process": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
+    "mi_qcounter_bank_read": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mi_qcounter_bank_get_params": (c_int, [c_void_p, c_uint32, POINTER(QuantizedCounterParams)]),
+    "mi_qcounter_bank_get_state": (c_int, [c_void_p, c_uint32, POINTER(QuantizedCounterState), c_void_p, c_void_p, c_void_p]),
+    "mi_qcounter_bank_set_state": (c_int, [c_void_p, c_uint32, POINTER(QuantizedCounterState), c_void_p, c_void_p, c_void_p]),
+    "mi_qcounter_bank_set_wave_combining": (c_int, [c_void_p, c_int]),
     "mi_oscillator_settings_init": (c_int, [POINTER(OscillatorSettings)]),
     "mi_oscillator_settings_set": (c_int, [POINTER(OscillatorSettings), c_uint32, c_double, c_double]),
     "mi_oscillator_settings_update": (c_int, [POINTER(OscillatorSettings)]),

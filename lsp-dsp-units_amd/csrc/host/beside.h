@@ -14,7 +14,7 @@
 // dspu_classes.cpp `staging`, the gain rows of DynamicFilters and Delay and the impls of MultiSpectralProcessor, LoudnessMeter
 // and ILUFSMeter.  registry with an entry of their own: Sidechain and Limiter.  registry<beside<>>: Compressor, Expander, Gate,
 // DynamicProcessor, AutoGain, SimpleAutoGain, Correlometer, Panometer, PeakMeter, SurgeProtector, Bypass, Crossfade, Depopper,
-// ADSREnvelope, MeterGraph and ScaledMeterGraph.
+// ADSREnvelope, MeterGraph, ScaledMeterGraph and QuantizedCounter.
 #pragma once
 #include <cstring>
 #include <mutex>

@@ -2648,6 +2648,92 @@ class ScaledMeterGraphBank:
             pass
 
 
+class QuantizedCounterBank:
+    """`channels` x lsp::dspu::QuantizedCounter (mi_qcounter_bank_*): the histogram of the last `period` samples of every row over
+    `levels` quantisation levels of [min, max), with a counter for what lies below the range and one for above, on the device."""
+    ALL = 0xFFFFFFFF
+
+    def __init__(self, channels, max_period, max_levels):
+        h = c_void_p()
+        check(lib.mi_qcounter_bank_create(byref(h), channels, max_period, max_levels))
+        self.handle, self.channels, self.max_period, self.max_levels = h, channels, max_period, max_levels
+
+    def set_period(self, channel, period):
+        check(lib.mi_qcounter_bank_set_period(self.handle, channel, period))
+
+    def set_levels(self, channel, levels):
+        check(lib.mi_qcounter_bank_set_levels(self.handle, channel, levels))
+
+    def set_min_value(self, channel, value):
+        check(lib.mi_qcounter_bank_set_min_value(self.handle, channel, float(value)))
+
+    def set_max_value(self, channel, value):
+        check(lib.mi_qcounter_bank_set_max_value(self.handle, channel, float(value)))
+
+    def set_value_range(self, channel, min_value, max_value):
+        check(lib.mi_qcounter_bank_set_value_range(self.handle, channel, float(min_value), float(max_value)))
+
+    def set_range(self, channel, min_value, max_value, levels):
+        check(lib.mi_qcounter_bank_set_range(self.handle, channel, float(min_value), float(max_value), levels))
+
+    def needs_update(self, channel):
+        v = ctypes.c_int()
+        check(lib.mi_qcounter_bank_needs_update(self.handle, channel, byref(v)))
+        return bool(v.value)
+
+    def update_settings(self, stream=None):
+        check(lib.mi_qcounter_bank_update_settings(self.handle, _stream(stream)))
+
+    def clear(self, channel=ALL):
+        check(lib.mi_qcounter_bank_clear(self.handle, channel))
+
+    def process(self, src, count, stride=None, stream=None):
+        check(lib.mi_qcounter_bank_process(self.handle, _opt(src), count, count if stride is None else stride, _stream(stream)))
+
+    def read(self, counters, stride, stream=None):
+        """counters: a device array [channels, stride] of uint32: the bins of the largest `levels`, then below, then above."""
+        check(lib.mi_qcounter_bank_read(self.handle, _opt(counters), stride, _stream(stream)))
+
+    def set_wave_combining(self, on):
+        check(lib.mi_qcounter_bank_set_wave_combining(self.handle, int(bool(on))))
+
+    def get_params(self, channel):
+        from .capi import QuantizedCounterParams
+        p = QuantizedCounterParams()
+        check(lib.mi_qcounter_bank_get_params(self.handle, channel, byref(p)))
+        return {"period": p.period, "levels": p.levels, "min_value": np.float32(p.min_value), "max_value": np.float32(p.max_value),
+                "rstep": np.float32(p.rstep), "update": bool(p.update)}
+
+    def get_state(self, channel, stream=None):
+        """nHead, nCount, nCapacity, the ring's words in storage order and vCounters' max_levels + 2 words."""
+        from .capi import QuantizedCounterState
+        s = QuantizedCounterState()
+        check(lib.mi_qcounter_bank_get_state(self.handle, channel, byref(s), None, None, _stream(stream)))
+        ring, counters = np.zeros(s.capacity, np.float32), np.zeros(self.max_levels + 2, np.uint32)
+        check(lib.mi_qcounter_bank_get_state(self.handle, channel, byref(s), ring.ctypes.data_as(c_void_p), counters.ctypes.data_as(c_void_p),
+                                             _stream(stream)))
+        return {"head": s.head, "count": s.count, "capacity": s.capacity, "ring": ring, "counters": counters}
+
+    def set_state(self, channel, head, count, ring=None, counters=None, stream=None):
+        from .capi import QuantizedCounterState
+        s = QuantizedCounterState(head, count, 0)
+        r = None if ring is None else np.ascontiguousarray(ring, np.float32)
+        c = None if counters is None else np.ascontiguousarray(counters, np.uint32)
+        check(lib.mi_qcounter_bank_set_state(self.handle, channel, byref(s), None if r is None else r.ctypes.data_as(c_void_p),
+                                             None if c is None else c.ctypes.data_as(c_void_p), _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            lib.mi_qcounter_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class SurgeProtectorBank:
     """`channels` x lsp::dspu::SurgeProtector (mi_surge_bank_*): a fade-in when the level row appears, a fade-out when it stops."""
     ALL = 0xFFFFFFFF
